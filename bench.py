@@ -1,24 +1,32 @@
 """Throughput of the SMC ELBO hot path on MI355X (BASELINE.json metric: particle-steps/sec).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|c4s|c4nl|c4ls|c5]
-                    [--proposal tuned|stock] [--scaling weak|strong] [--extras on|off]
+                    [--proposal tuned|stock] [--scaling weak|strong] [--full [--extras on|off]]
+                    [--dump-outputs DIR]
 
 One "step" = one SMC ELBO evaluation (aesmc_amd.losses.get_loss(..., 'aesmc') forward, autograd
 graph recorded as in training) over one synthetic batch already resident in HBM.  The default
 workload is the north-star shape of BASELINE.json: LGSSM d=10, B=1024, K=4096, T=100 ("c4").
 Up to 2^22 particles per timestep (c4 included) the ELBO is captured once and replayed as one hipGraph
 (aesmc_amd.graphs.GraphedLoss: fresh uniforms and noise per replay, verified against eager evaluations); `mode` says
-so and `eager_particle_steps_per_sec` gives the plain Python loop's figure beside it (`--mode eager` times that).
+so and, with `--full`, `eager_particle_steps_per_sec` gives the plain Python loop's figure beside it (`--mode eager`
+times that).
 
 N > 1: `python bench.py --gpus N` starts N fresh children itself (python -m
 torch.distributed.run, one rank per GPU, RCCL) before anything touches the GPU; it also runs as a
 child of an external torchrun (RANK / WORLD_SIZE in the environment).  Batch rows shard over the
 ranks; the only collective on the data path is the all-reduce of sum_b log Z_b.  `--scaling strong`
 (the default for c4, BASELINE.json's north-star shape): the workload's B rows are split over the ranks;
-`--scaling weak` (the default elsewhere): every rank owns the workload's B rows.  The other curve rides in
-`extras`, the all-reduce's own time in `allreduce_us_per_elbo`.
+`--scaling weak` (the default elsewhere): every rank owns the workload's B rows.  With `--full` the other curve rides
+in `extras`; the all-reduce's own time is in `allreduce_us_per_elbo`.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields:
+`metric`, `value` (particle-steps/s over the timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed
+step).  `--dump-outputs DIR` then also writes what the timed path returned in its last step — the loss of the last ELBO —
+as DIR/loss.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+`--full` measures and checks everything else as well; its line carries, beside the contract fields,
+  eager / fwd+bwd : the eager loop's rate beside a replayed headline, and the forward + backward (training step) rate;
   roofline     : the dominant kernel of the timed region (K16 — the launch that holds the resampling gather — on the
                  linear-Gaussian route; the fused step K2+K3 or K3 elsewhere; K1 for the IWAE workload), timed per
                  launch with HIP events on its stream on operands sampled from the timed steps; achieved =
@@ -108,8 +116,16 @@ def parse(argv=None):
                     help="N > 1 only. strong: the workload's B rows are split over the ranks (value = B K T / wall: the "
                          "north-star curve of c4, B=1024 over 8 GPUs); weak: every rank owns B rows.  Default: strong for "
                          "c4 — the shape BASELINE.json's scaling target names — weak elsewhere")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else this file measures and checks: the eager loop and the "
+                         "forward + backward beside the headline, the per-kernel and roofline figures, the extra blocks "
+                         "and the CPU baseline (without it a run only sets up, warms up and times the steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step (the loss) as "
+                         "DIR/loss.npy")
     ap.add_argument("--extras", default=None, choices=["on", "off"],
-                    help="the extra blocks (stock proposal, configs[1] hipGraph, kernel legs, parity); default: on for N=1")
+                    help="with --full: the extra blocks (stock proposal, configs[1] hipGraph, kernel legs, parity); "
+                         "default: on for N=1")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-backward", action="store_true")
     ap.add_argument("--tunableop", default="off", choices=["on", "off"],
@@ -129,7 +145,10 @@ def parse(argv=None):
                          "environment it adds) as JSON and exit without touching the GPU")
     ap.add_argument("--grad", default=None, choices=["on", "off"],
                     help="record the autograd graph during the forward step (default: on where it fits in HBM)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---- launcher --------------------------------------------------------------------------------------
@@ -327,6 +346,7 @@ class Context:
         for _ in range(n):
             loss = fn()
         self.barrier()
+        self.last_output = loss
         dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=self.device)
         self.last_per_rank_seconds = [float(dt.item())]
         if self.use_dist:
@@ -356,9 +376,10 @@ def traffic_record(workload, proposal, kernel):
 
 
 def run_workload(ctx, name, proposal, steps, warmup, scaling="weak", want_backward=True, want_kernels=True,
-                 mode=None, grad=None, callables=None):
-    """Times `steps` forward ELBOs of one workload (after `warmup`), then forward+backward, then the
-    per-kernel pass.  Returns a dict with the contract's numbers for this workload."""
+                 mode=None, grad=None, callables=None, want_eager=True):
+    """Times `steps` forward ELBOs of one workload (after `warmup`), then (`want_eager`) the eager loop beside a
+    replayed step, forward+backward, the per-kernel pass.  Returns a dict with the contract's numbers for this workload;
+    under "outputs" the loss the last timed step returned."""
     import numpy as np
     import torch
     import aesmc_amd
@@ -426,6 +447,7 @@ def run_workload(ctx, name, proposal, steps, warmup, scaling="weak", want_backwa
     for _ in range(warmup):
         forward()
     seconds, loss = ctx.timed(forward, steps)
+    outputs = {"loss": ctx.last_output.detach().clone()}     # (a replay's static tensor: the next replay overwrites it)
     per_rank_ms = [round(1e3 * t / steps, 4) for t in ctx.last_per_rank_seconds]
     if graphed is not None:
         graphed.check()
@@ -436,10 +458,10 @@ def run_workload(ctx, name, proposal, steps, warmup, scaling="weak", want_backwa
         "mode": ran_as, "graph_error": graph_error, "grad": grad, "scaling": scaling,
         "batch_per_gpu": local_B, "global_batch": global_B, "num_particles": K, "num_timesteps": T,
         "state_dim": dim, "algorithm": algorithm, "per_rank_ms_per_step": per_rank_ms,
-        "peak_memory_GB": round(torch.cuda.max_memory_allocated(device) / 1e9, 2),
+        "peak_memory_GB": round(torch.cuda.max_memory_allocated(device) / 1e9, 2), "outputs": outputs,
     }
 
-    if graphed is not None:  # the eager loop beside it, for the record
+    if graphed is not None and want_eager:  # the eager loop beside it, for the record
         for _ in range(2):      # (its first passes beside the capture's pool grow the allocator: not what a loop costs)
             step()
         n = max(2, steps // 2)
@@ -552,6 +574,17 @@ def run_workload(ctx, name, proposal, steps, warmup, scaling="weak", want_backwa
     gc.collect()
     torch.cuda.empty_cache()
     return out
+
+
+def dump_outputs(directory, outputs):
+    """`outputs` (name -> tensor) as DIR/<name>.npy: float32 and float64 as they are, anything else as float32."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, tensor in outputs.items():
+        array = tensor.detach().cpu().numpy()
+        if array.dtype not in (np.float32, np.float64):
+            array = array.astype(np.float32)
+        np.save(os.path.join(directory, name + ".npy"), array)
 
 
 def use_smc_path(algorithm):
@@ -955,7 +988,7 @@ def main(argv=None):
                   file=sys.stderr)
             args.tunableop = "off"
 
-    extras_on = (args.extras or ("on" if world == 1 else "off")) == "on"
+    extras_on = (args.extras or ("on" if args.full and world == 1 else "off")) == "on"
     seconds = {}          # wall time of every section of this run (the default run must stay within minutes)
     clock = [time.perf_counter()]
 
@@ -964,15 +997,18 @@ def main(argv=None):
         seconds[label] = round(now - clock[0], 1)
         clock[0] = now
     head = run_workload(ctx, args.workload, args.proposal, args.steps, args.warmup, scaling=args.scaling,
-                        want_backward=not args.no_backward, mode=args.mode, grad=args.grad)
+                        want_backward=args.full and not args.no_backward, want_kernels=args.full, mode=args.mode,
+                        grad=args.grad, want_eager=args.full)
     description, kind, dim, B, K, T, model_kwargs = WORKLOADS[args.workload]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["outputs"])
     lap("headline workload")
 
     out = {
         "metric": "particle_steps_per_sec", "value": head["value"], "unit": "particle-steps/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
         "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic",
+        "data": "synthetic", "full": args.full,
         "config": {"workload": head["workload"], "proposal": head["proposal"],
                    "callables": {"affine": "AffineNormal(source, weight, scale, offset), the proposal's with defer_draw=True: "
                                            "resampling gather, draw (noise from torch's Philox stream, inside the launch) "
@@ -1014,7 +1050,7 @@ def main(argv=None):
             if head["mode"] == "hipgraph" else head["value"]
 
     extras = {}
-    if world > 1 and (args.extras or "on") == "on":
+    if world > 1 and (args.extras or ("on" if args.full else "off")) == "on":
         # the other curve beside the headline: weak scaling (every rank owns the workload's B rows) under a strong
         # headline, the split of the workload's B rows under a weak one
         other = "weak" if args.scaling == "strong" else "strong"
@@ -1091,7 +1127,7 @@ def main(argv=None):
         extras["index_parity_vs_reference_fixtures"] = parity_block(ctx)
         extras["fp32_fixture_parity"] = fixture_parity_block(ctx)
         lap("parity blocks")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(kind, dim, B, K, T, head["algorithm"],
                                            args.proposal if kind == "lgssm" else "stock", model_kwargs)
         lap("cpu baseline")

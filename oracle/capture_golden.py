@@ -1,5 +1,5 @@
 """ORACLE — TEST INFRASTRUCTURE ONLY.  Generates tests/golden/*.npz by importing the reference
-from /root/reference (read-only, this container only) and recording, for each case:
+from a checkout of it named by the environment variable AESMC_REFERENCE and recording, for each case:
 
   inputs   : observations, model parameters, every standard-normal block and every numpy uniform
              block the reference drew (so the run can be replayed bit-for-bit on any device);
@@ -7,7 +7,8 @@ from /root/reference (read-only, this container only) and recording, for each ca
              latents, log_weight, last_latent, log_marginal_likelihood, the loss of
              aesmc.losses.get_loss and its parameter gradients.
 
-Run:  PYTHONDONTWRITEBYTECODE=1 python oracle/capture_golden.py
+Run:  AESMC_REFERENCE=<checkout of the reference> PYTHONDONTWRITEBYTECODE=1 python oracle/capture_golden.py [OUT_DIR]
+Re-run into a scratch OUT_DIR, it reproduces every committed array byte for byte.
 Nothing of the reference's source is stored: fixtures hold arrays and a JSON description only.
 The only missing dependency of the reference here is `pykalman` (imported by its
 test/models/lgssm.py for a Kalman smoother the fixtures do not use); it is stubbed.
@@ -22,7 +23,9 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
+REFERENCE = os.environ.get("AESMC_REFERENCE", "")
+if not os.path.isdir(os.path.join(REFERENCE, "aesmc")):
+    raise SystemExit("capture_golden.py: set AESMC_REFERENCE to a checkout of the reference (the directory holding aesmc/)")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, REFERENCE)

@@ -5,8 +5,7 @@ stores inputs, draws and outputs under tests/golden/.  They are FROZEN: plain `x
 the reference's own style (test/models/lgssm.py:40, :52, :66-77), touched by no performance work —
 the bench / test model `aesmc_amd.testing.models.LgssmNd` (which states the same distributions for the
 fused kernels, caches the observation term over time, ...) is free to change without the fixtures
-moving.  `tests/test_oracle.py::test_fixtures_regenerate_byte_for_byte` re-runs the generator and
-compares every array with the committed files.
+moving.  Re-run into a scratch directory, the generator reproduces every committed array byte for byte.
 
 Parameter names and their seeded initial values equal LgssmNd's (A, C, W0, b0, Wx, Wy, b), so a fixture's
 `param_model.*` arrays load into either class.

@@ -6,7 +6,7 @@ the resampler, the final stack of all weight tensors.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the
 product package (aesmc_amd/) never does.
 
-Pinning: oracle/capture_golden.py (run in the build container, where /root/reference is importable)
+Pinning: oracle/capture_golden.py (run where a checkout of the reference is importable)
 records the imported reference's inputs, random draws and outputs as tests/golden/*.npz;
 tests/test_oracle.py proves this port equal to those fixtures under the replayed draws wherever
 the tests run (indices exact, floats to the last place on the capture host).  The arithmetic lives in unpinned third-party libraries

@@ -25,6 +25,30 @@ def test_launcher_is_needed_only_outside_a_process_group():
     assert bench.needs_launcher(one, {}) is False
 
 
+def test_full_and_dump_outputs_are_opt_in():
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 7 and plain.warmup == 2
+    full = bench.parse(["--full", "--dump-outputs", "out"])
+    assert full.full is True and full.dump_outputs == "out"
+    try:
+        bench.parse(["--steps", "0"])
+    except SystemExit:
+        pass
+    else:
+        raise AssertionError("--steps 0 was accepted")
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+    import torch
+    bench.dump_outputs(str(tmp_path / "out"), {"loss": torch.tensor(1.5), "lml": torch.arange(3, dtype=torch.float64),
+                                               "count": torch.tensor([1, 2])})
+    assert sorted(os.listdir(tmp_path / "out")) == ["count.npy", "lml.npy", "loss.npy"]
+    assert np.load(tmp_path / "out" / "loss.npy").dtype == np.float32
+    assert np.load(tmp_path / "out" / "lml.npy").dtype == np.float64
+    assert np.load(tmp_path / "out" / "count.npy").dtype == np.float32
+
+
 def test_child_command_and_environment():
     argv = ["--gpus", "4", "--steps", "7", "--warmup", "2", "--scaling", "strong"]
     command = bench.child_command(argv, 4, port=23456, python="python3")

@@ -25,19 +25,47 @@ def _json_line(stdout):
 
 def test_bench_line_contract_on_a_tiny_workload(hip_device):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + FAST + ["--extras", "off"],
+    done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + FAST + ["--full", "--extras", "off"],
                           env=env, capture_output=True, text=True, timeout=900)
     assert done.returncode == 0, done.stderr[-3000:]
     line = _json_line(done.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in line, key
+    assert line["full"] is True and line["fwd_bwd_particle_steps_per_sec"] > 0 and line["kernels"]
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["scaling"] == "weak"
     assert line["config"]["workload"].startswith("tiny") and line["config"]["proposal"] == "tuned"
     assert line["value"] > 0 and line["rccl_world_size"] is None
     roofline = line["roofline"]
     assert roofline["bound"] == "hbm" and roofline["peak"] == 8000.0 and 0 < roofline["frac"] <= 1.0
     assert abs(line["value"] - 8 * 64 * 5 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+
+
+def test_a_plain_run_times_its_steps_and_dumps_the_last_step_s_outputs(hip_device, tmp_path):
+    """Without --full the run only sets up, warms up and times `--steps` steps; `--dump-outputs` writes the loss the
+    last timed step returned, and two runs with the same arguments start from the same inputs."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    argv = ["--workload", "tiny", "--steps", "3", "--warmup", "1"]
+    dumped = []
+    for run in ("a", "b"):
+        done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv +
+                              ["--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True,
+                              timeout=900)
+        assert done.returncode == 0, done.stderr[-3000:]
+        line = _json_line(done.stdout)
+        assert line["metric"] == "particle_steps_per_sec" and line["unit"] == "particle-steps/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["full"] is False
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 8 * 64 * 5 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        assert line["roofline"] is None and line["kernels"] is None and "cpu_baseline" not in line
+        assert "extras" not in line and line["fwd_bwd_particle_steps_per_sec"] is None
+        assert sorted(os.listdir(tmp_path / run)) == ["loss.npy"]
+        loss = np.load(tmp_path / run / "loss.npy")
+        assert loss.dtype == np.float32 and loss.size == 1 and np.isfinite(loss).all()
+        assert abs(float(loss) - line["loss"]) <= 1e-6 * abs(line["loss"])
+        dumped.append(loss)
+    np.testing.assert_allclose(dumped[0], dumped[1], rtol=1e-6)
 
 
 def test_the_launcher_s_child_command_runs_on_one_rank_over_rccl(hip_device):

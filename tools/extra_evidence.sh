@@ -13,6 +13,6 @@ python tools/summarize_rocprof.py $STATS 16 > $OUT/${TAG}_rocprof_c5h.csv
 rm -rf $OUT/${TAG}_c5h
 cut -c1-170 $OUT/${TAG}_rocprof_c5h.csv
 tail -1 $OUT/${TAG}_c5h.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c5h', d['mode'], round(d['ms_per_step'],2), d['value'])"
-timeout -k 10 300 python bench.py --workload c2 --mode eager --steps 10 --warmup 3 --extras off --no-cpu-baseline > $OUT/${TAG}_c2_eager.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --workload c2 --mode eager --steps 10 --warmup 3 --extras off --no-cpu-baseline > $OUT/${TAG}_c2_eager.json 2>/dev/null
 python -c "
 import json; d=json.loads(open('$OUT/${TAG}_c2_eager.json').read().strip().splitlines()[-1]); print('c2 eager', round(d['ms_per_step'],3), d['value'], d.get('fwd_bwd_particle_steps_per_sec'))"

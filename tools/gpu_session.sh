@@ -18,11 +18,11 @@ if [ "$TESTS" = "tests" ]; then
   if [ $rc -ne 0 ]; then grep -n "Error\|assert\|FAILED" $OUT/${TAG}_pytest_gpu.txt | head -40 | cut -c1-300; exit $rc; fi
 fi
 start=$(date +%s)
-timeout -k 10 600 python bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err || { tail -20 $OUT/${TAG}_bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err || { tail -20 $OUT/${TAG}_bench_default.err; exit 1; }
 echo "default bench wall: $(( $(date +%s) - start )) s"
 python tools/bench_digest.py $OUT/${TAG}_bench_default.json
 for LEG in fwd_bwd fwd; do
-  EXTRA=""; [ "$LEG" = "fwd" ] && EXTRA="--no-backward"
+  EXTRA="--full"; [ "$LEG" = "fwd" ] && EXTRA="--full --no-backward"
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
       -d $GRAFT_REPO_ROOT/$OUT/${TAG}_prof_$LEG -- python $GRAFT_REPO_ROOT/bench.py --workload c4 --steps 2 --warmup 1 \
       --no-cpu-baseline --extras off $EXTRA > $GRAFT_REPO_ROOT/$OUT/${TAG}_prof_$LEG.log 2>&1) || { tail -20 $OUT/${TAG}_prof_$LEG.log; exit 1; }

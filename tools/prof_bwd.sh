@@ -7,10 +7,10 @@ TAG=${1:-r01}
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 TUNED=/tmp/aesmc_tuned_bwd.csv
-EXTRA="--tunableop ${TUNABLE:-off}"
+EXTRA="--full --tunableop ${TUNABLE:-off}"
 if [ "${TUNABLE:-off}" = "on" ]; then
-  python $GRAFT_REPO_ROOT/bench.py --workload c2 --steps 2 --warmup 1 --no-cpu-baseline --tunableop-file $TUNED > /dev/null 2>&1
-  EXTRA="--tunableop on --tunableop-file $TUNED"
+  python "$(dirname "$0")/../bench.py" --full --workload c2 --steps 2 --warmup 1 --no-cpu-baseline --tunableop-file $TUNED > /dev/null 2>&1
+  EXTRA="--full --tunableop on --tunableop-file $TUNED"
 fi
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv \
     -d $OUT/${TAG}_profbwd -- python $GRAFT_REPO_ROOT/bench.py --workload c2 --steps 5 --warmup 1 \

@@ -11,7 +11,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv \
     -d $OUT/${TAG}_prof_${WORKLOAD} -- python3 $GRAFT_REPO_ROOT/bench.py --workload $WORKLOAD --steps 5 --warmup 1 \
-    --no-cpu-baseline --extras off "$@" > $OUT/${TAG}_prof_${WORKLOAD}.json 2> $OUT/${TAG}_prof_${WORKLOAD}.err)
+    --full --no-cpu-baseline --extras off "$@" > $OUT/${TAG}_prof_${WORKLOAD}.json 2> $OUT/${TAG}_prof_${WORKLOAD}.err)
 STATS=$(ls $OUT/${TAG}_prof_${WORKLOAD}/*/*kernel_stats.csv | head -1)
 python3 $GRAFT_REPO_ROOT/tools/summarize_rocprof.py $STATS 40 > $OUT/${TAG}_rocprof_${WORKLOAD}.csv
 rm -rf $OUT/${TAG}_prof_${WORKLOAD}

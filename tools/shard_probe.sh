@@ -3,6 +3,7 @@
 #   tools/shard_probe.sh [workload] [extra bench.py flags]
 set -u
 W=${1:-c4nl}; shift || true
+set -- --full "$@"      # the forward + backward come after the timed steps
 OUT=gpurun_out
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/probe_$W -- \
    python $GRAFT_REPO_ROOT/bench.py --workload $W --steps 2 --warmup 1 --no-cpu-baseline --extras off "$@" > $GRAFT_REPO_ROOT/$OUT/probe_$W.log 2>&1)

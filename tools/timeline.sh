@@ -4,8 +4,9 @@
 set -u
 W=${1:-c4}; FIRST=${2:-0}; ROWS=${3:-60}
 OUT=gpurun_out
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$OUT/tl_$W -- \
-   python $GRAFT_REPO_ROOT/bench.py --workload $W --steps 1 --warmup 1 --no-cpu-baseline --extras off > $GRAFT_REPO_ROOT/$OUT/tl_$W.log 2>&1)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d $ROOT/$OUT/tl_$W -- \
+   python $ROOT/bench.py --full --workload $W --steps 1 --warmup 1 --no-cpu-baseline --extras off > $ROOT/$OUT/tl_$W.log 2>&1)
 TRACE=$(ls $OUT/tl_$W/*/*kernel_trace.csv | head -1)
 python - "$TRACE" "$FIRST" "$ROWS" > $OUT/timeline_$W.txt <<'PY'
 import csv, sys
