@@ -49,12 +49,15 @@ def _ptr(t):
 
 
 _NO_SWITCH = contextlib.nullcontext()
+# torch.cuda.current_device() without its lazy-initialisation checks: a launch's operands already live on the device
+_current_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def _on_device(device):
     """Context that makes `device` current for the launch; free when it already is (the usual
     case: entering torch.cuda.device costs ~4 us of host time per kernel in the eager loop)."""
-    if torch.cuda.current_device() == device.index:
+    if _current_device() == device.index:
         return _NO_SWITCH
     return torch.cuda.device(device)
 
@@ -235,42 +238,73 @@ class HipKernels:
     def _stream(t):
         # the raw handle of torch's current stream on t's device (torch.cuda.current_stream builds a Stream
         # object around the same call: 3 us of host time per launch)
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        if raw is not None:
-            return raw(t.device.index if t.device.index is not None else torch.cuda.current_device())
+        if _raw_stream is not None:
+            return _raw_stream(t.device.index if t.device.index is not None else torch.cuda.current_device())
         return torch.cuda.current_stream(t.device).cuda_stream
+
+    # ---- the one launch path and the operand checks the wrappers share -------------------------
+    def _launch(self, device, entry, args, nbytes=None, keep=(), name=None, decline=False):
+        """Enqueues `entry(*args)` (a C-ABI entry point; the stream is the LAST of `args`) with `device` current and
+        raises on a failing status.  `decline`: the library's "unsupported shape" (nothing was launched) returns False
+        instead, for the caller's other route.  With a KernelTimer installed the launch is recorded under `name` (default:
+        the entry point's name without "aesmc_"), `nbytes()` its algorithmic traffic, `keep` everything whose address
+        is in `args` (the timer replays them after the caller has returned); `nbytes` None: never timed."""
+        with _on_device(device):
+            status = entry(*args)
+        if status != _lib.OK:
+            if decline and status == _lib.ERR_UNSUPPORTED:
+                return False
+            _lib.check(status, entry.__name__)
+        if self.timer is not None and nbytes is not None:
+            self.timer.note(name or entry.__name__[6:], (entry, args), nbytes(), keep)
+        return True
+
+    @staticmethod
+    def _expect(t, shape, like, what):
+        """ValueError unless `t` has `shape` and `like`'s dtype and device."""
+        if t.shape != shape or t.dtype != like.dtype or t.device != like.device:
+            raise ValueError("aesmc_amd: {} must be {} {} on {}, got {} {} on {}".format(
+                what, tuple(shape), like.dtype, like.device, tuple(t.shape), t.dtype, t.device))
+
+    @staticmethod
+    def _rows_operand(t, what):
+        """The dtype tag of a [batch_size, num_particles] float tensor on the HIP device."""
+        _require_hip(t, what)
+        tag = _tag(t, what)
+        if t.dim() != 2:
+            raise ValueError("aesmc_amd: {} must be [batch_size, num_particles], got {}".format(what, tuple(t.shape)))
+        return tag
+
+    def _resampling_operands(self, log_w, u):
+        """(tag, B, K) of K2's operands: log_w [B,K] float32/64, u B float64 values on its device."""
+        _require_hip(log_w, "log_weight")
+        _require_hip(u, "uniforms")
+        tag = self._rows_operand(log_w, "log_weight")
+        B, K = log_w.shape
+        if u.dtype != torch.float64 or u.numel() != B or u.device != log_w.device:
+            raise ValueError("aesmc_amd: uniforms must be {} float64 values on {}".format(B, log_w.device))
+        return tag, B, K
 
     # ---- K1 ------------------------------------------------------------------------------------
     def logweight_lse(self, a, b=None, c=None, want_lw=True, want_lse=True):
         """lw = a + b - c over [B,K]; lse[b] = logsumexp_k lw.  Returns (lw or None, lse or None)."""
-        _require_hip(a, "log-prob term")
-        tag = _tag(a, "log-prob term")
-        if a.dim() != 2:
-            raise ValueError("aesmc_amd: log-prob terms must be [batch_size, num_particles], got {}"
-                             .format(tuple(a.shape)))
-        terms = [a]
+        tag = self._rows_operand(a, "log-prob terms")
         for t in (b, c):
             if t is not None:
                 _require_hip(t, "log-prob term")
-                if t.shape != a.shape or t.dtype != a.dtype or t.device != a.device:
-                    raise ValueError("aesmc_amd: log-prob terms disagree: {} {} {} vs {} {} {}".format(
-                        tuple(t.shape), t.dtype, t.device, tuple(a.shape), a.dtype, a.device))
-            terms.append(t)
-        a, b, c = [None if t is None else t.contiguous() for t in terms]
+                self._expect(t, a.shape, a, "log-prob term")
+        a, b, c = [None if t is None else t.contiguous() for t in (a, b, c)]
         B, K = a.shape
         if b is None and c is None and not want_lse:
             return (a if want_lw else None), None
         need_lw = want_lw and not (b is None and c is None)
         lw = torch.empty_like(a) if need_lw else None
         lse = torch.empty(B, dtype=a.dtype, device=a.device) if want_lse else None
-        with _on_device(a.device):
-            args = (tag, _ptr(a), _ptr(b), _ptr(c), _ptr(lw), _ptr(lse), B, K, self._stream(a))
-            _lib.check(self._lib.aesmc_logweight_lse(*args), "aesmc_logweight_lse")
-            if self.timer is not None:
-                esz = a.element_size()
-                terms = 1 + (b is not None) + (c is not None) + (lw is not None)
-                self.timer.note("logweight_lse", (self._lib.aesmc_logweight_lse, args),
-                                B * K * esz * terms + B * esz, (a, b, c, lw, lse))
+        esz = a.element_size()
+        self._launch(a.device, self._lib.aesmc_logweight_lse,
+                     (tag, _ptr(a), _ptr(b), _ptr(c), _ptr(lw), _ptr(lse), B, K, self._stream(a)),
+                     lambda: B * K * esz * (1 + (b is not None) + (c is not None) + (lw is not None)) + B * esz,
+                     (a, b, c, lw, lse))
         if want_lw and not need_lw:
             lw = a
         return lw, lse
@@ -278,17 +312,11 @@ class HipKernels:
     def logweight_accumulate(self, a, b, c, acc, want_lw=True, want_lse=False):
         """K1 with the running sum over time of importance sampling: lw = a + b - c (b, c optional),
         total = acc + lw, lse[b] = logsumexp_k total.  Returns (lw or None, total, lse or None)."""
-        _require_hip(a, "log-prob term")
-        tag = _tag(a, "log-prob term")
-        if a.dim() != 2:
-            raise ValueError("aesmc_amd: log-prob terms must be [batch_size, num_particles], got {}"
-                             .format(tuple(a.shape)))
+        tag = self._rows_operand(a, "log-prob terms")
         for t in (b, c, acc):
             if t is not None:
                 _require_hip(t, "log-prob term")
-                if t.shape != a.shape or t.dtype != a.dtype or t.device != a.device:
-                    raise ValueError("aesmc_amd: log-prob terms disagree: {} {} {} vs {} {} {}".format(
-                        tuple(t.shape), t.dtype, t.device, tuple(a.shape), a.dtype, a.device))
+                self._expect(t, a.shape, a, "log-prob term")
         if acc is None:
             raise ValueError("aesmc_amd: logweight_accumulate needs the running sum")
         a, b, c, acc = [None if t is None else t.contiguous() for t in (a, b, c, acc)]
@@ -299,73 +327,48 @@ class HipKernels:
         lse = torch.empty(B, dtype=a.dtype, device=a.device) if want_lse else None
         if a.numel() == 0:
             return (lw if need_lw else (a if want_lw else None)), total, lse
-        with _on_device(a.device):
-            args = (tag, _ptr(a), _ptr(b), _ptr(c), _ptr(acc), _ptr(lw), _ptr(total), _ptr(lse), B, K,
-                    self._stream(a))
-            _lib.check(self._lib.aesmc_logweight_accumulate(*args), "aesmc_logweight_accumulate")
-            if self.timer is not None:
-                esz = a.element_size()
-                terms = 3 + (b is not None) + (c is not None) + (lw is not None)
-                self.timer.note("logweight_accumulate", (self._lib.aesmc_logweight_accumulate, args),
-                                B * K * esz * terms + (B * esz if want_lse else 0), (a, b, c, acc, lw, total, lse))
+        esz = a.element_size()
+        self._launch(a.device, self._lib.aesmc_logweight_accumulate,
+                     (tag, _ptr(a), _ptr(b), _ptr(c), _ptr(acc), _ptr(lw), _ptr(total), _ptr(lse), B, K, self._stream(a)),
+                     lambda: B * K * esz * (3 + (b is not None) + (c is not None) + (lw is not None)) +
+                     (B * esz if want_lse else 0), (a, b, c, acc, lw, total, lse))
         if want_lw and not need_lw:
             lw = a
         return lw, total, lse
 
     def logweight_lse_backward(self, lw, lse, grad_lw, grad_lse, want_neg=True):
-        _require_hip(lw, "lw")
-        tag = _tag(lw, "lw")
+        tag = self._rows_operand(lw, "lw")
         B, K = lw.shape
         lw = lw.contiguous()
         lse = lse.contiguous()
-        if lse.shape != (B,) or lse.dtype != lw.dtype or lse.device != lw.device:
-            raise ValueError("aesmc_amd: lse must be [{}] {} on {}".format(B, lw.dtype, lw.device))
+        self._expect(lse, (B,), lw, "lse")
         if grad_lw is not None:
-            if grad_lw.shape != lw.shape or grad_lw.dtype != lw.dtype or grad_lw.device != lw.device:
-                raise ValueError("aesmc_amd: grad_lw does not match lw")
+            self._expect(grad_lw, lw.shape, lw, "grad_lw")
             grad_lw = grad_lw.contiguous()
         if grad_lse is not None:
-            if grad_lse.shape != (B,) or grad_lse.dtype != lw.dtype or grad_lse.device != lw.device:
-                raise ValueError("aesmc_amd: grad_lse does not match lse")
+            self._expect(grad_lse, (B,), lw, "grad_lse")
             grad_lse = grad_lse.contiguous()
         g = torch.empty_like(lw)
         ng = torch.empty_like(lw) if want_neg else None
-        with _on_device(lw.device):
-            args = (tag, _ptr(lw), _ptr(lse), _ptr(grad_lw), _ptr(grad_lse), _ptr(g), _ptr(ng), B, K,
-                    self._stream(lw))
-            _lib.check(self._lib.aesmc_logweight_lse_backward(*args), "aesmc_logweight_lse_backward")
-            if self.timer is not None:
-                terms = 2 + (grad_lw is not None) + (ng is not None)
-                self.timer.note("logweight_lse_backward",
-                                (self._lib.aesmc_logweight_lse_backward, args),
-                                B * K * lw.element_size() * terms, (lw, lse, grad_lw, grad_lse, g, ng))
+        self._launch(lw.device, self._lib.aesmc_logweight_lse_backward,
+                     (tag, _ptr(lw), _ptr(lse), _ptr(grad_lw), _ptr(grad_lse), _ptr(g), _ptr(ng), B, K, self._stream(lw)),
+                     lambda: B * K * lw.element_size() * (2 + (grad_lw is not None) + (ng is not None)),
+                     (lw, lse, grad_lw, grad_lse, g, ng))
         return g, ng
 
     # ---- K2 ------------------------------------------------------------------------------------
     def ancestor_index(self, log_w, u):
         """log_w [B,K] float32/64, u [B] float64 (both on the HIP device) -> int64 [B,K]."""
-        _require_hip(log_w, "log_weight")
-        _require_hip(u, "uniforms")
-        tag = _tag(log_w, "log_weight")
-        if log_w.dim() != 2:
-            raise ValueError("aesmc_amd: log_weight must be [batch_size, num_particles], got {}"
-                             .format(tuple(log_w.shape)))
-        B, K = log_w.shape
-        if u.dtype != torch.float64 or u.numel() != B or u.device != log_w.device:
-            raise ValueError("aesmc_amd: uniforms must be {} float64 values on {}".format(B, log_w.device))
+        tag, B, K = self._resampling_operands(log_w, u)
         log_w = log_w.contiguous()
         u = u.contiguous()
         idx = torch.empty((B, K), dtype=torch.int64, device=log_w.device)
         ws_bytes = int(self._lib.aesmc_workspace_bytes(B, K))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=log_w.device) if ws_bytes else None
-        with _on_device(log_w.device):
-            flags = self.flags(log_w.device)
-            args = (tag, _ptr(log_w), _ptr(u), _ptr(idx), _ptr(flags), B, K, _ptr(ws), ws_bytes,
-                    self._stream(log_w))
-            _lib.check(self._lib.aesmc_ancestor_index(*args), "aesmc_ancestor_index")
-            if self.timer is not None:
-                self.timer.note("ancestor_index", (self._lib.aesmc_ancestor_index, args),
-                                B * K * (log_w.element_size() + 8) + 8 * B, (log_w, u, idx, ws))
+        self._launch(log_w.device, self._lib.aesmc_ancestor_index,
+                     (tag, _ptr(log_w), _ptr(u), _ptr(idx), _ptr(self.flags(log_w.device)), B, K, _ptr(ws), ws_bytes,
+                      self._stream(log_w)),
+                     lambda: B * K * (log_w.element_size() + 8) + 8 * B, (log_w, u, idx, ws))
         idx._aesmc_sorted = True  # systematic resampling is monotone in k: lets K3's backward skip atomics
         return idx
 
@@ -398,15 +401,7 @@ class HipKernels:
         payload tensor [B,K,...] is given (else None).  Returns None when the launch does not cover
         the operands (more particles than one workgroup holds, payload rows not 4-byte multiples):
         the caller then runs `ancestor_index` / `gather` / `logweight_lse` separately."""
-        _require_hip(log_w, "log_weight")
-        _require_hip(u, "uniforms")
-        tag = _tag(log_w, "log_weight")
-        if log_w.dim() != 2:
-            raise ValueError("aesmc_amd: log_weight must be [batch_size, num_particles], got {}"
-                             .format(tuple(log_w.shape)))
-        B, K = log_w.shape
-        if u.dtype != torch.float64 or u.numel() != B or u.device != log_w.device:
-            raise ValueError("aesmc_amd: uniforms must be {} float64 values on {}".format(B, log_w.device))
+        tag, B, K = self._resampling_operands(log_w, u)
         if K > self.lds_max_particles:
             return None
         log_w = log_w.contiguous()
@@ -434,30 +429,24 @@ class HipKernels:
         if idx.numel() == 0:
             return None
         child_end = None
-        with _on_device(log_w.device):
-            flags = self.flags(log_w.device)
-            if want_child_end and dst is None:
-                # the children ranges ride along (aesmc_resample_step_ranges): where each particle's children end, for
-                # the propagation's backward, which sums a particle's children itself (`idx._aesmc_child_end`)
-                child_end = torch.empty((B, K), dtype=torch.int32, device=log_w.device)
-                entry = self._lib.aesmc_resample_step_ranges
-                args = (tag, _ptr(log_w), _ptr(u), _ptr(idx), _ptr(lse), _ptr(child_end), _ptr(flags), B, K,
-                        self._stream(log_w))
-            else:
-                entry = self._lib.aesmc_resample_step
-                args = (tag, _ptr(log_w), _ptr(u), _ptr(idx), _ptr(lse), _ptr(payload if dst is not None else None),
-                        _ptr(dst), _ptr(flags), B, K, row_bytes, sb, sk, self._stream(log_w))
-            status = entry(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_resample_step")
-            if self.timer is not None:
-                nbytes = B * K * (log_w.element_size() + 8) + 8 * B
-                if dst is not None:  # K2's 12 B + K3's (8 + 2 row_bytes) per particle
-                    nbytes += B * K * (8 + 2 * row_bytes)
-                if child_end is not None:
-                    nbytes += 4 * B * K
-                self.timer.note("resample_step", (entry, args), nbytes, (log_w, u, idx, lse, payload, dst, child_end))
+        flags = self.flags(log_w.device)
+        if want_child_end and dst is None:
+            # the children ranges ride along (aesmc_resample_step_ranges): where each particle's children end, for
+            # the propagation's backward, which sums a particle's children itself (`idx._aesmc_child_end`)
+            child_end = torch.empty((B, K), dtype=torch.int32, device=log_w.device)
+            entry = self._lib.aesmc_resample_step_ranges
+            args = (tag, _ptr(log_w), _ptr(u), _ptr(idx), _ptr(lse), _ptr(child_end), _ptr(flags), B, K,
+                    self._stream(log_w))
+        else:
+            entry = self._lib.aesmc_resample_step
+            args = (tag, _ptr(log_w), _ptr(u), _ptr(idx), _ptr(lse), _ptr(payload if dst is not None else None),
+                    _ptr(dst), _ptr(flags), B, K, row_bytes, sb, sk, self._stream(log_w))
+        # K2's 12 B + K3's (8 + 2 row_bytes) per particle when the payload rides along
+        nbytes = lambda: B * K * (log_w.element_size() + 8) + 8 * B + \
+            (B * K * (8 + 2 * row_bytes) if dst is not None else 0) + (4 * B * K if child_end is not None else 0)
+        if not self._launch(log_w.device, entry, args, nbytes, (log_w, u, idx, lse, payload, dst, child_end),
+                            name="resample_step", decline=True):
+            return None
         idx._aesmc_sorted = True
         if child_end is not None:
             idx._aesmc_child_end = child_end
@@ -473,6 +462,16 @@ class HipKernels:
         if idx.device != value.device:
             raise RuntimeError("aesmc_amd: ancestral_index on {} but value on {}".format(
                 idx.device, value.device))
+
+    def _ancestors(self, value, ancestors, B, K, what):
+        """The indices a fused launch fetches `value`'s rows through (int64 [B,K] on value's device), dense; None stays
+        None."""
+        if ancestors is None:
+            return None
+        self._check_index(value, ancestors)
+        if ancestors.shape != (B, K):
+            raise ValueError("aesmc_amd: {} ancestors must be [{}, {}]".format(what, B, K))
+        return ancestors.contiguous()
 
     def gather(self, src, idx):
         """dst[b,k,...] = src[b, idx[b,k], ...]; src [B,K,...] any dtype, idx int64 [B,K]."""
@@ -490,14 +489,10 @@ class HipKernels:
         if dst.numel() == 0:
             return dst
         idx = idx.contiguous()
-        with _on_device(src.device):
-            flags = self.flags(src.device)
-            args = (_ptr(src), _ptr(idx), _ptr(dst), _ptr(flags), B, K, row_elems * esz,
-                    src.stride(0) * esz, src.stride(1) * esz, self._stream(src))
-            _lib.check(self._lib.aesmc_resample_gather(*args), "aesmc_resample_gather")
-            if self.timer is not None:
-                self.timer.note("resample_gather", (self._lib.aesmc_resample_gather, args),
-                                B * K * (8 + 2 * row_elems * esz), (src, idx, dst))
+        self._launch(src.device, self._lib.aesmc_resample_gather,
+                     (_ptr(src), _ptr(idx), _ptr(dst), _ptr(self.flags(src.device)), B, K, row_elems * esz,
+                      src.stride(0) * esz, src.stride(1) * esz, self._stream(src)),
+                     lambda: B * K * (8 + 2 * row_elems * esz), (src, idx, dst))
         return dst
 
     def gather_backward(self, grad_out, idx, sorted_index=False):
@@ -518,17 +513,10 @@ class HipKernels:
         grad_src = torch.zeros_like(grad_out) if sorted_index == "inherited" else torch.empty_like(grad_out)
         if grad_src.numel() == 0:
             return grad_src
-        with _on_device(grad_out.device):
-            flags = self.flags(grad_out.device)
-            args = (tag, _ptr(grad_out), _ptr(idx), _ptr(grad_src), _ptr(flags), B, K, row_elems,
-                    1 if sorted_index else 0, self._stream(grad_out))
-            _lib.check(self._lib.aesmc_resample_gather_backward(*args),
-                       "aesmc_resample_gather_backward")
-            if self.timer is not None:
-                self.timer.note("resample_gather_backward",
-                                (self._lib.aesmc_resample_gather_backward, args),
-                                B * K * (8 + 2 * row_elems * grad_out.element_size()),
-                                (grad_out, idx, grad_src))
+        self._launch(grad_out.device, self._lib.aesmc_resample_gather_backward,
+                     (tag, _ptr(grad_out), _ptr(idx), _ptr(grad_src), _ptr(self.flags(grad_out.device)), B, K, row_elems,
+                      1 if sorted_index else 0, self._stream(grad_out)),
+                     lambda: B * K * (8 + 2 * row_elems * grad_out.element_size()), (grad_out, idx, grad_src))
         return grad_src
 
 
@@ -579,10 +567,7 @@ class HipKernels:
             raise ValueError("aesmc_amd: value must be [batch_size, num_particles, ...]")
         for name, t in (("loc", loc), ("scale", scale)):
             _require_hip(t, name)
-            if t.shape != value.shape or t.dtype != value.dtype or t.device != value.device:
-                raise ValueError("aesmc_amd: {} must be a {} view of shape {} on {}, got {} {} on {}"
-                                 .format(name, value.dtype, tuple(value.shape), value.device, t.dtype,
-                                         tuple(t.shape), t.device))
+            self._expect(t, value.shape, value, name)
         (value, sv, D), (loc, sm, _), (scale, ss, _) = [self._view3(t) for t in (value, loc, scale)]
         return tag, value, loc, scale, sv, sm, ss, D
 
@@ -594,14 +579,10 @@ class HipKernels:
         out = torch.empty((B, K), dtype=value.dtype, device=value.device)
         if out.numel() == 0:
             return out
-        with _on_device(value.device):
-            args = (tag, _ptr(value), _ptr(loc), _ptr(scale), _ptr(out), B, K, D) + sv + sm + ss + \
-                (self._stream(value),)
-            _lib.check(self._lib.aesmc_normal_logprob_sum(*args), "aesmc_normal_logprob_sum")
-            if self.timer is not None:
-                nbytes = sum(self._unique_bytes(t) for t in (value, loc, scale)) + out.numel() * out.element_size()
-                self.timer.note("normal_logprob_sum", (self._lib.aesmc_normal_logprob_sum, args),
-                                nbytes, (value, loc, scale, out))
+        self._launch(value.device, self._lib.aesmc_normal_logprob_sum,
+                     (tag, _ptr(value), _ptr(loc), _ptr(scale), _ptr(out), B, K, D) + sv + sm + ss + (self._stream(value),),
+                     lambda: sum(self._unique_bytes(t) for t in (value, loc, scale)) + out.numel() * out.element_size(),
+                     (value, loc, scale, out))
         return out
 
     def normal_logprob_sum_backward(self, value, loc, scale, grad_out, need_value, need_loc, need_scale):
@@ -609,24 +590,18 @@ class HipKernels:
         shape = value.shape
         tag, value, loc, scale, sv, sm, ss, D = self._normal_operands(value, loc, scale)
         B, K = shape[:2]
-        if grad_out.shape != (B, K) or grad_out.dtype != value.dtype or grad_out.device != value.device:
-            raise ValueError("aesmc_amd: grad_out must be [{}, {}] {}".format(B, K, value.dtype))
+        self._expect(grad_out, (B, K), value, "grad_out")
         grad_out = grad_out.contiguous()
         outs = [torch.empty(shape, dtype=value.dtype, device=value.device) if need else None
                 for need in (need_value, need_loc, need_scale)]
         if value.numel() == 0 or not any(o is not None for o in outs):
             return tuple(None if o is None else o.zero_() for o in outs)
-        with _on_device(value.device):
-            args = (tag, _ptr(value), _ptr(loc), _ptr(scale), _ptr(grad_out), _ptr(outs[0]),
-                    _ptr(outs[1]), _ptr(outs[2]), B, K, D) + sv + sm + ss + (self._stream(value),)
-            _lib.check(self._lib.aesmc_normal_logprob_sum_backward(*args),
-                       "aesmc_normal_logprob_sum_backward")
-            if self.timer is not None:
-                nbytes = sum(self._unique_bytes(t) for t in (value, loc, scale, grad_out)) + \
-                    sum(o.numel() * o.element_size() for o in outs if o is not None)
-                self.timer.note("normal_logprob_sum_backward",
-                                (self._lib.aesmc_normal_logprob_sum_backward, args), nbytes,
-                                (value, loc, scale, grad_out) + tuple(outs))
+        self._launch(value.device, self._lib.aesmc_normal_logprob_sum_backward,
+                     (tag, _ptr(value), _ptr(loc), _ptr(scale), _ptr(grad_out), _ptr(outs[0]), _ptr(outs[1]),
+                      _ptr(outs[2]), B, K, D) + sv + sm + ss + (self._stream(value),),
+                     lambda: sum(self._unique_bytes(t) for t in (value, loc, scale, grad_out)) +
+                     sum(o.numel() * o.element_size() for o in outs if o is not None),
+                     (value, loc, scale, grad_out) + tuple(outs))
         return tuple(outs)
 
 
@@ -664,17 +639,12 @@ class HipKernels:
         views = (_lib.View3 * 8)(*[_lib.View3(_ptr(t), *st) for t, st in (
             (x, sx), (loc_p, sp), (scale_p, ssp), (y, sy), (loc_g, sg), (scale_g, ssg), (loc_q, sq),
             (scale_q, ssq))])
-        with _on_device(x.device):
-            args = (tag, views, _ptr(out), B, K, Dx, Dy, self._stream(x))
-            status = self._lib.aesmc_normal_logweight(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_normal_logweight")
-            if self.timer is not None:
-                nbytes = sum(self._unique_bytes(t) for t in (x, loc_p, y, loc_g, loc_q)) + \
-                    out.numel() * out.element_size()
-                self.timer.note("normal_logweight", (self._lib.aesmc_normal_logweight, args), nbytes,
-                                (x, loc_p, scale_p, y, loc_g, scale_g, loc_q, scale_q, out, views))
+        if not self._launch(x.device, self._lib.aesmc_normal_logweight,
+                            (tag, views, _ptr(out), B, K, Dx, Dy, self._stream(x)),
+                            lambda: sum(self._unique_bytes(t) for t in (x, loc_p, y, loc_g, loc_q)) +
+                            out.numel() * out.element_size(),
+                            (x, loc_p, scale_p, y, loc_g, scale_g, loc_q, scale_q, out, views), decline=True):
+            return None
         return out
 
     def normal_logweight_backward(self, x, loc_p, scale_p, y, loc_g, scale_g, loc_q, scale_q, grad_lw, need,
@@ -693,10 +663,9 @@ class HipKernels:
         fused_lse = grad_lse is not None
         if fused_lse:
             lw, lse, grad_lse = lw.contiguous(), lse.contiguous(), grad_lse.contiguous()
-            if lw.shape != (B, K) or lse.shape != (B,) or grad_lse.shape != (B,) or \
-                    any(t.dtype != x.dtype or t.device != x.device for t in (lw, lse, grad_lse)):
-                raise ValueError("aesmc_amd: lw must be [{0}, {1}], lse and grad_lse [{0}], all {2} on {3}".format(
-                    B, K, x.dtype, x.device))
+            self._expect(lw, (B, K), x, "lw")
+            self._expect(lse, (B,), x, "lse")
+            self._expect(grad_lse, (B,), x, "grad_lse")
         if grad_lw is not None:
             grad_lw = grad_lw.contiguous()
         elif not fused_lse:
@@ -710,25 +679,20 @@ class HipKernels:
         views = (_lib.View3 * 8)(*[_lib.View3(_ptr(t), *st) for t, st in (
             (x, sx), (loc_p, sp), (scale_p, ssp), (y, sy), (loc_g, sg), (scale_g, ssg), (loc_q, sq),
             (scale_q, ssq))])
-        with _on_device(x.device):
-            tail = (_ptr(gx), _ptr(gp), _ptr(gy), _ptr(gg), _ptr(gq), _ptr(gsp), _ptr(gsg), _ptr(gsq), B, K, Dx, Dy,
-                    self._stream(x))
-            if fused_lse:
-                entry, name = self._lib.aesmc_normal_logweight_lse_backward, "aesmc_normal_logweight_lse_backward"
-                args = (tag, views, _ptr(lw), _ptr(lse), _ptr(grad_lse), _ptr(grad_lw)) + tail
-            else:
-                entry, name = self._lib.aesmc_normal_logweight_backward, "aesmc_normal_logweight_backward"
-                args = (tag, views, _ptr(grad_lw)) + tail
-            status = entry(*args)
-            if status == 2:
-                return None
-            _lib.check(status, name)
-            if self.timer is not None:
-                live = [t for t in outs if t is not None]
-                reads = [t for t in (x, loc_p, scale_p, y, loc_g, scale_g, loc_q, scale_q, grad_lw, lw) if t is not None]
-                nbytes = sum(self._unique_bytes(t) for t in reads) + sum(t.numel() * t.element_size() for t in live)
-                self.timer.note(name[6:], (entry, args), nbytes,
-                                tuple(reads) + (lse, grad_lse, views) + tuple(live))
+        tail = (_ptr(gx), _ptr(gp), _ptr(gy), _ptr(gg), _ptr(gq), _ptr(gsp), _ptr(gsg), _ptr(gsq), B, K, Dx, Dy,
+                self._stream(x))
+        if fused_lse:
+            entry = self._lib.aesmc_normal_logweight_lse_backward
+            args = (tag, views, _ptr(lw), _ptr(lse), _ptr(grad_lse), _ptr(grad_lw)) + tail
+        else:
+            entry = self._lib.aesmc_normal_logweight_backward
+            args = (tag, views, _ptr(grad_lw)) + tail
+        reads = (x, loc_p, scale_p, y, loc_g, scale_g, loc_q, scale_q, grad_lw, lw)
+        if not self._launch(x.device, entry, args,
+                            lambda: sum(self._unique_bytes(t) for t in reads if t is not None) +
+                            sum(t.numel() * t.element_size() for t in outs if t is not None),
+                            reads + (lse, grad_lse, views) + tuple(outs), decline=True):
+            return None
         return outs
 
     def normal_rsample(self, eps, loc, scale):
@@ -741,21 +705,16 @@ class HipKernels:
         out = torch.empty(eps.shape, dtype=eps.dtype, device=eps.device)
         if out.numel() == 0:
             return out
-        with _on_device(eps.device):
-            for attempt in (0, 1):
-                views = [_lib.View3(_ptr(t), *st) for t, st in ((eps, se), (loc, sm), (scale, ss))]
-                args = (tag, ctypes.byref(views[0]), ctypes.byref(views[1]), ctypes.byref(views[2]), _ptr(out),
-                        B, K, D, self._stream(eps))
-                status = self._lib.aesmc_normal_rsample(*args)
-                if status != 2 or attempt == 1:
-                    break
-                eps = eps.contiguous()   # a noise layout the kernel does not know: materialise it
-                se = (eps.stride(0), eps.stride(1), 1)
-            _lib.check(status, "aesmc_normal_rsample")
-            if self.timer is not None:
-                nbytes = sum(self._unique_bytes(t) for t in (eps, loc, scale)) + out.numel() * out.element_size()
-                self.timer.note("normal_rsample", (self._lib.aesmc_normal_rsample, args), nbytes,
-                                (eps, loc, scale, out, views))
+        def launch(eps, se, decline):
+            views = [_lib.View3(_ptr(t), *st) for t, st in ((eps, se), (loc, sm), (scale, ss))]
+            return self._launch(eps.device, self._lib.aesmc_normal_rsample,
+                                (tag, ctypes.byref(views[0]), ctypes.byref(views[1]), ctypes.byref(views[2]), _ptr(out),
+                                 B, K, D, self._stream(eps)),
+                                lambda: sum(self._unique_bytes(t) for t in (eps, loc, scale)) + out.numel() * out.element_size(),
+                                (eps, loc, scale, out, views), decline=decline)
+        if not launch(eps, se, decline=True):
+            eps = eps.contiguous()   # a noise layout the kernel does not know: materialise it
+            launch(eps, (eps.stride(0), eps.stride(1), 1), decline=False)
         return out
 
     # Below this many elements the noise launch + K6 pair is as fast (both are launch-latency bound) and the drawn
@@ -777,18 +736,13 @@ class HipKernels:
         (loc, sm, D), (scale, ss, _) = [self._view3(t) for t in (loc, scale)]
         B, K = int(shape[0]), int(shape[1])
         out = torch.empty(tuple(shape), dtype=torch.float32, device=loc.device)
-        with _on_device(loc.device):
-            views = [_lib.View3(_ptr(t), *st) for t, st in ((loc, sm), (scale, ss))]
-            args = (_DTYPE_TAG[torch.float32], ctypes.byref(views[0]), ctypes.byref(views[1]), _ptr(out), B, K, D,
-                    noise.seed, noise.offset, noise.threads, 0, _ptr(noise.state), self._stream(loc))
-            status = self._lib.aesmc_normal_rsample_drawn(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_normal_rsample_drawn")
-            if self.timer is not None:
-                nbytes = self._unique_bytes(loc) + self._unique_bytes(scale) + 4 * numel
-                self.timer.note("normal_rsample_drawn", (self._lib.aesmc_normal_rsample_drawn, args), nbytes,
-                                (loc, scale, out, views))
+        views = [_lib.View3(_ptr(t), *st) for t, st in ((loc, sm), (scale, ss))]
+        if not self._launch(loc.device, self._lib.aesmc_normal_rsample_drawn,
+                            (_DTYPE_TAG[torch.float32], ctypes.byref(views[0]), ctypes.byref(views[1]), _ptr(out), B, K, D,
+                             noise.seed, noise.offset, noise.threads, 0, _ptr(noise.state), self._stream(loc)),
+                            lambda: self._unique_bytes(loc) + self._unique_bytes(scale) + 4 * numel,
+                            (loc, scale, out, views), decline=True):
+            return None
         return out
 
     # ---- K8 / K9 / K10: linear-Gaussian particle propagation -----------------------------------
@@ -857,6 +811,18 @@ class HipKernels:
             self._map_cache[(id(weight), slot)] = (weight, amap, (weight.shape, weight.stride()))
         return amap, (weight, offset)
 
+    @staticmethod
+    def _map_args(maps, scales):
+        """The three `_affine_map` results by reference, then (`scales` given) the three one-value scales: the argument
+        block every three-map entry point takes."""
+        refs = (ctypes.byref(maps[0][0]), ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]))
+        return refs if scales is None else refs + (_ptr(scales[0]), _ptr(scales[1]), _ptr(scales[2]))
+
+    @staticmethod
+    def _unit_rows(y_rows):
+        """The observation [B, dy] with unit element stride (its row stride is passed to the launch)."""
+        return y_rows if y_rows.stride(1) == 1 else y_rows.contiguous()
+
     def particle_affine(self, x1, w1, offset=None, x2=None, w2=None, base=None, through_tanh=False):
         """K8: base + (offset + x1 @ w1.T + x2 @ w2.T) -> dense [B,K,dout]; x2 / w2, offset, base optional.
         Every element is one fma chain (w1's terms, then w2's) started from the offset.  `through_tanh`: the launch stores
@@ -871,23 +837,17 @@ class HipKernels:
         x1 = self._dense16(x1)
         x2 = None if x2 is None else self._dense16(x2)
         if base is not None:
-            if base.shape != (B, K, dout) or base.dtype != x1.dtype or base.device != x1.device:
-                raise ValueError("aesmc_amd: particle_affine base must be [{}, {}, {}]".format(B, K, dout))
+            self._expect(base, (B, K, dout), x1, "particle_affine base")
             base = self._dense16(base)
         out = torch.empty((B, K, dout), dtype=x1.dtype, device=x1.device)
         m1, keep1 = self._affine_map(w1, offset)
         m2, keep2 = self._affine_map(w2, None) if x2 is not None else (None, ())
-        with _on_device(x1.device):
-            args = (tag, _ptr(x1), ctypes.byref(m1), _ptr(x2), ctypes.byref(m2) if m2 is not None else None,
-                    _ptr(base), _ptr(out), B, K, self._stream(x1))
-            entry = self._lib.aesmc_particle_affine_tanh if through_tanh else self._lib.aesmc_particle_affine
-            _lib.check(entry(*args), "aesmc_particle_affine")
-            if self.timer is not None:
-                esz = x1.element_size()
-                nbytes = esz * B * K * (x1.size(2) + (x2.size(2) if x2 is not None else 0) +
-                                        dout * (2 if base is not None else 1))
-                self.timer.note("particle_affine", (entry, args), nbytes,
-                                (x1, x2, base, out, m1, m2, keep1, keep2))
+        self._launch(x1.device, self._lib.aesmc_particle_affine_tanh if through_tanh else self._lib.aesmc_particle_affine,
+                     (tag, _ptr(x1), ctypes.byref(m1), _ptr(x2), ctypes.byref(m2) if m2 is not None else None,
+                      _ptr(base), _ptr(out), B, K, self._stream(x1)),
+                     lambda: x1.element_size() * B * K * (x1.size(2) + (x2.size(2) if x2 is not None else 0) +
+                                                          dout * (2 if base is not None else 1)),
+                     (x1, x2, base, out, m1, m2, keep1, keep2), name="particle_affine")
         return out
 
     def affine_rsample(self, source, weight, offset, eps, scale, out=None):
@@ -898,8 +858,7 @@ class HipKernels:
         tag = _DTYPE_TAG[source.dtype]
         B, K = source.shape[:2]
         dout = weight.size(0)
-        if eps.shape != (B, K, dout) or eps.dtype != source.dtype or eps.device != source.device:
-            raise ValueError("aesmc_amd: affine_rsample noise must be [{}, {}, {}] {}".format(B, K, dout, source.dtype))
+        self._expect(eps, (B, K, dout), source, "affine_rsample noise")
         if scale.numel() != 1 or scale.dtype != source.dtype or scale.device != source.device:
             raise ValueError("aesmc_amd: affine_rsample takes one scale value on the device")
         source, eps = self._dense16(source), self._dense16(eps)
@@ -908,14 +867,10 @@ class HipKernels:
         else:
             self._check_out(out, (B, K, dout), source, "affine_rsample")
         amap, keep = self._affine_map(weight, offset)
-        with _on_device(source.device):
-            args = (tag, _ptr(source), ctypes.byref(amap), _ptr(eps), _ptr(scale), _ptr(out), B, K,
-                    self._stream(source))
-            _lib.check(self._lib.aesmc_affine_normal_rsample(*args), "aesmc_affine_normal_rsample")
-            if self.timer is not None:
-                nbytes = source.element_size() * B * K * (source.size(2) + 2 * dout)
-                self.timer.note("affine_normal_rsample", (self._lib.aesmc_affine_normal_rsample, args), nbytes,
-                                (source, eps, scale, out, amap, keep))
+        self._launch(source.device, self._lib.aesmc_affine_normal_rsample,
+                     (tag, _ptr(source), ctypes.byref(amap), _ptr(eps), _ptr(scale), _ptr(out), B, K, self._stream(source)),
+                     lambda: source.element_size() * B * K * (source.size(2) + 2 * dout),
+                     (source, eps, scale, out, amap, keep))
         return out
 
     @staticmethod
@@ -936,44 +891,29 @@ class HipKernels:
         # `checked`: the caller has just run affine_logweight_covers on these operands (x_t in eps's place)
         if not checked and not self.affine_logweight_covers(x_prev, eps, y_rows, transition, emission, proposal, scales):
             raise ValueError("aesmc_amd: affine_propagate operands outside what kernel K15 covers")
-        if eps.shape != x_prev.shape or eps.dtype != x_prev.dtype or eps.device != x_prev.device:
-            raise ValueError("aesmc_amd: affine_propagate noise must match x_prev")
+        self._expect(eps, x_prev.shape, x_prev, "affine_propagate noise")
         tag = _DTYPE_TAG[eps.dtype]
         B, K, dx = eps.shape
         self._check_out(out_x, (B, K, dx), eps, "affine_propagate")
         x_prev, eps = self._dense16(x_prev), self._dense16(eps)
         if out_x.data_ptr() == x_prev.data_ptr():
             raise ValueError("aesmc_amd: affine_propagate cannot write the draw over x_prev")
-        if ancestors is not None:
-            self._check_index(x_prev, ancestors)
-            if ancestors.shape != (B, K):
-                raise ValueError("aesmc_amd: affine_propagate ancestors must be [{}, {}]".format(B, K))
-            ancestors = ancestors.contiguous()
-        if y_rows.stride(1) != 1:
-            y_rows = y_rows.contiguous()
+        ancestors = self._ancestors(x_prev, ancestors, B, K, "affine_propagate")
+        y_rows = self._unit_rows(y_rows)
         out = torch.empty((B, K), dtype=eps.dtype, device=eps.device)
         maps = [self._affine_map(*term, slot=slot) for slot, term in enumerate((transition, emission, proposal))]
-        with _on_device(eps.device):
-            tail = (_ptr(eps), _ptr(y_rows), y_rows.stride(0), ctypes.byref(maps[0][0]),
-                    ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]), _ptr(scales[0]), _ptr(scales[1]),
-                    _ptr(scales[2]), _ptr(out_x), _ptr(out))
-            if ancestors is not None:
-                entry, name = self._lib.aesmc_affine_normal_propagate_resampled, "affine_normal_propagate_resampled"
-                args = (tag, _ptr(x_prev), _ptr(ancestors)) + tail + (_ptr(self.flags(eps.device)), B, K,
-                                                                      self._stream(eps))
-                status = entry(*args)
-                if status == 2:
-                    return None
-            else:
-                entry, name = self._lib.aesmc_affine_normal_propagate, "affine_normal_propagate"
-                args = (tag, _ptr(x_prev)) + tail + (B, K, self._stream(eps))
-                status = entry(*args)
-            _lib.check(status, "aesmc_" + name)
-            if self.timer is not None:
-                nbytes = eps.element_size() * (B * K * (3 * dx + 1) + y_rows.numel())
-                if ancestors is not None:
-                    nbytes += 8 * B * K
-                self.timer.note(name, (entry, args), nbytes, (x_prev, ancestors, eps, y_rows, out, out_x, maps, scales))
+        tail = (_ptr(eps), _ptr(y_rows), y_rows.stride(0)) + self._map_args(maps, scales) + (_ptr(out_x), _ptr(out))
+        if ancestors is not None:
+            entry = self._lib.aesmc_affine_normal_propagate_resampled
+            args = (tag, _ptr(x_prev), _ptr(ancestors)) + tail + (_ptr(self.flags(eps.device)), B, K, self._stream(eps))
+        else:
+            entry = self._lib.aesmc_affine_normal_propagate
+            args = (tag, _ptr(x_prev)) + tail + (B, K, self._stream(eps))
+        if not self._launch(eps.device, entry, args,
+                            lambda: eps.element_size() * (B * K * (3 * dx + 1) + y_rows.numel()) +
+                            (8 * B * K if ancestors is not None else 0),
+                            (x_prev, ancestors, eps, y_rows, out, out_x, maps, scales), decline=ancestors is not None):
+            return None
         return out
 
     # Particles below which the noise is materialised (aesmc_philox_normal_fill, the same values) and the step takes the
@@ -993,12 +933,10 @@ class HipKernels:
                 out.numel(), stream_desc.numel))
         if out.numel() == 0:
             return out
-        with _on_device(out.device):
-            args = (_ptr(out), out.numel(), stream_desc.seed, stream_desc.offset, stream_desc.threads, 0,
-                    _ptr(stream_desc.state), self._stream(out))
-            _lib.check(self._lib.aesmc_philox_normal_fill(*args), "aesmc_philox_normal_fill")
-            if self.timer is not None:
-                self.timer.note("philox_normal_fill", (self._lib.aesmc_philox_normal_fill, args), 4 * out.numel(), (out,))
+        self._launch(out.device, self._lib.aesmc_philox_normal_fill,
+                     (_ptr(out), out.numel(), stream_desc.seed, stream_desc.offset, stream_desc.threads, 0,
+                      _ptr(stream_desc.state), self._stream(out)),
+                     lambda: 4 * out.numel(), (out,))
         return out
 
     # ---- K13: two-layer tanh net over the particles ---------------------------------------------
@@ -1034,16 +972,11 @@ class HipKernels:
         out = torch.empty((B, K, weight2.size(0)), dtype=x.dtype, device=x.device)
         m1, keep1 = self._affine_map(weight1, offset1)
         m2, keep2 = self._affine_map(weight2, bias2)
-        with _on_device(x.device):
-            args = (tag, _ptr(x), ctypes.byref(m1), ctypes.byref(m2), _ptr(out), B, K, self._stream(x))
-            status = self._lib.aesmc_particle_mlp(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_particle_mlp")
-            if self.timer is not None:
-                nbytes = x.element_size() * B * K * (x.size(2) + out.size(2))
-                self.timer.note("particle_mlp", (self._lib.aesmc_particle_mlp, args), nbytes,
-                                (x, out, m1, m2, keep1, keep2))
+        if not self._launch(x.device, self._lib.aesmc_particle_mlp,
+                            (tag, _ptr(x), ctypes.byref(m1), ctypes.byref(m2), _ptr(out), B, K, self._stream(x)),
+                            lambda: x.element_size() * B * K * (x.size(2) + out.size(2)),
+                            (x, out, m1, m2, keep1, keep2), decline=True):
+            return None
         return out
 
     def particle_mlp_backward(self, grad_out, x, weight1, offset1, weight2, need_x=True):
@@ -1067,17 +1000,12 @@ class HipKernels:
         rows = torch.empty((B, K // 64, 16 * chunks), dtype=x.dtype, device=x.device)
         m1, keep1 = self._affine_map(weight1, offset1)
         m2, keep2 = self._affine_map(weight2, None)
-        with _on_device(x.device):
-            args = (tag, _ptr(x), _ptr(grad_out), ctypes.byref(m1), ctypes.byref(m2), _ptr(grad_x), _ptr(rec_w1),
-                    _ptr(rec_w2), _ptr(rows), B, K, self._stream(x))
-            status = self._lib.aesmc_particle_mlp_backward(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_particle_mlp_backward")
-            if self.timer is not None:
-                nbytes = x.element_size() * B * K * (2 * din + dout)
-                self.timer.note("particle_mlp_backward", (self._lib.aesmc_particle_mlp_backward, args), nbytes,
-                                (x, grad_out, grad_x, rec_w1, rec_w2, rows, m1, m2, keep1, keep2))
+        if not self._launch(x.device, self._lib.aesmc_particle_mlp_backward,
+                            (tag, _ptr(x), _ptr(grad_out), ctypes.byref(m1), ctypes.byref(m2), _ptr(grad_x), _ptr(rec_w1),
+                             _ptr(rec_w2), _ptr(rows), B, K, self._stream(x)),
+                            lambda: x.element_size() * B * K * (2 * din + dout),
+                            (x, grad_out, grad_x, rec_w1, rec_w2, rows, m1, m2, keep1, keep2), decline=True):
+            return None
         # the wavefronts' partials, added in record order; grad_W1's chunk c holds rows 16 c .. 16 c + 15 (hidden units) x
         # inputs, grad_W2's chunk c holds outputs x hidden units 16 c .. 16 c + 15
         grad_w1 = rec_w1.sum(0).reshape(16 * chunks, 16)[:H, :din]
@@ -1149,8 +1077,8 @@ class HipKernels:
                 raise ValueError("aesmc_amd: affine_propagate_wide: the reservation does not match x_src")
             if dx != wide or dy != wide or K % 32 or eps.threads % wide or K % (4 * (eps.threads // wide)):
                 return None
-        elif eps.shape != x_src.shape or eps.dtype != x_src.dtype or eps.device != x_src.device:
-            raise ValueError("aesmc_amd: affine_propagate_wide noise must match x_src")
+        else:
+            self._expect(eps, x_src.shape, x_src, "affine_propagate_wide noise")
         for (weight, offset), scale, shape in zip((transition, emission, proposal), scales, ((dx, dx), (dy, dx), (dx, dx))):
             # (what affine_wide_covers tests, for callers that did not ask it)
             if not (torch.is_tensor(weight) and tuple(weight.shape) == shape and weight.is_contiguous() and
@@ -1169,31 +1097,21 @@ class HipKernels:
             eps = self._dense16(eps)
         if out_x.data_ptr() == x_src.data_ptr() or (not drawn and out_x.data_ptr() == eps.data_ptr()):
             raise ValueError("aesmc_amd: affine_propagate_wide cannot write the draw over its inputs")
-        if ancestors is not None:
-            self._check_index(x_src, ancestors)
-            if ancestors.shape != (B, K):
-                raise ValueError("aesmc_amd: affine_propagate_wide ancestors must be [{}, {}]".format(B, K))
-            ancestors = ancestors.contiguous()
+        ancestors = self._ancestors(x_src, ancestors, B, K, "affine_propagate_wide")
         if y_rows.stride(1) != 1 or y_rows.stride(0) % 4 or y_rows.data_ptr() % 16:
             y_rows = y_rows.contiguous()
         out = torch.empty((B, K), dtype=torch.float32, device=x_src.device)
         ws_bytes = int(self._lib.aesmc_affine_wide_workspace_bytes_for(B, K, dx, dy))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x_src.device)
         maps = [self._affine_map(*term, slot=slot) for slot, term in enumerate((transition, emission, proposal))]
-        with _on_device(x_src.device):
-            noise = (eps.seed, eps.offset, eps.threads, _ptr(eps.state)) if drawn else (0, 0, 256, 0)
-            args = (_ptr(x_src), _ptr(ancestors), 0 if drawn else _ptr(eps), _ptr(y_rows), y_rows.stride(0),
-                    ctypes.byref(maps[0][0]), ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]), _ptr(scales[0]),
-                    _ptr(scales[1]), _ptr(scales[2]), _ptr(out_x), _ptr(out), _ptr(ws), ws_bytes,
-                    _ptr(self.flags(x_src.device)), B, K) + noise + (self._stream(x_src),)
-            status = self._lib.aesmc_affine_normal_propagate_wide(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_affine_normal_propagate_wide")
-            if self.timer is not None:
-                nbytes = 4 * (B * K * (3 * dx + 1) + y_rows.numel()) + (8 * B * K if ancestors is not None else 0)
-                self.timer.note("affine_normal_propagate_wide", (self._lib.aesmc_affine_normal_propagate_wide, args),
-                                nbytes, (x_src, ancestors, eps, y_rows, out, out_x, ws, maps, scales))
+        noise = (eps.seed, eps.offset, eps.threads, _ptr(eps.state)) if drawn else (0, 0, 256, 0)
+        args = (_ptr(x_src), _ptr(ancestors), 0 if drawn else _ptr(eps), _ptr(y_rows), y_rows.stride(0)) + \
+            self._map_args(maps, scales) + (_ptr(out_x), _ptr(out), _ptr(ws), ws_bytes, _ptr(self.flags(x_src.device)),
+                                            B, K) + noise + (self._stream(x_src),)
+        if not self._launch(x_src.device, self._lib.aesmc_affine_normal_propagate_wide, args,
+                            lambda: 4 * (B * K * (3 * dx + 1) + y_rows.numel()) + (8 * B * K if ancestors is not None else 0),
+                            (x_src, ancestors, eps, y_rows, out, out_x, ws, maps, scales), decline=True):
+            return None
         return out
 
     def affine_initial_step(self, eps, loc_q, scale_q, loc_p, scale_p, y, weight, offset, scale_g, out_x):
@@ -1222,17 +1140,12 @@ class HipKernels:
             views.append(_lib.View3(_ptr(view), view.stride(0), 0, view.stride(2)))
         out = torch.empty((B, K), dtype=torch.float32, device=eps.device)
         amap, held = self._affine_map(weight, offset)
-        with _on_device(eps.device):
-            args = (_ptr(eps),) + tuple(ctypes.byref(v) for v in views[:5]) + (ctypes.byref(amap), ctypes.byref(views[5]),
-                                                                                _ptr(out_x), _ptr(out), B, K, self._stream(eps))
-            status = self._lib.aesmc_affine_normal_initial_step(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_affine_normal_initial_step")
-            if self.timer is not None:
-                nbytes = 4 * (2 * B * K * dx + B * K)
-                self.timer.note("affine_normal_initial_step", (self._lib.aesmc_affine_normal_initial_step, args), nbytes,
-                                (eps, loc_q, scale_q, loc_p, scale_p, y, scale_g, out_x, out, views, amap, held))
+        args = (_ptr(eps),) + tuple(ctypes.byref(v) for v in views[:5]) + (ctypes.byref(amap), ctypes.byref(views[5]),
+                                                                            _ptr(out_x), _ptr(out), B, K, self._stream(eps))
+        if not self._launch(eps.device, self._lib.aesmc_affine_normal_initial_step, args,
+                            lambda: 4 * (2 * B * K * dx + B * K),
+                            (eps, loc_q, scale_q, loc_p, scale_p, y, scale_g, out_x, out, views, amap, held), decline=True):
+            return None
         return out
 
     def begin_evaluation(self):
@@ -1247,14 +1160,8 @@ class HipKernels:
         """One launch: the interleaved pairs, with the three densities' constants behind them when `scales` is given
         (aesmc_affine_weight_pairs_scaled) — else their tag cleared (the propagating launch forms them itself)."""
         pairs = torch.empty(int(self._lib.aesmc_affine_weight_pairs_floats()), dtype=torch.float32, device=device)
-        if scales is not None:
-            _lib.check(self._lib.aesmc_affine_weight_pairs_scaled(
-                ctypes.byref(maps[0][0]), ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]), _ptr(scales[0]),
-                _ptr(scales[1]), _ptr(scales[2]), _ptr(pairs), self._stream(pairs)), "aesmc_affine_weight_pairs_scaled")
-        else:
-            _lib.check(self._lib.aesmc_affine_weight_pairs(ctypes.byref(maps[0][0]), ctypes.byref(maps[1][0]),
-                                                           ctypes.byref(maps[2][0]), _ptr(pairs), self._stream(pairs)),
-                       "aesmc_affine_weight_pairs")
+        entry = self._lib.aesmc_affine_weight_pairs if scales is None else self._lib.aesmc_affine_weight_pairs_scaled
+        self._launch(pairs.device, entry, self._map_args(maps, scales) + (_ptr(pairs), self._stream(pairs)))   # (not timed)
         return pairs
 
     # how often one evaluation may rebuild the pairs because the SCALES it was handed are other tensors than last time
@@ -1321,33 +1228,22 @@ class HipKernels:
         x_src = self._dense16(x_src)
         if out_x.data_ptr() == x_src.data_ptr():
             raise ValueError("aesmc_amd: affine_propagate_drawn cannot write the draw over x_src")
-        if ancestors is not None:
-            self._check_index(x_src, ancestors)
-            if ancestors.shape != (B, K):
-                raise ValueError("aesmc_amd: affine_propagate_drawn ancestors must be [{}, {}]".format(B, K))
-            ancestors = ancestors.contiguous()
-        if y_rows.stride(1) != 1:
-            y_rows = y_rows.contiguous()
+        ancestors = self._ancestors(x_src, ancestors, B, K, "affine_propagate_drawn")
+        y_rows = self._unit_rows(y_rows)
         out = torch.empty((B, K), dtype=x_src.dtype, device=x_src.device)
         maps = [self._affine_map(*term, slot=slot) for slot, term in enumerate((transition, emission, proposal))]
-        with _on_device(x_src.device):
-            pairs = None
-            if self.WEIGHT_PAIRS and 2 <= dx <= 16:
-                pairs = self._weight_pairs(maps, (transition[0], emission[0], proposal[0]), x_src.device,
-                                           scales if self.SCALED_PAIRS else None)
-            args = (_ptr(x_src), _ptr(ancestors), _ptr(y_rows), y_rows.stride(0), ctypes.byref(maps[0][0]),
-                    ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]), _ptr(scales[0]), _ptr(scales[1]),
-                    _ptr(scales[2]), _ptr(out_x), _ptr(out), _ptr(self.flags(x_src.device)), B, K, noise.seed,
-                    noise.offset, noise.threads, _ptr(noise.state), _ptr(pairs), self._stream(x_src))
-            status = self._lib.aesmc_affine_normal_propagate_drawn_paired(*args)
-            if status == 2:
-                return None
-            _lib.check(status, "aesmc_affine_normal_propagate_drawn")
-            if self.timer is not None:
-                nbytes = 4 * (B * K * (2 * dx + 1) + y_rows.numel()) + (8 * B * K if ancestors is not None else 0)
-                self.timer.note("affine_normal_propagate_drawn",
-                                (self._lib.aesmc_affine_normal_propagate_drawn_paired, args), nbytes,
-                                (x_src, ancestors, None, y_rows, out, out_x, maps, scales, pairs))
+        pairs = None
+        if self.WEIGHT_PAIRS and 2 <= dx <= 16:
+            pairs = self._weight_pairs(maps, (transition[0], emission[0], proposal[0]), x_src.device,
+                                       scales if self.SCALED_PAIRS else None)
+        args = (_ptr(x_src), _ptr(ancestors), _ptr(y_rows), y_rows.stride(0)) + self._map_args(maps, scales) + \
+            (_ptr(out_x), _ptr(out), _ptr(self.flags(x_src.device)), B, K, noise.seed, noise.offset, noise.threads,
+             _ptr(noise.state), _ptr(pairs), self._stream(x_src))
+        if not self._launch(x_src.device, self._lib.aesmc_affine_normal_propagate_drawn_paired, args,
+                            lambda: 4 * (B * K * (2 * dx + 1) + y_rows.numel()) + (8 * B * K if ancestors is not None else 0),
+                            (x_src, ancestors, None, y_rows, out, out_x, maps, scales, pairs),
+                            name="affine_normal_propagate_drawn", decline=True):
+            return None
         return out
 
     def affine_logweight_covers(self, x_prev, x, y_rows, transition, emission, proposal, scales):
@@ -1411,19 +1307,14 @@ class HipKernels:
         tag = _DTYPE_TAG[x.dtype]
         B, K, dx = x.shape
         x_prev, x = self._dense16(x_prev), self._dense16(x)
-        if y_rows.stride(1) != 1:
-            y_rows = y_rows.contiguous()
+        y_rows = self._unit_rows(y_rows)
         out = torch.empty((B, K), dtype=x.dtype, device=x.device)
         maps = [self._affine_map(*term) for term in (transition, emission, proposal)]
-        with _on_device(x.device):
-            args = (tag, _ptr(x_prev), _ptr(x), _ptr(y_rows), y_rows.stride(0), ctypes.byref(maps[0][0]),
-                    ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]), _ptr(scales[0]), _ptr(scales[1]),
-                    _ptr(scales[2]), _ptr(out), B, K, self._stream(x))
-            _lib.check(self._lib.aesmc_affine_normal_logweight(*args), "aesmc_affine_normal_logweight")
-            if self.timer is not None:
-                nbytes = x.element_size() * (B * K * (2 * dx + 1) + y_rows.numel())
-                self.timer.note("affine_normal_logweight", (self._lib.aesmc_affine_normal_logweight, args), nbytes,
-                                (x_prev, x, y_rows, out, maps, scales))
+        self._launch(x.device, self._lib.aesmc_affine_normal_logweight,
+                     (tag, _ptr(x_prev), _ptr(x), _ptr(y_rows), y_rows.stride(0)) + self._map_args(maps, scales) +
+                     (_ptr(out), B, K, self._stream(x)),
+                     lambda: x.element_size() * (B * K * (2 * dx + 1) + y_rows.numel()),
+                     (x_prev, x, y_rows, out, maps, scales))
         return out
 
     def particle_affine_backward(self, grad, x, weight, need_x=True, need_weight=True, need_offset=False):
@@ -1448,19 +1339,14 @@ class HipKernels:
         ws_bytes = int(self._lib.aesmc_affine_backward_workspace_bytes(tag, B, K)) if reduces else 0
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
         amap, keep = self._affine_map(weight, None)
-        with _on_device(x.device):
-            args = (tag, _ptr(grad), _ptr(x), ctypes.byref(amap), _ptr(gx), _ptr(gw), _ptr(goff), _ptr(ws), ws_bytes,
-                    B, K, self._stream(x))
-            status = self._lib.aesmc_particle_affine_backward(*args)
-            if status == 2 and goff is not None:     # the row sums do not fit this shape: the caller's reduction instead
-                goff = None
-                args = args[:6] + (0,) + args[7:]
-                status = self._lib.aesmc_particle_affine_backward(*args)
-            _lib.check(status, "aesmc_particle_affine_backward")
-            if self.timer is not None:
-                nbytes = x.element_size() * B * K * (dout + (din if need_weight else 0) + (din if need_x else 0))
-                self.timer.note("particle_affine_backward", (self._lib.aesmc_particle_affine_backward, args), nbytes,
-                                (grad, x, gx, gw, goff, ws, amap, keep))
+        entry = self._lib.aesmc_particle_affine_backward
+        args = (tag, _ptr(grad), _ptr(x), ctypes.byref(amap), _ptr(gx), _ptr(gw), _ptr(goff), _ptr(ws), ws_bytes,
+                B, K, self._stream(x))
+        nbytes = lambda: x.element_size() * B * K * (dout + (din if need_weight else 0) + (din if need_x else 0))
+        if not self._launch(x.device, entry, args, nbytes, (grad, x, gx, gw, goff, ws, amap, keep),
+                            decline=goff is not None):
+            goff = None     # the row sums do not fit this shape: the caller's reduction instead
+            self._launch(x.device, entry, args[:6] + (0,) + args[7:], nbytes, (grad, x, gx, gw, goff, ws, amap, keep))
         if need_offset and goff is None:
             goff = grad.sum(dim=1)
         return gx, gw, goff
@@ -1471,6 +1357,44 @@ class HipKernels:
         placeholder = torch.empty((g.size(2), x.size(2)), dtype=x.dtype, device=x.device)
         return self.particle_affine_backward(g, x, placeholder, need_x=False, need_weight=True)[1]
 
+    @staticmethod
+    def _affine_grad_buffers(need, offsets, dx, dy, dtype, device, B=None, sums=True):
+        """The optional outputs of K12 / K14 / the collect in `aesmc_affine_logweight_grads` order after the dense ones:
+        (grad_A, grad_C, grad_Q, the three scales' [3], then the three locations' gradients summed over each batch row's
+        particles [B,dx] / [B,dy] / [B,dx]), None where `need` does not ask for one (`B` None: no row sums; `sums` false:
+        no weight or scale sums — a deferring K14 leaves those as records)."""
+        off_p, off_g, off_q = offsets
+        make = lambda shape, wanted: torch.empty(shape, dtype=dtype, device=device) if wanted else None
+        rows = B is not None
+        rows_p = make((B, dx), rows and need[4] and off_p is not None)
+        rows_g = make((B, dy), rows and ((need[6] and off_g is not None) or need[2]))
+        rows_q = make((B, dx), rows and need[8] and off_q is not None)
+        gA, gC, gQ = make((dx, dx), sums and need[3]), make((dy, dx), sums and need[5]), make((dx, dx), sums and need[7])
+        gscales = make((3,), sums and (need[9] or need[10] or need[11]))
+        return gA, gC, gQ, gscales, rows_p, rows_g, rows_q
+
+    @staticmethod
+    def _affine_grad_slots(g_prev, g_x, buffers, need, offsets, scales):
+        """The 12-slot gradient list (x_prev, x, y_rows, A, off_p, C, off_g, Q, off_q, s_p, s_g, s_q) from the dense
+        gradients and `_affine_grad_buffers`: y's is minus the emission's row sums, an offset's is its location's row sums
+        (all rows added for a shared [d] offset)."""
+        gA, gC, gQ, gscales, rows_p, rows_g, rows_q = buffers
+        off_p, off_g, off_q = offsets
+        fold = lambda rows, off: rows if off.dim() == 2 else rows.sum(dim=0)     # a shared [d] offset: all rows
+        grads = [g_prev, g_x, None, gA, None, gC, None, gQ, None, None, None, None]
+        if need[2] and rows_g is not None:
+            grads[2] = -rows_g
+        if rows_p is not None:
+            grads[4] = fold(rows_p, off_p)
+        if need[6] and off_g is not None and rows_g is not None:
+            grads[6] = fold(rows_g, off_g)
+        if rows_q is not None:
+            grads[8] = fold(rows_q, off_q)
+        for slot, s in ((9, scales[0]), (10, scales[1]), (11, scales[2])):
+            if need[slot] and gscales is not None:
+                grads[slot] = gscales[slot - 9].reshape(s.shape)
+        return grads
+
     def affine_logweight_backward(self, x_prev, x, y_rows, transition, emission, proposal, scales, need,
                                   grad_lw=None, lw=None, lse=None, grad_lse=None):
         """K12: gradients of `affine_logweight` with respect to its twelve operands, in the order
@@ -1480,70 +1404,44 @@ class HipKernels:
         and x; the weight gradients are summed on the matrix cores in a fixed order."""
         if not self.affine_logweight_covers(x_prev, x, y_rows, transition, emission, proposal, scales):
             raise ValueError("aesmc_amd: affine_logweight_backward operands outside what kernel K12 covers")
-        (A, off_p), (C, off_g), (Q, off_q) = transition, emission, proposal
+        offsets = (transition[1], emission[1], proposal[1])
         tag = _DTYPE_TAG[x.dtype]
         B, K, dx = x.shape
         dy = y_rows.size(1)
         fused_lse = grad_lse is not None
-        check = lambda t, shape, what: None if (t.shape == shape and t.dtype == x.dtype and t.device == x.device) \
-            else (_ for _ in ()).throw(ValueError("aesmc_amd: {} must be {} {} on {}".format(what, shape, x.dtype, x.device)))
         if fused_lse:
             lw, lse, grad_lse = lw.contiguous(), lse.contiguous(), grad_lse.contiguous()
-            check(lw, (B, K), "lw"), check(lse, (B,), "lse"), check(grad_lse, (B,), "grad_lse")
+            self._expect(lw, (B, K), x, "lw")
+            self._expect(lse, (B,), x, "lse")
+            self._expect(grad_lse, (B,), x, "grad_lse")
         if grad_lw is not None:
             grad_lw = grad_lw.contiguous()
-            check(grad_lw, (B, K), "grad_lw")
+            self._expect(grad_lw, (B, K), x, "grad_lw")
         elif not fused_lse:
             raise ValueError("aesmc_amd: affine_logweight_backward needs grad_lw or (lw, lse, grad_lse)")
         x_prev, x = self._dense16(x_prev), self._dense16(x)
-        if y_rows.stride(1) != 1:
-            y_rows = y_rows.contiguous()
-        make = lambda shape, wanted: torch.empty(shape, dtype=x.dtype, device=x.device) if wanted else None
-        gx_prev, gx = make((B, K, dx), need[0]), make((B, K, dx), need[1])
-        rows_p = make((B, dx), need[4] and off_p is not None)      # location gradients summed over each row's particles
-        rows_g = make((B, dy), (need[6] and off_g is not None) or need[2])
-        rows_q = make((B, dx), need[8] and off_q is not None)
-        gA, gC, gQ = make((dx, dx), need[3]), make((dy, dx), need[5]), make((dx, dx), need[7])
-        gscales = make((3,), need[9] or need[10] or need[11])
+        y_rows = self._unit_rows(y_rows)
+        make = lambda wanted: torch.empty((B, K, dx), dtype=x.dtype, device=x.device) if wanted else None
+        gx_prev, gx = make(need[0]), make(need[1])
+        sums = self._affine_grad_buffers(need, offsets, dx, dy, x.dtype, x.device, B=B)
         ws_bytes = int(self._lib.aesmc_affine_backward_workspace_bytes(tag, B, K))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        outs = _lib.AffineLogweightGrads(_ptr(gx_prev), _ptr(gx), 0, 0, 0, _ptr(gA), _ptr(gC), _ptr(gQ), _ptr(gscales),
-                                         _ptr(rows_p), _ptr(rows_g), _ptr(rows_q))
+        outs = _lib.AffineLogweightGrads(_ptr(gx_prev), _ptr(gx), 0, 0, 0, *map(_ptr, sums))
         maps = [self._affine_map(*term) for term in (transition, emission, proposal)]
-        with _on_device(x.device):
-            args = (tag, _ptr(x_prev), _ptr(x), _ptr(y_rows), y_rows.stride(0), ctypes.byref(maps[0][0]),
-                    ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]), _ptr(scales[0]), _ptr(scales[1]),
-                    _ptr(scales[2]), _ptr(lw) if fused_lse else 0, _ptr(lse) if fused_lse else 0,
-                    _ptr(grad_lse) if fused_lse else 0, _ptr(grad_lw), ctypes.byref(outs), _ptr(ws), ws_bytes, B, K,
-                    self._stream(x))
-            status = self._lib.aesmc_affine_normal_logweight_backward(*args)
-            if status == 2:     # too few particles per batch row for the fused kernel's row table
-                return self.affine_logweight_backward_unfused(
-                    x_prev, x, y_rows, transition, emission, proposal, scales, need, grad_lw=grad_lw,
-                    lw=lw if fused_lse else None, lse=lse if fused_lse else None,
-                    grad_lse=grad_lse if fused_lse else None)
-            _lib.check(status, "aesmc_affine_normal_logweight_backward")
-            if self.timer is not None:
-                dense = [t for t in (gx_prev, gx) if t is not None]
-                nbytes = x.element_size() * (B * K * (2 * dx + 1)) + sum(t.numel() * t.element_size() for t in dense)
-                self.timer.note("affine_normal_logweight_backward",
-                                (self._lib.aesmc_affine_normal_logweight_backward, args), nbytes,
-                                (x_prev, x, y_rows, lw, lse, grad_lse, grad_lw, outs, ws, maps, scales, gA, gC, gQ,
-                                 gscales, rows_p, rows_g, rows_q) + tuple(dense))
-        fold = lambda rows, off: rows if off.dim() == 2 else rows.sum(dim=0)     # a shared [d] offset: all rows
-        grads = [gx_prev, gx, None, gA, None, gC, None, gQ, None, None, None, None]
-        if need[2]:
-            grads[2] = -rows_g
-        if rows_p is not None:
-            grads[4] = fold(rows_p, off_p)
-        if need[6] and off_g is not None:
-            grads[6] = fold(rows_g, off_g)
-        if rows_q is not None:
-            grads[8] = fold(rows_q, off_q)
-        for slot, s in ((9, scales[0]), (10, scales[1]), (11, scales[2])):
-            if need[slot]:
-                grads[slot] = gscales[slot - 9].reshape(s.shape)
-        return grads
+        args = (tag, _ptr(x_prev), _ptr(x), _ptr(y_rows), y_rows.stride(0)) + self._map_args(maps, scales) + \
+            (_ptr(lw) if fused_lse else 0, _ptr(lse) if fused_lse else 0, _ptr(grad_lse) if fused_lse else 0,
+             _ptr(grad_lw), ctypes.byref(outs), _ptr(ws), ws_bytes, B, K, self._stream(x))
+        if not self._launch(x.device, self._lib.aesmc_affine_normal_logweight_backward, args,
+                            lambda: x.element_size() * (B * K * (2 * dx + 1)) +
+                            sum(t.numel() * t.element_size() for t in (gx_prev, gx) if t is not None),
+                            (x_prev, x, y_rows, lw, lse, grad_lse, grad_lw, outs, ws, maps, scales) + sums + (gx_prev, gx),
+                            decline=True):
+            # too few particles per batch row for the fused kernel's row table
+            return self.affine_logweight_backward_unfused(
+                x_prev, x, y_rows, transition, emission, proposal, scales, need, grad_lw=grad_lw,
+                lw=lw if fused_lse else None, lse=lse if fused_lse else None,
+                grad_lse=grad_lse if fused_lse else None)
+        return self._affine_grad_slots(gx_prev, gx, sums, need, offsets, scales)
 
     def affine_logweight_backward_unfused(self, x_prev, x, y_rows, transition, emission, proposal, scales, need,
                                           grad_lw=None, lw=None, lse=None, grad_lse=None):
@@ -1616,22 +1514,22 @@ class HipKernels:
             raise ValueError("aesmc_amd: affine_step_backward operands outside what kernel K14 covers")
         if need[1]:
             raise ValueError("aesmc_amd: affine_step_backward: x is the proposal's draw and has no gradient slot")
-        (A, off_p), (C, off_g), (Q, off_q) = transition, emission, proposal
+        offsets = (transition[1], emission[1], proposal[1])
         tag = _DTYPE_TAG[x.dtype]
         B, K, dx = x.shape
         dy = y_rows.size(1)
-        check = lambda t, shape, what: None if (t.shape == shape and t.dtype == x.dtype and t.device == x.device) \
-            else (_ for _ in ()).throw(ValueError("aesmc_amd: {} must be {} {} on {}".format(what, shape, x.dtype, x.device)))
         fused_lse = grad_lse is not None
         if fused_lse:
             lw, lse, grad_lse = lw.contiguous(), lse.contiguous(), grad_lse.contiguous()
-            check(lw, (B, K), "lw"), check(lse, (B,), "lse"), check(grad_lse, (B,), "grad_lse")
+            self._expect(lw, (B, K), x, "lw")
+            self._expect(lse, (B,), x, "lse")
+            self._expect(grad_lse, (B,), x, "grad_lse")
         if grad_lw is not None:
             grad_lw = grad_lw.contiguous()
-            check(grad_lw, (B, K), "grad_lw")
+            self._expect(grad_lw, (B, K), x, "grad_lw")
         if grad_x is not None:
             grad_x = self._dense16(grad_x)
-            check(grad_x, (B, K, dx), "grad_x")
+            self._expect(grad_x, (B, K, dx), x, "grad_x")
         if not fused_lse and grad_lw is None and grad_x is None and child_grad is None:
             raise ValueError("aesmc_amd: affine_step_backward needs a gradient: (lw, lse, grad_lse), grad_lw or grad_x")
         if child_grad is not None:
@@ -1639,103 +1537,69 @@ class HipKernels:
             # kernel sums each particle's children itself — torch.gather's backward, where it is consumed
             if ancestors is None:
                 raise ValueError("aesmc_amd: affine_step_backward folds the children's gradient only through ancestors")
-            check(child_grad, (B, K, dx), "child_grad")
+            self._expect(child_grad, (B, K, dx), x, "child_grad")
             child_grad = self._dense16(child_grad)
             if child_end is None or child_end.shape != (B, K) or child_end.dtype != torch.int32 or \
                     child_end.device != x.device:
                 raise ValueError("aesmc_amd: affine_step_backward child_end must be int32 [{}, {}] on {}".format(B, K, x.device))
             child_end = child_end.contiguous()
-        if ancestors is not None:
-            # `x_prev` is the un-resampled latent: the kernel fetches x_prev[b, ancestors[b,k]] itself and slot 0 of
-            # the result is the gradient of those RESAMPLED rows (the caller sums children into ancestors)
-            self._check_index(x_prev, ancestors)
-            if ancestors.shape != (B, K):
-                raise ValueError("aesmc_amd: affine_step_backward ancestors must be [{}, {}]".format(B, K))
-            ancestors = ancestors.contiguous()
+        # `x_prev` is the un-resampled latent when `ancestors` is given: the kernel fetches x_prev[b, ancestors[b,k]]
+        # itself and slot 0 of the result is the gradient of those RESAMPLED rows (the caller sums children into ancestors)
+        ancestors = self._ancestors(x_prev, ancestors, B, K, "affine_step_backward")
         x_prev, x = self._dense16(x_prev), self._dense16(x)
-        if y_rows.stride(1) != 1:
-            y_rows = y_rows.contiguous()
-        make = lambda shape, wanted: torch.empty(shape, dtype=x.dtype, device=x.device) if wanted else None
-        gx_prev = make((B, K, dx), need[0])
-        rows_p = make((B, dx), need[4] and off_p is not None)
-        rows_g = make((B, dy), (need[6] and off_g is not None) or need[2])
-        rows_q = make((B, dx), need[8] and off_q is not None)
+        y_rows = self._unit_rows(y_rows)
+        gx_prev = torch.empty((B, K, dx), dtype=x.dtype, device=x.device) if need[0] else None
         carry = chain["carry"] if chain is not None else None
         defer = chain is not None and bool(chain["defer"])
-        gA, gC, gQ = (make((dx, dx), need[3] and not defer), make((dy, dx), need[5] and not defer),
-                      make((dx, dx), need[7] and not defer))
-        gscales = make((3,), (need[9] or need[10] or need[11]) and not defer)
+        sums = self._affine_grad_buffers(need, offsets, dx, dy, x.dtype, x.device, B=B, sums=not defer)
         ws_bytes = int(self._lib.aesmc_affine_backward_workspace_bytes(tag, B, K))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        outs = _lib.AffineLogweightGrads(_ptr(gx_prev), 0, 0, 0, 0, _ptr(gA), _ptr(gC), _ptr(gQ), _ptr(gscales),
-                                         _ptr(rows_p), _ptr(rows_g), _ptr(rows_q))
+        outs = _lib.AffineLogweightGrads(_ptr(gx_prev), 0, 0, 0, 0, *map(_ptr, sums))
         maps = [self._affine_map(*term) for term in (transition, emission, proposal)]
-        with _on_device(x.device):
-            middle = (_ptr(x), _ptr(y_rows), y_rows.stride(0), ctypes.byref(maps[0][0]),
-                      ctypes.byref(maps[1][0]), ctypes.byref(maps[2][0]), _ptr(scales[0]), _ptr(scales[1]),
-                      _ptr(scales[2]), _ptr(lw) if fused_lse else 0, _ptr(lse) if fused_lse else 0,
-                      _ptr(grad_lse) if fused_lse else 0, _ptr(grad_lw), _ptr(grad_x))
-            tail = (ctypes.byref(outs), _ptr(ws), ws_bytes)
-            link = None
-            if chain is not None:
-                # (carry[2], carry[3]: where the run's interleaved weight pairs lie and the workspace that holds them — built by
-                #  the run's first call, handed on from step to step instead of one small launch per step)
-                pairs_in = carry[2] if carry is not None and len(carry) > 2 and carry[2] else 0
-                link = _lib.AffineChain(_ptr(carry[0]) if carry is not None else 0, carry[1] if carry is not None else 0,
-                                        (2 if (need[9] or need[10] or need[11]) else 1) if defer else 0, 0, pairs_in, 0)
-            if ancestors is not None:
-                entry = self._lib.aesmc_affine_step_backward_resampled
-                args = (tag, _ptr(x_prev), _ptr(ancestors)) + middle + (_ptr(child_grad), _ptr(child_end)) + tail + \
-                    (_ptr(self.flags(x.device)), ctypes.byref(link) if link is not None else None, B, K, self._stream(x))
-            else:
-                entry = self._lib.aesmc_affine_step_backward
-                args = (tag, _ptr(x_prev)) + middle + tail + (B, K, self._stream(x))
-            status = entry(*args)
-            if status == 2 and child_grad is not None:      # the unfused route takes the summed gradient as a tensor
+        middle = (_ptr(x), _ptr(y_rows), y_rows.stride(0)) + self._map_args(maps, scales) + \
+            (_ptr(lw) if fused_lse else 0, _ptr(lse) if fused_lse else 0, _ptr(grad_lse) if fused_lse else 0,
+             _ptr(grad_lw), _ptr(grad_x))
+        tail = (ctypes.byref(outs), _ptr(ws), ws_bytes)
+        link = None
+        if chain is not None:
+            # (carry[2], carry[3]: where the run's interleaved weight pairs lie and the workspace that holds them — built by
+            #  the run's first call, handed on from step to step instead of one small launch per step)
+            pairs_in = carry[2] if carry is not None and len(carry) > 2 and carry[2] else 0
+            link = _lib.AffineChain(_ptr(carry[0]) if carry is not None else 0, carry[1] if carry is not None else 0,
+                                    (2 if (need[9] or need[10] or need[11]) else 1) if defer else 0, 0, pairs_in, 0)
+        if ancestors is not None:
+            entry = self._lib.aesmc_affine_step_backward_resampled
+            args = (tag, _ptr(x_prev), _ptr(ancestors)) + middle + (_ptr(child_grad), _ptr(child_end)) + tail + \
+                (_ptr(self.flags(x.device)), ctypes.byref(link) if link is not None else None, B, K, self._stream(x))
+        else:
+            entry = self._lib.aesmc_affine_step_backward
+            args = (tag, _ptr(x_prev)) + middle + tail + (B, K, self._stream(x))
+        esz = x.element_size()
+        nbytes = lambda: esz * B * K * (2 * dx + 1 + (dx if grad_x is not None else 0) + (dx if gx_prev is not None else 0)) + \
+            (8 * B * K if ancestors is not None else 0) + (esz * B * K * dx + 4 * B * K if child_grad is not None else 0)
+        if not self._launch(x.device, entry, args, nbytes,
+                            (x_prev, ancestors, x, y_rows, lw, lse, grad_lse, grad_lw, grad_x, child_grad, child_end, outs,
+                             ws, maps, scales) + sums + (gx_prev, link, carry), decline=True):
+            if child_grad is not None:      # the unfused route takes the summed gradient as a tensor
                 summed = self.gather_backward_ranges(child_grad, child_end)
                 grad_x, child_grad, child_end = (summed if grad_x is None else grad_x + summed), None, None
-            if status == 2 and ancestors is not None:       # the unfused route wants the resampled rows as a tensor
+            if ancestors is not None:       # the unfused route wants the resampled rows as a tensor
                 x_prev, ancestors = self.gather(x_prev, ancestors), None
-            if status == 2:     # too few particles per batch row for the fused kernel's row table
-                grads = self.affine_step_backward_unfused(
-                    x_prev, x, y_rows, transition, emission, proposal, scales, need, lw if fused_lse else None,
-                    lse if fused_lse else None, grad_lse=grad_lse if fused_lse else None, grad_x=grad_x,
-                    grad_lw=grad_lw)
-                if carry is not None:      # what the steps before left: finished here, added to this step's own
-                    carried = self.affine_backward_collect(carry, x.dtype, x.device, dx, dy, need, scales)
-                    for slot, value in enumerate(carried):
-                        if value is not None:
-                            grads[slot] = value if grads[slot] is None else grads[slot] + value
-                return grads
-            _lib.check(status, "aesmc_affine_step_backward")
-            if defer:
-                handed_on = carry is not None and len(carry) > 2 and carry[2] and link.pairs_out == carry[2]
-                chain["left"] = (ws, int(link.records), link.pairs_out or 0, carry[3] if handed_on else ws)
-            if self.timer is not None:
-                nbytes = x.element_size() * B * K * (2 * dx + 1 + (dx if grad_x is not None else 0) +
-                                                     (dx if gx_prev is not None else 0))
-                if ancestors is not None:
-                    nbytes += 8 * B * K
-                if child_grad is not None:
-                    nbytes += x.element_size() * B * K * dx + 4 * B * K
-                self.timer.note("affine_step_backward" + ("_resampled" if ancestors is not None else ""), (entry, args),
-                                nbytes, (x_prev, ancestors, x, y_rows, lw, lse, grad_lse, grad_lw, grad_x, child_grad,
-                                         child_end, outs, ws, maps, scales, gA, gC, gQ, gscales, rows_p, rows_g, rows_q,
-                                         gx_prev, link, carry))
-        fold = lambda rows, off: rows if off.dim() == 2 else rows.sum(dim=0)
-        grads = [gx_prev, None, None, gA, None, gC, None, gQ, None, None, None, None]
-        if need[2]:
-            grads[2] = -rows_g
-        if rows_p is not None:
-            grads[4] = fold(rows_p, off_p)
-        if need[6] and off_g is not None:
-            grads[6] = fold(rows_g, off_g)
-        if rows_q is not None:
-            grads[8] = fold(rows_q, off_q)
-        for slot, s in ((9, scales[0]), (10, scales[1]), (11, scales[2])):
-            if need[slot] and gscales is not None:
-                grads[slot] = gscales[slot - 9].reshape(s.shape)
-        return grads
+            # too few particles per batch row for the fused kernel's row table
+            grads = self.affine_step_backward_unfused(
+                x_prev, x, y_rows, transition, emission, proposal, scales, need, lw if fused_lse else None,
+                lse if fused_lse else None, grad_lse=grad_lse if fused_lse else None, grad_x=grad_x,
+                grad_lw=grad_lw)
+            if carry is not None:      # what the steps before left: finished here, added to this step's own
+                carried = self.affine_backward_collect(carry, x.dtype, x.device, dx, dy, need, scales)
+                for slot, value in enumerate(carried):
+                    if value is not None:
+                        grads[slot] = value if grads[slot] is None else grads[slot] + value
+            return grads
+        if defer:
+            handed_on = carry is not None and len(carry) > 2 and carry[2] and link.pairs_out == carry[2]
+            chain["left"] = (ws, int(link.records), link.pairs_out or 0, carry[3] if handed_on else ws)
+        return self._affine_grad_slots(gx_prev, None, sums, need, offsets, scales)
 
     @property
     def wide_dim(self):
@@ -1763,13 +1627,10 @@ class HipKernels:
         sq = torch.empty((B, K), dtype=torch.float32, device=u.device) if want_sq else None
         tiles = K // self.wide_adjoint_tile
         rows = torch.empty((B, tiles, d), dtype=torch.float32, device=u.device) if want_rows else None
-        with _on_device(u.device):
-            args = (_ptr(u), _ptr(weight), _ptr(scale), _ptr(base), base.stride(0) if base is not None else 0, _ptr(sq),
-                    _ptr(rows), B, K, self._stream(u))
-            _lib.check(self._lib.aesmc_wide_adjoint_scale(*args), "aesmc_wide_adjoint_scale")
-            if self.timer is not None:
-                self.timer.note("wide_adjoint_scale", (self._lib.aesmc_wide_adjoint_scale, args), 8 * u.numel(),
-                                (u, weight, scale, sq, rows, base))
+        self._launch(u.device, self._lib.aesmc_wide_adjoint_scale,
+                     (_ptr(u), _ptr(weight), _ptr(scale), _ptr(base), base.stride(0) if base is not None else 0, _ptr(sq),
+                      _ptr(rows), B, K, self._stream(u)),
+                     lambda: 8 * u.numel(), (u, weight, scale, sq, rows, base))
         return sq, (rows.sum(1) if rows is not None else None)
 
     def wide_adjoint_merge(self, u_p, at_x, weight, scale, want_sq, want_rows_p, want_rows_x, value=None, base=None,
@@ -1783,14 +1644,11 @@ class HipKernels:
         sq = torch.empty((B, K), dtype=torch.float32, device=u_p.device) if want_sq else None
         rows_p = torch.empty((B, tiles, d), dtype=torch.float32, device=u_p.device) if want_rows_p else None
         rows_x = torch.empty((B, tiles, d), dtype=torch.float32, device=u_p.device) if want_rows_x else None
-        with _on_device(u_p.device):
-            args = (_ptr(u_p), _ptr(at_x), _ptr(weight), _ptr(scale), _ptr(value), _ptr(base),
-                    base.stride(0) if base is not None else 0, _ptr(add), _ptr(sq), _ptr(rows_p), _ptr(rows_x), B, K,
-                    self._stream(u_p))
-            _lib.check(self._lib.aesmc_wide_adjoint_merge(*args), "aesmc_wide_adjoint_merge")
-            if self.timer is not None:
-                self.timer.note("wide_adjoint_merge", (self._lib.aesmc_wide_adjoint_merge, args), 16 * u_p.numel(),
-                                (u_p, at_x, weight, scale, sq, rows_p, rows_x, value, base, add))
+        self._launch(u_p.device, self._lib.aesmc_wide_adjoint_merge,
+                     (_ptr(u_p), _ptr(at_x), _ptr(weight), _ptr(scale), _ptr(value), _ptr(base),
+                      base.stride(0) if base is not None else 0, _ptr(add), _ptr(sq), _ptr(rows_p), _ptr(rows_x), B, K,
+                      self._stream(u_p)),
+                     lambda: 16 * u_p.numel(), (u_p, at_x, weight, scale, sq, rows_p, rows_x, value, base, add))
         return sq, (rows_p.sum(1) if rows_p is not None else None), (rows_x.sum(1) if rows_x is not None else None)
 
     def affine_step_backward_wide(self, x_prev, x, y_rows, transition, emission, proposal, scales, need, lw, lse,
@@ -1934,21 +1792,12 @@ class HipKernels:
         """The weights' and scales' gradients (a 12-slot list like affine_step_backward's, None elsewhere) out of the
         records a deferring K14 call left — `left` = its chain["left"] — when no later call carried them on."""
         ws, records = left[0], left[1]      # (+ where the run's weight pairs lie and their holder: not needed here)
-        make = lambda shape, wanted: torch.empty(shape, dtype=dtype, device=device) if wanted else None
-        gA, gC, gQ = make((dx, dx), need[3]), make((dy, dx), need[5]), make((dx, dx), need[7])
-        gscales = make((3,), need[9] or need[10] or need[11])
-        outs = _lib.AffineLogweightGrads(0, 0, 0, 0, 0, _ptr(gA), _ptr(gC), _ptr(gQ), _ptr(gscales), 0, 0, 0)
-        with _on_device(device):
-            args = (_DTYPE_TAG[dtype], _ptr(ws), records, dx, dy, ctypes.byref(outs), self._stream(ws))
-            _lib.check(self._lib.aesmc_affine_backward_collect(*args), "aesmc_affine_backward_collect")
-            if self.timer is not None:
-                self.timer.note("affine_backward_collect", (self._lib.aesmc_affine_backward_collect, args),
-                                records * 1024 * (8 if dtype == torch.float64 else 4), (ws, outs, gA, gC, gQ, gscales))
-        grads = [None, None, None, gA, None, gC, None, gQ, None, None, None, None]
-        for slot, s in ((9, scales[0]), (10, scales[1]), (11, scales[2])):
-            if need[slot]:
-                grads[slot] = gscales[slot - 9].reshape(s.shape)
-        return grads
+        sums = self._affine_grad_buffers(need, (None, None, None), dx, dy, dtype, device)
+        outs = _lib.AffineLogweightGrads(0, 0, 0, 0, 0, *map(_ptr, sums))
+        self._launch(device, self._lib.aesmc_affine_backward_collect,
+                     (_DTYPE_TAG[dtype], _ptr(ws), records, dx, dy, ctypes.byref(outs), self._stream(ws)),
+                     lambda: records * 1024 * (8 if dtype == torch.float64 else 4), (ws, outs) + sums)
+        return self._affine_grad_slots(None, None, sums, need, (None, None, None), scales)
 
 
     def affine_step_backward_unfused(self, x_prev, x, y_rows, transition, emission, proposal, scales, need, lw, lse,
@@ -1983,11 +1832,7 @@ class HipKernels:
     def particle_summary(self, log_w, value=None, want_log_ess=False, want_mean=False, want_second=False):
         """(log_ess [B], mean [B,...], second moment [B,...]) under w = softmax(log_w, dim=1); entries
         not asked for are None.  value [B,K,...] of log_w's dtype, may be strided."""
-        _require_hip(log_w, "log_weight")
-        tag = _tag(log_w, "log_weight")
-        if log_w.dim() != 2:
-            raise ValueError("aesmc_amd: log_weight must be [batch_size, num_particles], got {}"
-                             .format(tuple(log_w.shape)))
+        tag = self._rows_operand(log_w, "log_weight")
         B, K = log_w.shape
         if K == 0:
             raise ValueError("aesmc_amd: particle summaries need at least one particle")
@@ -2015,15 +1860,12 @@ class HipKernels:
                 second.zero_()
         ws_bytes = int(self._lib.aesmc_particle_summary_workspace_bytes(tag, B, K, D))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=log_w.device) if ws_bytes else None
-        with _on_device(log_w.device):
-            args = (tag, _ptr(log_w), ctypes.byref(view) if view is not None else None,
-                    _ptr(log_ess), _ptr(mean) if D > 0 else 0, _ptr(second) if D > 0 else 0, B, K, D,
-                    _ptr(ws), ws_bytes, self._stream(log_w))
-            _lib.check(self._lib.aesmc_particle_summary(*args), "aesmc_particle_summary")
-            if self.timer is not None:
-                nbytes = log_w.numel() * log_w.element_size() + (self._unique_bytes(value) if view is not None else 0)
-                self.timer.note("particle_summary", (self._lib.aesmc_particle_summary, args), nbytes,
-                                (log_w, value, view, log_ess, mean, second, ws))
+        self._launch(log_w.device, self._lib.aesmc_particle_summary,
+                     (tag, _ptr(log_w), ctypes.byref(view) if view is not None else None,
+                      _ptr(log_ess), _ptr(mean) if D > 0 else 0, _ptr(second) if D > 0 else 0, B, K, D,
+                      _ptr(ws), ws_bytes, self._stream(log_w)),
+                     lambda: log_w.numel() * log_w.element_size() + (self._unique_bytes(value) if view is not None else 0),
+                     (log_w, value, view, log_ess, mean, second, ws))
         return log_ess, mean, second
 
 

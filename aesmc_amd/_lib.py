@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libaesmc_hip.so")
 
 OK = 0
+ERR_UNSUPPORTED = 2  # the kernel does not cover the operands' shape; nothing was launched
 ERR_NAMES = {1: "invalid argument", 2: "unsupported shape", 3: "kernel launch failed",
              4: "workspace missing or too small"}
 FLAG_NAN_LOG_WEIGHT = 1
