@@ -138,6 +138,7 @@ TEST_HOOKS = {
     "aesmc_test_set_k2_form": (_i32, [_i32]),
     "aesmc_test_last_k2_form": (_i32, []),
     "aesmc_test_last_logweight_backward_form": (_i32, []),
+    "aesmc_test_last_affine_backward_particles_per_lane": (_i32, []),
 }
 
 _lib = None

@@ -2,6 +2,7 @@
 // for the forward kernels, the arithmetic contract and the reference call sites).  The weight gradients are
 // contractions over the particle index and run on the matrix cores; everything per particle stays on the
 // vector ALUs, one lane = one particle.
+#include <atomic>
 #include "linear_gaussian_backward.hpp"
 namespace aesmc {
 
@@ -1060,6 +1061,9 @@ static int launch_particle_affine_backward(const void *g, const void *x, const a
   return AESMC_OK;
 }
 
+// particles per lane of the last K12 / K14 launch (0: declined) — what the size and LDS rules above came to (test hook below)
+static std::atomic<int> g_lg_bwd_last_ppl{0};
+
 template <typename T, int DP, int PPL>
 static constexpr auto affine_step_backward_exact = &affine_step_backward_kernel<T, DP, PPL, true>;
 template <typename T, int DP, int PPL>
@@ -1081,7 +1085,9 @@ static int launch_affine_logweight_backward(const void *xprev, const void *x, co
   static const int forced = [] { const char *v = measurement_knob("AESMC_LG_BWD_PPL"); return v != nullptr ? atoi(v) : 0; }();   // measurement knob
   // rows of ten float32 values, tiles inside one batch row, an nn.Linear's weights: the second form of the step kernel
   bool rows_form = false;
-  if constexpr (sizeof(T) == 4) rows_form = step && N % kLgBlock == 0 && affine_step_backward_rows_covers(mp, mg, mq, B, K);
+  // (the question is put for every float32 step: aesmc_test_last_step_backward_form reports this DECISION — a shape
+  //  declined further down still reads 1; the rows form takes whole tiles only, which `covers` asks of K itself)
+  if constexpr (sizeof(T) == 4) rows_form = step && affine_step_backward_rows_covers(mp, mg, mq, B, K);
   int ppl = (sizeof(T) == 4 && dp <= 12 && !lg_few_tiles(N)) ? 2 : 1;
   // the step kernel is latency-bound: one particle per lane and three workgroups per CU where the registers
   // allow it without spills (d = 10: 322 -> 300 us; d = 8: no difference; d = 12: 448 -> 477, kept at two)
@@ -1095,6 +1101,7 @@ static int launch_affine_logweight_backward(const void *xprev, const void *x, co
                        std::max(lg_tile_elems<T>(tp, dx), lg_tile_elems<T>(tp, dy)));
     if (lds <= (ppl > 1 ? (size_t)78 * 1024 : kLgLdsLimit) && lg_rows_spanned((int64_t)tp, K) <= kLgRowsMax) break;
   }
+  g_lg_bwd_last_ppl.store(ppl < 1 ? 0 : ppl, std::memory_order_relaxed);
   if (ppl < 1) return AESMC_ERR_UNSUPPORTED;   // fewer than ~43 particles per batch row: the caller takes the unfused route
   // the children's rows go through a tile of their own where that costs no resident workgroup (else lanes fetch them)
   bool child_stage = false;
@@ -1212,6 +1219,10 @@ static int launch_affine_collect(const void *ws, int records, int64_t dx, int64_
 }  // namespace aesmc
 
 using namespace aesmc;
+
+extern "C" int aesmc_test_last_affine_backward_particles_per_lane(void) {
+  return aesmc::g_lg_bwd_last_ppl.load(std::memory_order_relaxed);
+}
 
 extern "C" int aesmc_affine_normal_logweight_backward(
     int dtype, const void *x_prev, const void *x, const void *y, int64_t y_stride_b, const aesmc_affine_map *transition,
