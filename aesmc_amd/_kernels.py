@@ -276,14 +276,40 @@ class HipKernels:
         return tag
 
     def _resampling_operands(self, log_w, u):
-        """(tag, B, K) of K2's operands: log_w [B,K] float32/64, u B float64 values on its device."""
+        """(tag, B, K, stratified) of K2's operands: log_w [B,K] float32/64, u float64 on its device.  The SHAPE of the
+        uniforms names the scheme: B values (one per batch row) — systematic; [B,K] (one per particle) — stratified."""
         _require_hip(log_w, "log_weight")
         _require_hip(u, "uniforms")
         tag = self._rows_operand(log_w, "log_weight")
         B, K = log_w.shape
-        if u.dtype != torch.float64 or u.numel() != B or u.device != log_w.device:
-            raise ValueError("aesmc_amd: uniforms must be {} float64 values on {}".format(B, log_w.device))
-        return tag, B, K
+        stratified = u.dim() == 2 and tuple(u.shape) == (B, K)      # (K == 1: the two schemes are the same function)
+        if u.dtype != torch.float64 or u.device != log_w.device or not (stratified or u.numel() == B):
+            raise ValueError("aesmc_amd: uniforms must be {} float64 values (systematic) or [{}, {}] float64 (stratified) "
+                             "on {}".format(B, B, K, log_w.device))
+        return tag, B, K, stratified
+
+    def _stratified(self, tag, log_w, u, B, K, want_lse, want_child_end, decline):
+        """The one launch of the stratified scheme (aesmc_resample_step_stratified): (idx, lse, child_end), or None where
+        the library declines (`decline`: by-products beyond the in-workgroup limit)."""
+        idx = torch.empty((B, K), dtype=torch.int64, device=log_w.device)
+        lse = torch.empty((B,), dtype=log_w.dtype, device=log_w.device) if want_lse else None
+        child_end = torch.empty((B, K), dtype=torch.int32, device=log_w.device) if want_child_end else None
+        if idx.numel() == 0:
+            return idx, lse, child_end
+        ws_bytes = int(self._lib.aesmc_workspace_bytes(B, K))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=log_w.device) if ws_bytes else None
+        # the systematic step's 12 B per particle plus one float64 uniform each
+        nbytes = lambda: B * K * (log_w.element_size() + 16) + (4 * B * K if child_end is not None else 0) + \
+            (B * log_w.element_size() if lse is not None else 0)
+        if not self._launch(log_w.device, self._lib.aesmc_resample_step_stratified,
+                            (tag, _ptr(log_w), _ptr(u), _ptr(idx), _ptr(lse), _ptr(child_end),
+                             _ptr(self.flags(log_w.device)), B, K, _ptr(ws), ws_bytes, self._stream(log_w)),
+                            nbytes, (log_w, u, idx, lse, child_end, ws), name="resample_step_stratified", decline=decline):
+            return None
+        idx._aesmc_sorted = True  # one position per stratum: monotone in k, like the systematic scheme
+        if child_end is not None:
+            idx._aesmc_child_end = child_end
+        return idx, lse, child_end
 
     # ---- K1 ------------------------------------------------------------------------------------
     def logweight_lse(self, a, b=None, c=None, want_lw=True, want_lse=True):
@@ -358,10 +384,13 @@ class HipKernels:
 
     # ---- K2 ------------------------------------------------------------------------------------
     def ancestor_index(self, log_w, u):
-        """log_w [B,K] float32/64, u [B] float64 (both on the HIP device) -> int64 [B,K]."""
-        tag, B, K = self._resampling_operands(log_w, u)
+        """log_w [B,K] float32/64, u float64 (both on the HIP device) -> int64 [B,K].  u [B]: systematic resampling
+        (one uniform per batch row); u [B,K]: stratified (one per particle)."""
+        tag, B, K, stratified = self._resampling_operands(log_w, u)
         log_w = log_w.contiguous()
         u = u.contiguous()
+        if stratified:
+            return self._stratified(tag, log_w, u, B, K, False, False, decline=False)[0]
         idx = torch.empty((B, K), dtype=torch.int64, device=log_w.device)
         ws_bytes = int(self._lib.aesmc_workspace_bytes(B, K))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=log_w.device) if ws_bytes else None
@@ -400,12 +429,19 @@ class HipKernels:
         lse = logsumexp over particles [B] when `want_lse`, payload[b, idx[b,k]] as `gather` when a
         payload tensor [B,K,...] is given (else None).  Returns None when the launch does not cover
         the operands (more particles than one workgroup holds, payload rows not 4-byte multiples):
-        the caller then runs `ancestor_index` / `gather` / `logweight_lse` separately."""
-        tag, B, K = self._resampling_operands(log_w, u)
+        the caller then runs `ancestor_index` / `gather` / `logweight_lse` separately.
+        u [B,K] (stratified resampling): the stratified launch, which has no payload tail — `moved` is None whatever
+        payload was offered and the caller gathers with the indices."""
+        tag, B, K, stratified = self._resampling_operands(log_w, u)
         if K > self.lds_max_particles:
             return None
         log_w = log_w.contiguous()
         u = u.contiguous()
+        if stratified:
+            if log_w.numel() == 0:
+                return None
+            out = self._stratified(tag, log_w, u, B, K, want_lse, want_child_end, decline=True)
+            return None if out is None else (out[0], out[1], None)
         row_bytes = sb = sk = 0
         dst = None
         if payload is not None:

@@ -349,7 +349,7 @@ def row_logsumexp(x):
 
 
 class _ResampleStep(torch.autograd.Function):
-    """(idx, lse, moved) of the fused resampling step.  idx carries no gradient
+    """(idx, lse, moved) of the fused resampling step (either scheme: see `resample_step`).  idx carries no gradient
     (aesmc/inference.py:254); lse differentiates into the log-weights as K1's does; moved =
     payload[b, idx[b,k]] differentiates into the payload by the sorted segmented sum."""
 
@@ -382,7 +382,8 @@ class _ResampleStep(torch.autograd.Function):
 
 def resample_step(log_weight, uniforms, payload=None, want_lse=False, pending=None, want_child_end=False):
     """One resampling step: (ancestor indices [B,K], logsumexp over particles [B] or None,
-    payload[b, idx[b,k], ...] or None).  One launch when the fused kernel covers the operands;
+    payload[b, idx[b,k], ...] or None).  `uniforms` [B]: systematic resampling; [B,K]: stratified (the provider reads
+    the scheme off the shape; the stratified launch copies no payload: `moved` is None).  One launch when the fused kernel covers the operands;
     `moved` is None when it does not cover the payload (the caller gathers with the indices).
     `pending` (with want_lse): the PendingStep of the step that produced `log_weight` — the log-sum-exp
     comes back bound to it (its gradient reaches that step's node), with no autograd node of its own."""
@@ -425,7 +426,7 @@ def resample_gather(value, idx):
 
 
 def ancestor_index(log_weight, uniforms):
-    """Systematic-resampling ancestor indices; never differentiable."""
+    """Ancestor indices — systematic resampling for uniforms [B], stratified for uniforms [B,K]; never differentiable."""
     return _kernels.get().ancestor_index(log_weight.detach(), uniforms)
 
 

@@ -49,7 +49,9 @@ def shard_observations(observations, rank, world_size):
 def shard_scope(global_batch_size, rank, world_size):
     """While active, the resampler's per-step uniforms are drawn for the whole global batch and
     sliced to this rank's rows, so a sharded run consumes numpy's RNG exactly like an unsharded
-    one and produces the same ancestor indices row for row."""
+    one and produces the same ancestor indices row for row.  That guarantee rests on the host block of
+    systematic resampling: stratified resampling (`settings.Settings.resampling`) draws per particle on the
+    device and raises NotImplementedError inside this scope rather than break it silently."""
     lo, hi = shard_bounds(global_batch_size, rank, world_size)
     token = _ACTIVE_SHARD.set((global_batch_size, lo, hi))
     try:

@@ -165,8 +165,18 @@ class GraphedLoss:
                         if p.requires_grad and all(p is not q for q in self.parameters):
                             self.parameters.append(p)
         num_timesteps = len(observations)
+        # The resampling scheme in force at construction is the captured one; every later evaluation (replays, the
+        # eager sides of the verification) keeps it.  Systematic: the static feed of host uniforms below.  Stratified: no
+        # feed — its per-particle draws are `torch.rand` calls inside the captured region, which PyTorch refreshes on
+        # every replay; the warm-up then sees the generator advance by more than went through `_philox`, so the
+        # captured region's noise goes through PyTorch too (the `advanced == counted` test below).
+        from . import settings
+        self.resampling = settings.current().resampling
+        if self.resampling == "stratified" and shard:
+            raise NotImplementedError("aesmc_amd: stratified resampling is not implemented for a sharded GraphedLoss "
+                                      "(see distributed.shard_scope); use resampling='systematic'")
         self.feed = _StaticUniformFeed(first.size(0), num_timesteps - 1, self.device) \
-            if algorithm == "aesmc" and num_timesteps > 1 else None
+            if algorithm == "aesmc" and num_timesteps > 1 and self.resampling == "systematic" else None
 
         kernels = _kernels.get()
         kernels.flags(self.device)                       # allocate the status word before capture
@@ -352,13 +362,14 @@ class GraphedLoss:
         if self.feed is not None:
             self.feed.begin()
         from . import settings
-        noise_scope = switches = contextlib.nullcontext()
+        noise_scope = contextlib.nullcontext()
+        changes = {"resampling": self.resampling}      # the scheme captured, whatever the caller's context says now
         if capturing:
             if self.noise is not None:
                 noise_scope = _philox.graph_noise_scope(self.noise)
             else:
-                switches = settings.override(kernel_noise=False)      # every draw through PyTorch's own captured generator state
-        with switches:
+                changes["kernel_noise"] = False      # every draw through PyTorch's own captured generator state
+        with settings.override(**changes):
             return self._evaluate_body(noise_scope, num_particles, algorithm, initial, transition, emission, proposal)
 
     def _evaluate_body(self, noise_scope, num_particles, algorithm, initial, transition, emission, proposal):

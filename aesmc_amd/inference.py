@@ -171,6 +171,39 @@ class _UniformFeed:
         return row
 
 
+class _StratifiedFeed:
+    """Per-resample uniforms of STRATIFIED resampling: one float64 per particle, `torch.rand` on the log-weights' own
+    device from torch's generator for that device — no host block, no copy, and capturable into a hipGraph as it is
+    (PyTorch refreshes a captured draw on every replay).  numpy's global RandomState is not consumed."""
+
+    def __init__(self, batch_size, num_particles, device):
+        self.shape = (batch_size, num_particles)
+        self.device = device
+
+    def next(self):
+        return torch.rand(self.shape, dtype=torch.float64, device=self.device)
+
+
+def _resolve_resampling(resampling):
+    """The resampling scheme in force: the argument, else `settings.current().resampling`.  ValueError for a name that
+    is no scheme; NotImplementedError for 'stratified' inside `distributed.shard_scope` (the sharded run equals the
+    unsharded one because every rank draws the GLOBAL host block of uniforms and keeps its rows; the per-particle
+    device draws of the stratified scheme have no such block)."""
+    if resampling is None:
+        resampling = settings.current().resampling
+    if resampling not in settings.RESAMPLING_SCHEMES:
+        raise ValueError("resampling must be one of {} (or None: the setting), got {!r}".format(
+            ", ".join(settings.RESAMPLING_SCHEMES), resampling))
+    if resampling == "stratified":
+        from . import distributed
+        if distributed.active_shard() is not None:
+            raise NotImplementedError(
+                "aesmc_amd: stratified resampling inside distributed.shard_scope is not implemented: a sharded run "
+                "reproduces the unsharded one through the global block of host uniforms every rank draws, which the "
+                "per-particle device draws of the stratified scheme do not have. Use resampling='systematic' when sharding.")
+    return resampling
+
+
 def draw_uniform_block(batch_size):
     """One resampling step's uniforms, float64 [batch_size], consuming numpy's global RandomState
     exactly as aesmc/inference.py:250 does (`np.random.uniform(size=[batch_size, 1])`); inside
@@ -192,7 +225,8 @@ _FEED_OVERRIDE = contextvars.ContextVar("aesmc_amd_feed_override", default=None)
 @contextlib.contextmanager
 def uniform_feed(feed):
     """While active, `infer` takes its per-resample uniforms from `feed` (an object with `next()`
-    returning a float64 [batch_size] device tensor) instead of drawing them itself."""
+    returning a float64 [batch_size] device tensor — under stratified resampling: float64
+    [batch_size, num_particles]) instead of drawing them itself."""
     token = _FEED_OVERRIDE.set(feed)
     try:
         yield
@@ -236,14 +270,20 @@ def _first_tensor(value):
     return next(iter(value.values())) if isinstance(value, dict) else value
 
 
-def sample_ancestral_index(log_weight):
+def sample_ancestral_index(log_weight, resampling=None):
     """Systematic resampling (aesmc/inference.py:234-269): log_weight [batch_size, num_particles]
     unnormalised -> zero-indexed ancestor LongTensor of the same shape on the same device.
-    Draws one np.random.uniform(size=[batch_size, 1]) block; raises FloatingPointError on NaN."""
+    Draws one np.random.uniform(size=[batch_size, 1]) block; raises FloatingPointError on NaN.
+    `resampling`: 'systematic', 'stratified' or None (`settings.current().resampling`).  Stratified draws
+    torch.rand((batch_size, num_particles), dtype=float64) on log_weight's device instead and leaves numpy's
+    RandomState alone; an unknown name raises ValueError."""
     batch_size = log_weight.size(0)
-    uniforms = torch.from_numpy(np.random.uniform(size=[batch_size, 1]).reshape(-1))
-    if log_weight.is_cuda:
-        uniforms = uniforms.to(log_weight.device)
+    if _resolve_resampling(resampling) == "stratified":
+        uniforms = torch.rand(tuple(log_weight.shape), dtype=torch.float64, device=log_weight.device)
+    else:
+        uniforms = torch.from_numpy(np.random.uniform(size=[batch_size, 1]).reshape(-1))
+        if log_weight.is_cuda:
+            uniforms = uniforms.to(log_weight.device)
     index = _ops.ancestor_index(log_weight, uniforms)
     # every bit raises — also one left behind by an earlier deferred check: an all -inf (or +inf) row
     # yields indices equal to num_particles, where the reference fails inside np.digitize / torch.gather
@@ -283,7 +323,7 @@ def infer(inference_algorithm, observations, initial, transition, emission,
           proposal, num_particles, return_log_marginal_likelihood=False,
           return_latents=True, return_original_latents=False,
           return_log_weight=True, return_log_weights=False,
-          return_ancestral_indices=False):
+          return_ancestral_indices=False, resampling=None):
     """Runs 'is' or 'smc' inference (aesmc/inference.py:8-193).
 
     observations: length-T sequence of [batch_size, ...] tensors (or dicts of them).
@@ -297,6 +337,14 @@ def infer(inference_algorithm, observations, initial, transition, emission,
     Returns a dict with keys log_marginal_likelihood [batch_size], latents, original_latents,
     log_weight [batch_size, num_particles], log_weights, ancestral_indices (None unless requested
     through the return_* flags) and last_latent (always).
+
+    resampling: the scheme 'smc' resamples by — 'systematic' (the reference's), 'stratified', or None for
+    `settings.current().resampling`; anything else raises ValueError.  Systematic draws one
+    np.random.uniform(size=[batch_size, 1]) block per resampling step from numpy's global RandomState, as the
+    reference does.  Stratified draws torch.rand((batch_size, num_particles), dtype=torch.float64) per step on the
+    log-weights' device from torch's generator for that device and does NOT consume numpy's RandomState: seed it with
+    torch.manual_seed.  `uniform_feed(feed)` overrides both (under stratified `feed.next()` returns float64
+    [batch_size, num_particles]).  Inside `distributed.shard_scope` stratified raises NotImplementedError.
 
     Data-dependent failures are collected in one status word per device and raised at the end (see
     `check_device_status`); the word is shared by every stream and thread using that device, so run
@@ -314,7 +362,7 @@ def infer(inference_algorithm, observations, initial, transition, emission,
             return _infer(inference_algorithm, observations, initial, transition, emission, proposal,
                           num_particles, return_log_marginal_likelihood, return_latents,
                           return_original_latents, return_log_weight, return_log_weights,
-                          return_ancestral_indices)
+                          return_ancestral_indices, resampling)
     except BaseException:
         _discard_pending_flags()
         raise
@@ -332,7 +380,7 @@ def _infer(inference_algorithm, observations, initial, transition, emission,
            proposal, num_particles, return_log_marginal_likelihood=False,
            return_latents=True, return_original_latents=False,
            return_log_weight=True, return_log_weights=False,
-           return_ancestral_indices=False):
+           return_ancestral_indices=False, resampling=None):
     """The body of `infer` (aesmc/inference.py:8-193).
 
     observations: length-T sequence of [batch_size, ...] tensors (or dicts of them).
@@ -351,6 +399,7 @@ def _infer(inference_algorithm, observations, initial, transition, emission,
         raise ValueError("inference_algorithm must be either is or smc. currently = {}".format(
             inference_algorithm))
     use_smc = inference_algorithm == "smc"
+    stratified = _resolve_resampling(resampling) == "stratified"
     # SMC differentiates the log-weights only through their per-step row log-sum-exp unless the caller
     # asks for the weights themselves (get_loss does not): then K5 runs without an autograd node and
     # the log-sum-exp — produced by the NEXT step's resampling launch — is tied to K5's operands
@@ -384,7 +433,17 @@ def _infer(inference_algorithm, observations, initial, transition, emission,
             if use_smc:
                 previous = log_weights[-1]
                 if feed is None:
-                    feed = _FEED_OVERRIDE.get() or _UniformFeed(batch_size, num_timesteps - 1, previous.device)
+                    feed = _FEED_OVERRIDE.get() or (
+                        _StratifiedFeed(batch_size, num_particles, previous.device) if stratified else
+                        _UniformFeed(batch_size, num_timesteps - 1, previous.device))
+                uniforms = feed.next()
+                # the provider reads the scheme off the uniforms' shape: a feed of the other scheme's shape must not
+                # switch schemes silently
+                per_particle = uniforms.dim() == 2 and tuple(uniforms.shape) == tuple(previous.shape)
+                if per_particle != stratified and num_particles != 1:      # (one particle: the schemes coincide)
+                    raise ValueError("aesmc_amd: {} resampling takes {} uniforms per step, the feed returned {}".format(
+                        "stratified" if stratified else "systematic",
+                        "[batch_size, num_particles]" if stratified else "[batch_size]", tuple(uniforms.shape)))
                 # K2; the same launch re-indexes the newest latent (what a Markov model reads) and
                 # returns the row log-sum-exp when the step before left it pending (K5 route)
                 newest = history[-1] if torch.is_tensor(history[-1]) else None
@@ -399,7 +458,7 @@ def _infer(inference_algorithm, observations, initial, transition, emission,
                 # (with the latents handed to nobody, consecutive linear-Gaussian steps pass the gather's backward from
                 #  node to node — `_ops.StepLink` — and the resampling launch writes the children ranges it needs)
                 fold_gather = lazy_step and pending is not None and fold_children and torch.is_grad_enabled()
-                index, lse_previous, moved = _ops.resample_step(previous, feed.next(), None if lazy_step else newest,
+                index, lse_previous, moved = _ops.resample_step(previous, uniforms, None if lazy_step else newest,
                                                                 want_lse=step_lse[-1] is None, pending=pending,
                                                                 want_child_end=fold_gather)
                 if step_lse[-1] is None:

@@ -11,14 +11,19 @@ everybody.  Here a `Settings` object holds them all; `current()` is what the cod
     THIS context only (contextvars: per thread, per asyncio task) — what `inference.lazy_gather(...)`,
     `inference.fold_gather_backward(...)` and the hipGraph capture use.
 
-The reference has no switches (aesmc/ is one code path); every combination here gives the same numbers — they select
-which of this package's equivalent routes runs (see each field) — except `validation_mode`, which chooses WHEN a
-violation surfaces.  Environment variables give the defaults' initial values (measurement knobs, read once at import).
+The reference has no switches (aesmc/ is one code path); every combination of the ROUTE switches here gives the same
+numbers — they select which of this package's equivalent routes runs (see each field) — except `validation_mode`,
+which chooses WHEN a violation surfaces.  One field is not a route switch: `resampling` names the resampling SCHEME, and
+unlike the others it changes the numbers (other ancestors from other uniforms; the reference knows 'systematic' only).
+Environment variables give the defaults' initial values (measurement knobs, read once at import).
 """
 import contextlib
 import contextvars
 import dataclasses
 import os
+
+
+RESAMPLING_SCHEMES = ("systematic", "stratified")
 
 
 def _env_flag(name, default=True):
@@ -59,7 +64,17 @@ class Settings:
     # stands for (K6, K8, K5); off: those three  [AESMC_INITIAL_STEP]
     initial_step: bool = True
 
+    # the resampling SCHEME of 'smc' inference — NOT a route switch: it changes the numbers.  'systematic' (the
+    # reference's, aesmc/inference.py:234-269): positions (u + k) / K from ONE uniform per batch row, drawn from numpy's
+    # global RandomState.  'stratified': positions (u_k + k) / K from one uniform per PARTICLE, drawn with torch.rand from
+    # the generator of the log-weights' device (numpy's RandomState is not consumed).  Both yield ancestor indices that
+    # are non-decreasing along the particles, so every route above serves both.  `infer(..., resampling=...)` and
+    # `sample_ancestral_index(..., resampling=...)` override it per call.
+    resampling: str = "systematic"
+
     def validate(self):
+        if self.resampling not in RESAMPLING_SCHEMES:
+            raise ValueError("resampling must be one of {}, got {!r}".format(", ".join(RESAMPLING_SCHEMES), self.resampling))
         if self.history_mode not in ("lazy", "eager"):
             raise ValueError("history mode must be 'lazy' or 'eager', got {}".format(self.history_mode))
         if self.validation_mode not in ("deferred", "eager"):

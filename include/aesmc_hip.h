@@ -60,6 +60,8 @@ extern "C" {
  *                three densities' constants and their tag behind the pairs: aesmc_affine_weight_pairs clears the tag);
  *                added aesmc_affine_normal_initial_step (K20: the first timestep's draw, emission location and
  *                log-weight in one launch).
+ *                Additive since, version unchanged: aesmc_resample_step_stratified (K2's stratified sibling: one uniform
+ *                per particle).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -256,6 +258,27 @@ int aesmc_resample_step(int dtype, const void *log_w, const double *u, int64_t *
  * The scan has the value in a register anyway: 4 more bytes per particle written. */
 int aesmc_resample_step_ranges(int dtype, const void *log_w, const double *u, int64_t *out_idx, void *out_lse,
                                int32_t *out_child_end, int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K2's stratified sibling — one independent uniform per particle instead of one per batch row:
+ *   c[j]     as K2's                                             (float64; the same arithmetic, operation for operation)
+ *   pos[k]   = min((u[b,k] + k) / K, 1 - 2^-53)                  (float64: sum, true division, clamp; `u` is [B,K])
+ *   idx[b,k] = #{ j : c[j] <= pos[k] }
+ * Exactly one position per stratum [k/K, (k+1)/K], so the indices are non-decreasing along k like K2's and everything
+ * that consumes them (aesmc_resample_gather_backward's sorted form, aesmc_affine_step_backward_resampled, the fused
+ * propagation launches) takes them unchanged.  The clamp keeps a position that u + (K-1) rounded up to 1.0 inside the
+ * last stratum: a row with a finite maximum never yields the index K.  NaN rows and rows whose maximum is +-inf: K2's
+ * conventions (idx == K, the flag bits, out_lse as aesmc_resample_step's).
+ * By-products as aesmc_resample_step / aesmc_resample_step_ranges define them, each may be NULL:
+ *   out_lse[b]         = logsumexp_k log_w[b,k]                  (dtype of log_w)
+ *   out_child_end[b,k] = #{k' : out_idx[b,k'] <= k}              (int32 [B,K]; monotone on knife-edge rows too)
+ * There is no payload tail: a caller that reads resampled values gathers with aesmc_resample_gather.
+ * K up to aesmc_ancestor_index_lds_max_particles() is resolved inside one workgroup; a larger K goes through `ws`
+ * (aesmc_workspace_bytes(B, K) bytes, else AESMC_ERR_WORKSPACE) and delivers the indices only: asked for a by-product
+ * there the entry returns AESMC_ERR_UNSUPPORTED and launches nothing (the caller composes K1 / the ranges itself).
+ */
+int aesmc_resample_step_stratified(int dtype, const void *log_w, const double *u, int64_t *out_idx, void *out_lse,
+                                   int32_t *out_child_end, int32_t *flags, int64_t B, int64_t K, void *ws,
+                                   size_t ws_bytes, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
