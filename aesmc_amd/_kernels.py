@@ -1904,6 +1904,79 @@ class HipKernels:
                      (log_w, value, view, log_ess, mean, second, ws))
         return log_ess, mean, second
 
+    # ---- K21 -----------------------------------------------------------------------------------
+    BACKWARD_SAMPLE_MAX_DIM = 256
+
+    @staticmethod
+    def backward_sample_covers(log_w, loc, target, scale, u, payload=None):
+        """Whether `backward_sample` takes these operands: float32 / float64 throughout and all on one device, at least one
+        particle, a transition term of at most 256 values per particle whose scale is one value or one per value."""
+        if not (torch.is_tensor(log_w) and log_w.dim() == 2 and log_w.dtype in _DTYPE_TAG and log_w.size(1) > 0):
+            return False
+        if not (torch.is_tensor(u) and u.dim() == 2 and u.dtype == torch.float64 and u.size(0) == log_w.size(0) and
+                u.device == log_w.device):
+            return False
+        if payload is not None and not (torch.is_tensor(payload) and payload.dim() >= 2 and payload.dtype == log_w.dtype and
+                                        payload.device == log_w.device and
+                                        tuple(payload.shape[:2]) == tuple(log_w.shape)):
+            return False
+        if loc is None:
+            return target is None and scale is None
+        if not all(torch.is_tensor(t) and t.dtype == log_w.dtype and t.device == log_w.device
+                   for t in (loc, target, scale)):
+            return False
+        if loc.dim() < 2 or tuple(loc.shape[:2]) != tuple(log_w.shape) or target.dim() != loc.dim() or \
+                tuple(target.shape[:2]) != tuple(u.shape) or tuple(target.shape[2:]) != tuple(loc.shape[2:]):
+            return False
+        D = 1
+        for size in loc.shape[2:]:
+            D *= size
+        return 0 < D <= HipKernels.BACKWARD_SAMPLE_MAX_DIM and scale.dim() <= 1 and scale.numel() in (1, D)
+
+    def backward_sample(self, log_w, loc, target, scale, u, payload=None):
+        """One backward-simulation step (aesmc_backward_sample, K21): log_w [B,K], loc [B,K,*] (the transition's location
+        per stored particle), target [B,M,*] (the trajectories' next states), scale one value or one per location value, u
+        float64 [B,M]; loc = target = scale = None: no transition term (the last timestep).  Returns (idx int64 [B,M],
+        payload[b, idx[b,m]] as [B,M,*] or None).  Views are taken as they are (element strides)."""
+        tag = self._rows_operand(log_w, "log_weight")
+        _require_hip(u, "uniforms")
+        B, K = log_w.shape
+        if u.dim() != 2 or u.size(0) != B or u.dtype != torch.float64 or u.device != log_w.device:
+            raise ValueError("aesmc_amd: uniforms must be [{}, num_trajectories] float64 on {}".format(B, log_w.device))
+        if not self.backward_sample_covers(log_w, loc, target, scale, u, payload):
+            raise ValueError("aesmc_amd: backward_sample does not take these operands (see backward_sample_covers)")
+        M = u.size(1)
+        log_w, u = log_w.contiguous(), u.contiguous()
+        views, keep, D, scale_stride = [None, None, None], [], 0, 0
+        if loc is not None:
+            for t in (loc, target, scale):
+                _require_hip(t, "transition term")
+            (loc, sl, D), (target, st, _) = self._view3(loc), self._view3(target)
+            scale = scale.reshape(-1).contiguous()
+            scale_stride = 0 if scale.numel() == 1 else 1
+            views[0], views[1] = _lib.View3(_ptr(loc), *sl), _lib.View3(_ptr(target), *st)
+            keep += [loc, target, scale]
+        P, moved = 0, None
+        if payload is not None:
+            _require_hip(payload, "payload")
+            tail = tuple(payload.shape[2:])
+            payload, sp, P = self._view3(payload)
+            moved = torch.empty((B, M) + tail, dtype=payload.dtype, device=payload.device)
+            if P > 0:
+                views[2] = _lib.View3(_ptr(payload), *sp)
+            keep.append(payload)
+        idx = torch.empty((B, M), dtype=torch.int64, device=log_w.device)
+        if idx.numel() == 0:
+            return idx, moved
+        esz = log_w.element_size()
+        refs = [ctypes.byref(v) if v is not None else None for v in views]
+        self._launch(log_w.device, self._lib.aesmc_backward_sample,
+                     (tag, _ptr(log_w), refs[0], refs[1], _ptr(scale) if D else 0, scale_stride, _ptr(u), _ptr(idx), refs[2],
+                      _ptr(moved) if P else 0, _ptr(self.flags(log_w.device)), B, K, M, D, P, self._stream(log_w)),
+                     lambda: B * K * esz * (1 + D) + B * M * (16 + esz * (D + 2 * P)),
+                     tuple(keep) + (log_w, u, idx, moved) + tuple(views))
+        return idx, moved
+
 
 _provider = None
 _provider_lock = threading.Lock()

@@ -10,7 +10,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libaesmc_hip.so")
-SOURCES = ["abi.hip", "logweight_lse.hip", "ancestor_index.hip", "ancestor_index_stratified.hip", "resample_gather.hip",
+SOURCES = ["abi.hip", "logweight_lse.hip", "ancestor_index.hip", "ancestor_index_stratified.hip", "backward_sample.hip",
+           "resample_gather.hip",
            "normal_logprob.hip", "normal_rsample.hip", "particle_summary.hip", "linear_gaussian.hip",
            "linear_gaussian_backward.hip", "philox_normal.hip", "linear_gaussian_noise.hip",
            "linear_gaussian_fused.hip", "linear_gaussian_item.hip", "linear_gaussian_step_backward.hip", "linear_gaussian_wide.hip", "linear_gaussian_wide_backward.hip",

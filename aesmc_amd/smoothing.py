@@ -1,0 +1,163 @@
+"""Forward filtering / backward simulation (FFBS; Godsill, Doucet & West 2004): equally weighted draws from the JOINT
+smoothing distribution p(x_0..x_{T-1} | y_0..y_{T-1}), from the particles an SMC run has already stored.
+
+The smoothed posterior `infer(..., return_latents=True)` gives is the genealogy (`inference.get_resampled_latents`): every
+final particle traced back through the ancestor indices.  Over a long sequence the genealogy collapses — after a hundred
+resampling steps a thousand final particles descend from a dozen or two particles at time 0.  Backward simulation instead
+re-draws, going backwards in time, which stored particle of step t each trajectory passes through, in proportion to
+
+    exp(log_weights[t][b,k]) * transition(x_{t+1} | latents[t][b,k])
+
+so every stored particle of every step can be reached.  The draw is kernel K21 (`aesmc_backward_sample`: a pairwise
+trajectory x particle score with one categorical draw per trajectory, O(B M K D) per step, nothing of size [M,K] stored).
+
+The reference has no counterpart; this module adds to its interface and changes none of it.
+"""
+import torch
+
+from . import _kernels
+from . import _lazy
+from . import _syncfree
+from . import inference
+from . import state
+from .linear_gaussian import AffineNormal
+
+MAX_LATENT_DIM = 256
+_COVERED = ("covered: a transition that returns an AffineNormal or a torch.distributions.Normal in FULLY_EXPANDED "
+            "batch-shape mode, its location shaped like the latent [batch_size, num_particles, ...] with at most {} "
+            "values per particle, its scale one value or one per latent dimension (not varying over batch or "
+            "particle, by shape or zero strides); tensor latents".format(MAX_LATENT_DIM))
+
+
+def _refuse(what):
+    raise NotImplementedError("aesmc_amd.smoothing: {} is not implemented; {}".format(what, _COVERED))
+
+
+def _transition_terms(distribution, latent):
+    """(loc [B,K,...], scale of 1 or D values) of a covered transition distribution over `latent`'s particles."""
+    if isinstance(distribution, dict):
+        _refuse("a dict of transition distributions")
+    if type(distribution) not in (AffineNormal, torch.distributions.Normal):
+        _refuse("a transition distribution of type {}".format(type(distribution).__name__))
+    loc, scale = distribution.loc, distribution.scale      # (an AffineNormal's location: kernel K8, once)
+    batch_size, num_particles = latent.shape[:2]
+    if state.get_batch_shape_mode(distribution, batch_size, num_particles) != state.BatchShapeMode.FULLY_EXPANDED:
+        _refuse("a transition that is not in FULLY_EXPANDED batch-shape mode")
+    loc = _lazy.real(loc).detach()
+    if tuple(loc.shape) != tuple(latent.shape) or loc.dtype != latent.dtype:
+        _refuse("a transition location of shape {} {} for latents of shape {} {}".format(
+            tuple(loc.shape), loc.dtype, tuple(latent.shape), latent.dtype))
+    dim = 1
+    for size in latent.shape[2:]:
+        dim *= size
+    if dim > MAX_LATENT_DIM:
+        _refuse("a latent of {} values per particle (D > {})".format(dim, MAX_LATENT_DIM))
+    scale = _lazy.real(scale).detach()
+    if tuple(scale.shape) != tuple(latent.shape):
+        try:
+            scale = scale.expand(latent.shape)
+        except RuntimeError:
+            _refuse("a scale of shape {} for latents of shape {}".format(tuple(scale.shape), tuple(latent.shape)))
+    if any(size != 1 and stride != 0 for size, stride in zip(scale.shape[:2], scale.stride()[:2])):
+        _refuse("a scale that varies over batch or particle (a particle-dependent scale)")
+    per_dim = scale[0, 0]
+    if all(size == 1 or stride == 0 for size, stride in zip(per_dim.shape, per_dim.stride())):
+        values = per_dim.reshape(-1)[:1]      # one value for the whole latent
+    else:
+        values = per_dim.reshape(-1)
+    return loc, values.to(latent.dtype)
+
+
+def backward_simulate(latents, log_weights, transition, num_trajectories=None, observations=None, uniforms=None,
+                      return_indices=False):
+    """Backward simulation over the particles of one SMC run.
+
+    latents, log_weights: what `infer("smc", ..., return_original_latents=True, return_log_weights=True)` returned as
+        `original_latents` and `log_weights` — T tensors [batch_size, num_particles, ...] (the particles as drawn, before
+        resampling) and T tensors [batch_size, num_particles].
+    transition: the model's transition callable.  For t = T-2 ... 0 it is called ONCE on the stored particles, as
+        `transition(previous_latents=latents[:t+1], time=t+1, previous_observations=observations[:t+1])` with plain
+        tensors.  MARKOV MODELS ONLY: `previous_latents[-1]` must be all of the latents the transition reads — the
+        earlier entries handed over are the filter's stored particles, not the trajectories' own pasts.
+    num_trajectories: M, trajectories per batch element (default: num_particles).
+    observations: handed to the transition (None: it gets `previous_observations=None`).
+    uniforms: None — one `torch.rand((batch_size, M), dtype=torch.float64)` block per timestep on the particles' device,
+        from torch's generator for that device, drawn for t = T-1 first and t = 0 last (seed with torch.manual_seed;
+        numpy's RandomState is not consumed); or a length-T sequence of such blocks, `uniforms[t]` for the draw at time t
+        (replay).  Inside `distributed.shard_scope`, None raises NotImplementedError (as stratified resampling does: the
+        device draws have no global block that every rank could cut its rows from).
+    return_indices: also return which stored particle each trajectory passes through, T int64 tensors [batch_size, M].
+
+    Returns T tensors [batch_size, M, ...]: trajectory m of batch element b is (out[0][b,m], ..., out[T-1][b,m]), an
+    equally weighted draw from the joint smoothing distribution; detached.  With `return_indices`: (trajectories, indices).
+
+    Covered: a transition that returns an `AffineNormal` or a `torch.distributions.Normal` in FULLY_EXPANDED batch-shape
+    mode, its location shaped like the latent with at most 256 values per particle (trailing dims are flattened; a
+    [batch_size, num_particles] latent has one), its scale one value or one per latent dimension, not varying over batch
+    or particle (by shape or zero strides).  Everything else — dict latents, other distributions, a particle-dependent
+    scale, more than 256 values — raises NotImplementedError.  NaN log-weights or locations raise FloatingPointError, a
+    row without a finite maximum RuntimeError — read once, at the end (one synchronisation per call).  Not capturable
+    into a hipGraph."""
+    num_timesteps = len(latents)
+    if num_timesteps == 0 or len(log_weights) != num_timesteps:
+        raise ValueError("backward_simulate: latents and log_weights must be equally long and not empty, got {} and {}"
+                         .format(num_timesteps, len(log_weights)))
+    if any(isinstance(latent, dict) for latent in latents):
+        _refuse("dict latents")
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            latents = [_lazy.real(latent).detach() for latent in latents]
+            log_weights = [_lazy.real(log_weight).detach() for log_weight in log_weights]
+            batch_size, num_particles = log_weights[-1].shape
+            device = log_weights[-1].device
+            num_trajectories = num_particles if num_trajectories is None else int(num_trajectories)
+            if num_trajectories < 0:
+                raise ValueError("backward_simulate: num_trajectories must not be negative")
+            if uniforms is None:
+                from . import distributed
+                if distributed.active_shard() is not None:
+                    raise NotImplementedError(
+                        "aesmc_amd: backward_simulate inside distributed.shard_scope draws its uniforms on the device, "
+                        "where no global block exists that every rank could cut its rows from. Pass uniforms= (one "
+                        "[batch_size, num_trajectories] float64 block per timestep).")
+            elif len(uniforms) != num_timesteps:
+                raise ValueError("backward_simulate: uniforms must hold one block per timestep ({}), got {}".format(
+                    num_timesteps, len(uniforms)))
+
+            def block(time):
+                if uniforms is None:
+                    return torch.rand((batch_size, num_trajectories), dtype=torch.float64, device=device)
+                u = uniforms[time]
+                if tuple(u.shape) != (batch_size, num_trajectories) or u.dtype != torch.float64:
+                    raise ValueError("backward_simulate: uniforms[{}] must be [{}, {}] float64, got {} {}".format(
+                        time, batch_size, num_trajectories, tuple(u.shape), u.dtype))
+                return u
+
+            trajectories, indices = [None] * num_timesteps, [None] * num_timesteps
+            indices[-1], trajectories[-1] = provider.backward_sample(log_weights[-1], None, None, None,
+                                                                     block(num_timesteps - 1), payload=latents[-1])
+            for time in range(num_timesteps - 2, -1, -1):
+                distribution = transition(
+                    previous_latents=latents[:time + 1], time=time + 1,
+                    previous_observations=None if observations is None else observations[:time + 1])
+                loc, scale = _transition_terms(distribution, latents[time])
+                indices[time], trajectories[time] = provider.backward_sample(
+                    log_weights[time], loc, trajectories[time + 1], scale, block(time), payload=latents[time])
+            inference._raise_for_flags(provider.read_flags(device))
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return (trajectories, indices) if return_indices else trajectories
+
+
+def smooth(observations, initial, transition, emission, proposal, num_particles, num_trajectories=None, resampling=None):
+    """Runs the SMC filter (`inference.infer("smc", ...)`, keeping the particles as drawn and every step's log-weights)
+    and then `backward_simulate` over what it stored.  Returns (trajectories, log_marginal_likelihood): T tensors
+    [batch_size, num_trajectories, ...] (default: num_particles trajectories) and the filter's [batch_size] estimate."""
+    out = inference.infer("smc", observations, initial, transition, emission, proposal, num_particles,
+                          return_log_marginal_likelihood=True, return_latents=False, return_original_latents=True,
+                          return_log_weight=False, return_log_weights=True, resampling=resampling)
+    trajectories = backward_simulate(out["original_latents"], out["log_weights"], transition,
+                                     num_trajectories=num_trajectories, observations=observations)
+    return trajectories, out["log_marginal_likelihood"]

@@ -3,7 +3,7 @@ d-dimensional linear-Gaussian state-space model with the AESMC objective on the 
 summarise the filtering posterior.
 
     python examples/lgssm_train.py [--dim 10] [--particles 1024] [--batch 256] [--steps 200] [--graph]
-                                   [--callables affine|matmul]
+                                   [--callables affine|matmul] [--smoother genealogy|ffbs]
 
 `--graph` runs the optimisation loop on one captured hipGraph (aesmc_amd.train(..., hip_graph=True)).
 """
@@ -31,6 +31,10 @@ def main():
     ap.add_argument("--callables", default="affine", choices=["affine", "matmul"],
                     help="affine: the model's callables return aesmc_amd.linear_gaussian.AffineNormal (locations "
                          "evaluated inside the sampling / weighting kernels); matmul: Normal(x @ W.T + c, s)")
+    ap.add_argument("--smoother", default="genealogy", choices=["genealogy", "ffbs"],
+                    help="genealogy (default): the summaries as they are, from infer's own latents; ffbs: adds the "
+                         "smoothed posterior at time 0 from backward simulation (aesmc_amd.smoothing.backward_simulate) "
+                         "over the particles the same run stored, beside the genealogy's")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-tunableop", action="store_true",
                     help="keep PyTorch's default GEMM picks for the model's matmuls (slower on MI355X: see DESIGN.md 6)")
@@ -69,7 +73,9 @@ def main():
     observations = truth.simulate(args.timesteps, args.batch, seed=7)
     with torch.no_grad():
         out = aesmc.inference.infer("smc", observations, model.initial, model.transition, model.emission,
-                                    model.proposal, args.particles, return_log_marginal_likelihood=True)
+                                    model.proposal, args.particles, return_log_marginal_likelihood=True,
+                                    return_original_latents=args.smoother == "ffbs",
+                                    return_log_weights=args.smoother == "ffbs")
     last = out["latents"][-1]
     mean = aesmc.statistics.empirical_mean(last, out["log_weight"])
     variance = aesmc.statistics.empirical_variance(last, out["log_weight"])
@@ -77,6 +83,21 @@ def main():
     print("log Z per sequence {:.3f}; last-step ESS {:.1f} of {}; |mean| {:.3f}, mean variance {:.3f}".format(
         out["log_marginal_likelihood"].mean().item(), ess.mean().item(), args.particles,
         mean.abs().mean().item(), variance.mean().item()))
+    if args.smoother == "ffbs":
+        # the smoothed posterior of x_0 given ALL the observations, where a genealogy has collapsed the most: the
+        # genealogy's own summary beside that of the backward-simulated trajectories
+        def summary(name, first, smoothed_mean, smoothed_variance):
+            distinct = np.mean([len(torch.unique(row[:, 0])) for row in first])
+            print("smoothed x_0 ({}): |mean| {:.3f}, mean variance {:.3f}, {:.0f} distinct particles of {} per sequence"
+                  .format(name, smoothed_mean.abs().mean().item(), smoothed_variance.mean().item(), distinct,
+                          first.size(1)))
+
+        first = out["latents"][0]
+        summary("genealogy", first, aesmc.statistics.empirical_mean(first, out["log_weight"]),
+                aesmc.statistics.empirical_variance(first, out["log_weight"]))
+        first = aesmc.smoothing.backward_simulate(out["original_latents"], out["log_weights"], model.transition,
+                                                  observations=observations)[0]
+        summary("ffbs", first, first.mean(dim=1), first.var(dim=1, unbiased=False))
 
 
 if __name__ == "__main__":

@@ -61,7 +61,7 @@ extern "C" {
  *                added aesmc_affine_normal_initial_step (K20: the first timestep's draw, emission location and
  *                log-weight in one launch).
  *                Additive since, version unchanged: aesmc_resample_step_stratified (K2's stratified sibling: one uniform
- *                per particle).
+ *                per particle); aesmc_backward_sample (K21: one step of backward simulation, FFBS).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -279,6 +279,42 @@ int aesmc_resample_step_ranges(int dtype, const void *log_w, const double *u, in
 int aesmc_resample_step_stratified(int dtype, const void *log_w, const double *u, int64_t *out_idx, void *out_lse,
                                    int32_t *out_child_end, int32_t *flags, int64_t B, int64_t K, void *ws,
                                    size_t ws_bytes, void *stream);
+
+/* K21 — one backward step of forward filtering / backward simulation (FFBS; Godsill, Doucet & West 2004): M
+ * trajectories per batch row each draw one of the filter's K stored particles of step t, in proportion to its weight
+ * times the transition density from it to the trajectory's state at t+1.  The reference has no such call site: its one
+ * smoothed posterior is the genealogy (aesmc/inference.py:196-231), which collapses over long sequences.
+ *   log_w   T [B,K] dense                 the filter's step-t log-weights
+ *   loc     T [B,K,D] view                the transition's location for every stored particle
+ *   target  T [B,M,D] view                the trajectories' states at t+1 (`stride_k` steps along m)
+ *   scale   T, D values                   read with the element stride `scale_stride`: 0 (one value) or 1
+ *   u       float64 [B,M] dense           in [0, 1)
+ * T is float32 or float64 (`dtype`); D == 0 (loc / target / scale may be NULL) means no transition term: the draw at the
+ * last timestep.  All arithmetic is in float64 whatever T is:
+ *   inv[d]   = 1 / (double)scale[d]
+ *   q[m,k]   = sum_d ((double)target[b,m,d] - (double)loc[b,k,d])^2 * inv[d]^2   (as ((t - l) * inv)^2, d ascending)
+ *   s[m,k]   = (double)log_w[b,k] - 0.5 * q[m,k]
+ *   smax[m]  = max_k s[m,k]
+ *   w[m,k]   = exp(s[m,k] - smax[m])                                            (K2's float64 exp of a non-positive number)
+ *   C[m,k]   = w[m,0] + ... + w[m,k]
+ *   idx[b,m] = min( #{k : C[m,k] <= u[b,m] * C[m,K-1]},  max{k : w[m,k] > 0} )
+ * The Normal's normalising constant is the same for every k (the scale does not depend on the particle) and is dropped.
+ * The order of the two sums (over d, over k) and the contraction of multiply-adds are the kernel's: a difference in the
+ * last place decides an index only on a knife edge of measure zero (K2's stance).  The `min` is the clamp: u * C[K-1] can
+ * round to C[K-1] itself, the count is then K and the last particle of positive weight is the answer; the drawn particle
+ * always has positive weight.
+ * Bad rows, per (b, m), by K2's conventions: any NaN among s[m,:] raises AESMC_FLAG_NAN_LOG_WEIGHT and idx = K; an smax
+ * that is not finite (all -inf, or a +inf) raises AESMC_FLAG_DEGENERATE_ROW and idx = K.
+ * Optional tail (P > 0): out_payload[b,m,:] = payload[b, idx[b,m], :] with `payload` a T [B,K,P] view and out_payload
+ * dense [B,M,P] (K3 cannot serve: its index tensor has the payload's own particle count); idx == K copies particle K-1,
+ * clamped as in K3, and nothing is ever read out of bounds.
+ * No workspace, K not bounded by LDS.  D above 256 returns AESMC_ERR_UNSUPPORTED and launches nothing; B M == 0 is a
+ * no-op; K == 0 with trajectories to draw is AESMC_ERR_INVALID_ARGUMENT.
+ */
+int aesmc_backward_sample(int dtype, const void *log_w, const aesmc_view3 *loc, const aesmc_view3 *target,
+                          const void *scale, int64_t scale_stride, const double *u, int64_t *out_idx,
+                          const aesmc_view3 *payload, void *out_payload, int32_t *flags, int64_t B, int64_t K, int64_t M,
+                          int64_t D, int64_t P, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
