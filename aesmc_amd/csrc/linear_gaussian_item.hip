@@ -22,6 +22,20 @@
 
 namespace aesmc {
 
+// The three quotients (-q) / (2 s^2) of a particle's log-weight through reciprocals formed once per workgroup.  With
+// r = RN(1 / d): q0 = n r, e = fma(-d, q0, n) (exact), q = fma(e, r, q0) is the correctly rounded n / d — the bits of the
+// division — while numerator, quotient and residual stay clear of the subnormal range (tests/test_division_by_reciprocal.py
+// restates the arithmetic).  The guard that keeps them there: numerators in [2^-60, 2^60] (as bit patterns: a NaN, an
+// infinity, a zero and anything negative fall outside), divisors in [2^-19, 2^19].
+[[maybe_unused]] constexpr uint32_t kRecipNumLo = 0x21800000u, kRecipNumHi = 0x5d800000u;      // 2^-60, 2^60
+[[maybe_unused]] constexpr uint32_t kRecipDivLo = 0x36000000u, kRecipDivHi = 0x49000000u;      // 2^-19, 2^19
+constexpr uint32_t kRecipF = 4;                                               // floats of LDS behind the noise tile
+__device__ __forceinline__ float item_quotient(float n, float d, float r) {
+  const float q0 = n * r;
+  const float e = fma_t(-d, q0, n);
+  return fma_t(e, r, q0);
+}
+
 // DXC: the latent's extent (compile time).  DYC: the observation's, or 0 = run time (<= 16).  PAIRED: the maps' `w` point
 // at their interleaved copies (aesmc_affine_weight_pairs) and the chains of two outputs advance together, one
 // v_pk_fma_f32 per input (linear_gaussian_fused.hpp: the same bits as the v_fmac_f32 chains).
@@ -40,6 +54,7 @@ __global__ __launch_bounds__(512, 4) void affine_propagate_item_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char item_smem[];
   float *tab = reinterpret_cast<float *>(item_smem);            // [kTabF]: [window][batch row 0 / 1][p, q, g, y][16]
   float *noise = tab + kTabF;                                   // [4][kRunP * dx + 4]: window i's run at i * kRunStride, rows end to end
+  float *recip = noise + 4u * kRunStride;                       // [kRecipF]: 1 / (2 s^2) of p, g, q (PAIRED with constants at hand)
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
   const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -71,28 +86,31 @@ __global__ __launch_bounds__(512, 4) void affine_propagate_item_kernel(
   }
 
   // ---- this wavefront's block of the table: window wi, batch row c; lane = (vector, element) ----------------------
-  float held = 0.0f;
+  // Everything but the lane's place in the block is wavefront-uniform: the four rows' addresses `ptr + b sb` are scalar
+  // arithmetic and each row is fetched through a buffer descriptor of its own whose extent is the row's length (0 for a
+  // vector the launch does not have, a batch row beyond Bn, an empty window).  All 64 lanes issue the four loads with
+  // the byte offset 4 (lane - 16 a): the sixteen lanes of vector a fall inside its row where it has the element, every
+  // other lane (a negative offset wraps around to a huge one) outside — the hardware returns zero for those without
+  // touching memory, so nothing is read that is not there and at most one of a lane's four words is not zero.  No
+  // branch (the compiler would wait for every load in flight where one ends), no select, no 64-bit vector product.
+  // (0x00020000: the descriptor's last word for raw 32-bit data on gfx9.)
+  float held;
   {
     const LgRowVec<float> vec[4] = {lg_offset_vec<float>(mp), lg_offset_vec<float>(mq), lg_offset_vec<float>(mg),
                                     {y, y_sb, (int)dy}};
-    const uint32_t tab_a = lane >> 4, tab_j = lane & 15u;
-    const float *tab_src = vec[0].ptr;
-    int64_t tab_sb = vec[0].sb;
-    int tab_len = vec[0].ptr != nullptr ? vec[0].len : 0;
-#pragma unroll
-    for (int a = 1; a < 4; ++a) {
-      const bool mine = tab_a == (uint32_t)a;
-      tab_src = mine ? vec[a].ptr : tab_src;
-      tab_sb = mine ? vec[a].sb : tab_sb;
-      tab_len = mine ? (vec[a].ptr != nullptr ? vec[a].len : 0) : tab_len;
-    }
-    // (no branch around the load — the compiler would wait for every load in flight where the branch ends —: an entry
-    //  the table does not have reads a word that is always there, and is then replaced by zero)
     const uint32_t b = cur.b0 + c;
-    const bool present = cur.count != 0 && b < Bn && (int)tab_j < tab_len;
-    const float *at = present ? tab_src + ((int64_t)b * tab_sb + tab_j) : y;
-    const float value = *at;
-    held = present ? value : 0.0f;
+    const bool row = cur.count != 0 && b < Bn;
+    const int lane4 = (int)(lane << 2);
+    uint32_t word[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      // (a length is 1 .. 16; a lane of the vector never asks past element 15, so a longer extent would read nothing more)
+      const int bytes = (row && vec[a].ptr != nullptr) ? 4 * (vec[a].len & 31) : 0;
+      const unsigned long long at = (unsigned long long)vec[a].ptr + (unsigned long long)((int64_t)b * vec[a].sb) * sizeof(float);
+      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)at, (short)0, bytes, 0x00020000);
+      word[a] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, lane4 - 64 * a, 0, 0);
+    }
+    held = __uint_as_float((word[0] | word[1]) | (word[2] | word[3]));
   }
 
   // (PAIRED: the densities' constants behind the pairs — eight scalar registers sent for here, read behind the barrier)
@@ -187,6 +205,18 @@ __global__ __launch_bounds__(512, 4) void affine_propagate_item_kernel(
     }
   }
   tab[64u * w + lane] = held;
+  // (PAIRED, constants at hand: the last wavefront — never one with a third Philox call — divides once for the workgroup,
+  //  the three divisors on three lanes of one division)
+  bool at_hand = false, by_reciprocal = false;
+  if constexpr (PAIRED) {
+    at_hand = __float_as_uint(consts[6]) == fused_consts_tag(dx, dy);
+    const auto inside = [](float d) { return __float_as_uint(d) - kRecipDivLo <= kRecipDivHi - kRecipDivLo; };
+    by_reciprocal = at_hand && inside(consts[0]) && inside(consts[2]) && inside(consts[4]);
+    if (by_reciprocal && w == 7u) {
+      const float d = lane == 0u ? consts[0] : (lane == 1u ? consts[2] : consts[4]);
+      recip[min(lane, kRecipF - 1u)] = 1.0f / d;
+    }
+  }
   lg_lds_barrier();
 
   // ---- propagate: lane = particle; the maps' weights in scalar registers --------------------------------------------
@@ -198,9 +228,7 @@ __global__ __launch_bounds__(512, 4) void affine_propagate_item_kernel(
   // the densities' constants: behind the pairs when the launch that interleaved them had the scales (scalar loads; the tag
   // names the extents they were formed for), else from the scales here — the same expressions, the same bits
   float two_var_p, const_p, two_var_g, const_g, two_var_q, const_q;
-  bool at_hand = false;
   if constexpr (PAIRED) {
-    at_hand = __float_as_uint(consts[6]) == fused_consts_tag(dx, dy);
     if (at_hand) {
       two_var_p = consts[0]; const_p = consts[1];
       two_var_g = consts[2]; const_g = consts[3];
@@ -284,11 +312,22 @@ __global__ __launch_bounds__(512, 4) void affine_propagate_item_kernel(
       }
     }
   }
-  if (live) {
-    const float lp = (-qp) / two_var_p - const_p;
-    const float lg = (-qg) / two_var_g - const_g;
-    const float lq = (-qq) / two_var_q - const_q;
-    out_lw[cur.nf + rl] = (lp + lg) - lq;
+  {
+    // the sums of squares are >= +0 or NaN: as bit patterns their order is the numbers', and a NaN lies above every bound
+    const uint32_t up = __float_as_uint(qp), ug = __float_as_uint(qg), uq = __float_as_uint(qq);
+    const bool outside = live && !(min(min(up, ug), uq) >= kRecipNumLo && max(max(up, ug), uq) <= kRecipNumHi);
+    float lp, lg, lq;
+    if (by_reciprocal && __builtin_amdgcn_ballot_w64(outside) == 0ull) {      // (uniform)
+      const fz4 r = *reinterpret_cast<const fz4 *>(recip);
+      lp = item_quotient(-qp, two_var_p, r[0]) - const_p;
+      lg = item_quotient(-qg, two_var_g, r[1]) - const_g;
+      lq = item_quotient(-qq, two_var_q, r[2]) - const_q;
+    } else {
+      lp = (-qp) / two_var_p - const_p;
+      lg = (-qg) / two_var_g - const_g;
+      lq = (-qq) / two_var_q - const_q;
+    }
+    if (live) out_lw[cur.nf + rl] = (lp + lg) - lq;
   }
   // ---- the chunk's rows of x_t leave as one contiguous run, staged where the chunk's noise was (every lane of this
   //      wavefront has read its noise: a wavefront's LDS accesses execute in order) ------------------------------------
@@ -400,7 +439,8 @@ int launch_affine_propagate_item(const void *xsrc, const int64_t *anc_idx, const
   FusedPlan plan;
   const int planned = fused_make_plan(plan, B, K, dx, threads);
   if (planned != AESMC_OK) return planned;
-  const size_t lds = sizeof(float) * ((size_t)kTabF + 4 * ((size_t)kRunP * (size_t)dx + 4));      // (four windows' areas)
+  // (four windows' areas and the reciprocals' words: 33.9 KB at dx = 16, so item_launch's opt-in above 64 KB stays unused)
+  const size_t lds = sizeof(float) * ((size_t)kTabF + 4 * ((size_t)kRunP * (size_t)dx + 4) + kRecipF);
   if (lds > kLgLdsLimit) return AESMC_ERR_UNSUPPORTED;
   const PhiloxStream ps = philox_stream(seed, offset, threads, rng_state);
   const dim3 grid(plan.items);
