@@ -1977,6 +1977,70 @@ class HipKernels:
                      tuple(keep) + (log_w, u, idx, moved) + tuple(views))
         return idx, moved
 
+    # ---- K22 -----------------------------------------------------------------------------------
+    PAIRWISE_LSE_MAX_DIM = 256
+
+    @staticmethod
+    def pairwise_lse_covers(rows, cols, scale, col_a, col_sub=None, row_add=None):
+        """Whether `pairwise_lse` takes these operands: float32 / float64 throughout and all on one device, rows [B,R,*]
+        and cols [B,C,*] with the same trailing dims of at most 256 values (none: no distance term, scale may be None), at
+        least one column, a scale of one value or one per value, col_a / col_sub [B,C] and row_add [B,R]."""
+        if not (torch.is_tensor(col_a) and col_a.dim() == 2 and col_a.dtype in _DTYPE_TAG and col_a.size(1) > 0):
+            return False
+        same = lambda t: torch.is_tensor(t) and t.dtype == col_a.dtype and t.device == col_a.device
+        if not (same(rows) and same(cols) and rows.dim() >= 2 and cols.dim() == rows.dim() and
+                rows.size(0) == col_a.size(0) and tuple(cols.shape[:2]) == tuple(col_a.shape) and
+                tuple(cols.shape[2:]) == tuple(rows.shape[2:])):
+            return False
+        if col_sub is not None and not (same(col_sub) and tuple(col_sub.shape) == tuple(col_a.shape)):
+            return False
+        if row_add is not None and not (same(row_add) and tuple(row_add.shape) == tuple(rows.shape[:2])):
+            return False
+        D = 1
+        for size in rows.shape[2:]:
+            D *= size
+        if D == 0:
+            return scale is None or same(scale)
+        return D <= HipKernels.PAIRWISE_LSE_MAX_DIM and same(scale) and scale.dim() <= 1 and scale.numel() in (1, D)
+
+    def pairwise_lse(self, rows, cols, scale, col_a, col_sub=None, row_add=None):
+        """The pairwise Gaussian log-sum-exp (aesmc_pairwise_lse, K22):
+            out[b,r] = row_add[b,r] + log sum_c exp(col_a[b,c] - col_sub[b,c] - 1/2 sum_d ((rows[b,r,d] - cols[b,c,d]) / scale[d])^2)
+        rows [B,R,*], cols [B,C,*] (trailing dims flattened; a [B,R] tensor has one value per point, a [B,R,0] one none:
+        no distance term), scale one value or one per value, col_a / col_sub [B,C], row_add [B,R]; col_sub / row_add None:
+        0.  Returns [B,R] in col_a's dtype.  Views are taken as they are (element strides)."""
+        tag = self._rows_operand(col_a, "col_a")
+        if not self.pairwise_lse_covers(rows, cols, scale, col_a, col_sub, row_add):
+            raise ValueError("aesmc_amd: pairwise_lse does not take these operands (see pairwise_lse_covers)")
+        B, C = col_a.shape
+        R = rows.size(1)
+        for t in (rows, cols, col_sub, row_add):
+            if t is not None:
+                _require_hip(t, "pairwise operand")
+        col_a = col_a.contiguous()
+        col_sub = None if col_sub is None else col_sub.contiguous()
+        row_add = None if row_add is None else row_add.contiguous()
+        out = torch.empty((B, R), dtype=col_a.dtype, device=col_a.device)
+        if out.numel() == 0:
+            return out
+        views, keep, D, scale_stride = [None, None], [rows, cols], 0, 0
+        if all(size > 0 for size in rows.shape[2:]):
+            (rows, sr, D), (cols, sc, _) = self._view3(rows), self._view3(cols)
+            _require_hip(scale, "scale")
+            scale = scale.reshape(-1).contiguous()
+            scale_stride = 0 if scale.numel() == 1 else 1
+            views = [_lib.View3(_ptr(rows), *sr), _lib.View3(_ptr(cols), *sc)]
+            keep = [rows, cols, scale]
+        esz = col_a.element_size()
+        refs = [ctypes.byref(v) if v is not None else None for v in views]
+        self._launch(col_a.device, self._lib.aesmc_pairwise_lse,
+                     (tag, refs[0], refs[1], _ptr(scale) if D else 0, scale_stride, _ptr(col_a), _ptr(col_sub),
+                      _ptr(row_add), _ptr(out), _ptr(self.flags(col_a.device)), B, R, C, D, self._stream(col_a)),
+                     lambda: B * esz * ((R + C) * D + C * (2 if col_sub is not None else 1) +
+                                        R * (2 if row_add is not None else 1)),
+                     tuple(keep) + (col_a, col_sub, row_add, out) + tuple(views))
+        return out
+
 
 _provider = None
 _provider_lock = threading.Lock()

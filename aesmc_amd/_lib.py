@@ -98,6 +98,8 @@ SIGNATURES = {
     "aesmc_resample_step_stratified": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp]),
     "aesmc_backward_sample": (_i32, [_i32, _vp, ctypes.POINTER(View3), ctypes.POINTER(View3), _vp, _i64, _vp, _vp,
                                      ctypes.POINTER(View3), _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "aesmc_pairwise_lse": (_i32, [_i32, ctypes.POINTER(View3), ctypes.POINTER(View3), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                  _i64, _i64, _i64, _i64, _vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,
@@ -142,6 +144,7 @@ TEST_HOOKS = {
     "aesmc_test_last_k2_form": (_i32, []),
     "aesmc_test_last_logweight_backward_form": (_i32, []),
     "aesmc_test_last_affine_backward_particles_per_lane": (_i32, []),
+    "aesmc_test_set_pairwise_lse_form": (_i32, [_i32, _i32, _i32]),
 }
 
 _lib = None

@@ -1,6 +1,8 @@
 """NumPy statement of the CONTRACT of the backward-simulation kernel (include/aesmc_hip.h, aesmc_backward_sample),
 written without regard to the kernel's structure (no tiles, no chunks, no passes) — what the tests hold the HIP result to,
-exactly — and of the whole backward pass that `aesmc_amd.smoothing.backward_simulate` makes of it.
+exactly — and of the whole backward pass that `aesmc_amd.smoothing.backward_simulate` makes of it.  Below it the same
+for the marginal smoother: the pairwise log-sum-exp (aesmc_pairwise_lse), the bound its kernel is held to, and the
+backward recursion that `aesmc_amd.smoothing.marginal_log_weights` makes of it.
 
 One backward step of forward filtering / backward simulation (Godsill, Doucet & West 2004): trajectory m, whose state at
 t+1 is target[b,m], draws particle k of step t with probability proportional to
@@ -93,3 +95,131 @@ def backward_pass(latents, log_weights, locations, scale, uniforms):
         indices[t], _, states[t] = backward_sample(log_weights[t], locations(t), states[t + 1], scale, uniforms[t],
                                                    latents[t])
     return states, indices
+
+
+# ---- the marginal smoother (FFBSm; Huerzeler & Kuensch 1998, Doucet, Godsill & Andrieu 2000) --------------------------------
+EPSILON = 2.0 ** -52
+NEAR_THE_MAXIMUM = 40.0      # columns further below a row point's maximum carry less than C e^-40 of its sum
+
+
+def _pairwise_operands(rows, cols, scale, col_a, col_sub, row_add):
+    """float64 (rows [B,R,D], cols [B,C,D], inv [D], col_a [B,C], col_sub [B,C] or None, row_add [B,R] or None)."""
+    col_a = np.asarray(col_a)
+    B, C = col_a.shape
+    rows, cols = np.asarray(rows), np.asarray(cols)
+    R = rows.shape[1]
+    D = int(np.prod(rows.shape[2:], dtype=np.int64))
+    wide = lambda a: None if a is None else np.asarray(a).astype(np.float64)
+    inv = np.zeros(0)
+    if D:
+        inv = 1.0 / np.broadcast_to(wide(scale).reshape(-1), (D,))
+    return wide(rows).reshape(B, R, D), wide(cols).reshape(B, C, D), inv, wide(col_a), wide(col_sub), wide(row_add)
+
+
+def _pairwise_scores(rows_b, cols_b, inv, col_a_b, col_sub_b):
+    """(s [R,C], term [C], q [R,C]) of one batch row, float64."""
+    R, C = rows_b.shape[0], cols_b.shape[0]
+    q = np.zeros((R, C), dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for d in range(rows_b.shape[1]):
+            q = q + ((rows_b[:, None, d] - cols_b[None, :, d]) * inv[d]) ** 2
+        term = col_a_b if col_sub_b is None else np.where(col_a_b == -np.inf, -np.inf, col_a_b - col_sub_b)
+        s = term[None, :] - 0.5 * q
+    return s, term, q
+
+
+def pairwise_lse(rows, cols, scale, col_a, col_sub=None, row_add=None):
+    """rows [B,R,...], cols [B,C,...] (trailing dims flattened to D values; none: no distance term), scale one value or
+    [D], col_a / col_sub [B,C], row_add [B,R] -> (out float64 [B,R], flags):
+
+        out[b,r] = row_add[b,r] + log sum_c exp( term[b,c] - 1/2 sum_d ((rows[b,r,d] - cols[b,c,d]) / scale[d])^2 )
+        term[b,c] = col_a[b,c] - col_sub[b,c],   -inf where col_a[b,c] == -inf whatever col_sub holds
+
+    in float64 whatever the operands' dtype is.  A NaN among a row point's scores or in its row_add: FLAG_NAN_LOG_WEIGHT and
+    NaN; else a maximum score of +inf: FLAG_DEGENERATE_ROW and +inf; else every score -inf: -inf and no flag."""
+    rows, cols, inv, col_a, col_sub, row_add = _pairwise_operands(rows, cols, scale, col_a, col_sub, row_add)
+    B, R = rows.shape[:2]
+    out = np.empty((B, R), dtype=np.float64)
+    flags = 0
+    for b in range(B):
+        s, _, _ = _pairwise_scores(rows[b], cols[b], inv, col_a[b], None if col_sub is None else col_sub[b])
+        add = np.zeros(R) if row_add is None else row_add[b]
+        nan = np.isnan(s).any(axis=1) | np.isnan(add)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            smax = np.max(np.where(np.isnan(s), -np.inf, s), axis=1)
+            finite = np.isfinite(smax) & ~nan
+            x = s - np.where(finite, smax, 0.0)[:, None]
+            w = np.where(x > EXP_UNDERFLOW, np.exp(np.minimum(x, 0.0)), 0.0)
+            value = add + (smax + np.log(w.sum(axis=1)))
+        value = np.where(finite, value, smax)          # +inf and -inf as they are, whatever row_add holds
+        out[b] = np.where(nan, np.nan, value)
+        if nan.any():
+            flags |= FLAG_NAN_LOG_WEIGHT
+        if (~nan & (smax == np.inf)).any():
+            flags |= FLAG_DEGENERATE_ROW
+    return out, flags
+
+
+def pairwise_lse_bound(rows, cols, scale, col_a, col_sub=None, row_add=None):
+    """[B,R] float64: how far a float64 evaluation of `pairwise_lse` in another order may lie from this one, derived and
+    not measured.  With eps = 2^-52, D values per point and C columns
+
+        bound[b,r] = eps * ( (D + 4) * max_c (|term[b,c]| + q[r,c] / 2)  +  C + 8 )
+
+    the maximum over the columns whose score lies within 40 of the row point's largest: the first part is fused against
+    separately rounded multiply-adds (and the order of the D additions) in the scores that matter, the second any order
+    of the C additions plus exp and log; columns further down carry less than C e^-40 of the sum.  Zero where the result
+    is not finite (those are conventions, held exactly)."""
+    rows, cols, inv, col_a, col_sub, row_add = _pairwise_operands(rows, cols, scale, col_a, col_sub, row_add)
+    B, R, D = rows.shape
+    C = cols.shape[1]
+    bound = np.zeros((B, R), dtype=np.float64)
+    for b in range(B):
+        s, term, q = _pairwise_scores(rows[b], cols[b], inv, col_a[b], None if col_sub is None else col_sub[b])
+        with np.errstate(invalid="ignore"):
+            smax = np.max(np.where(np.isnan(s), -np.inf, s), axis=1)
+            finite = np.isfinite(smax) & ~np.isnan(s).any(axis=1)
+            near = s >= (smax - NEAR_THE_MAXIMUM)[:, None]
+            size = np.where(near, np.abs(term)[None, :] + 0.5 * q, 0.0).max(axis=1)
+        bound[b] = np.where(finite, EPSILON * ((D + 4) * np.where(finite, size, 0.0) + C + 8), 0.0)
+    return bound
+
+
+def marginal_pass(latents, log_weights, locations, scale, return_tolerance=False):
+    """The whole backward recursion of the marginal smoother: latents T x [B,K,...], log_weights T x [B,K], locations(t)
+    -> the transition's location [B,K,...] of step t's stored particles for time t+1, scale as above.  Returns T x [B,K]
+    smoothed log-weights in log_weights' dtype:
+
+        ls[T-1] = log_w[T-1] - logsumexp(log_w[T-1])
+        den[j]  = log sum_l exp(log_w[t][l] - 1/2 |x[t+1][j] - loc[l]|^2)                         (pairwise_lse)
+        ls[t]   = log_w[t] + log sum_j exp(ls[t+1][j] - den[j] - 1/2 |loc[i] - x[t+1][j]|^2)      (pairwise_lse)
+
+    (|.|^2 in units of the scale), every pairwise_lse rounded to that dtype as the device's launches round theirs.
+    `return_tolerance`: also T x [B,K] float64, how far an evaluation that keeps every launch within `pairwise_lse_bound`
+    (and, in float32, within one unit in the last place of the rounding) may lie from this one: log-sum-exp moves by
+    at most the largest move of its terms, so a step's tolerance is the largest of the step after it plus the largest of
+    its denominators' plus its own; the last step's is four units in the last place of the row's log-sum-exp and of the
+    result (the log-sum-exp in the dtype's own arithmetic, one subtraction)."""
+    T = len(latents)
+    dtype = np.asarray(log_weights[-1]).dtype
+
+    def last_place(v):      # of the rounding to the dtype: float64 results are not rounded again
+        if dtype == np.float64:
+            return np.zeros(v.shape)
+        return np.where(np.isfinite(v), np.spacing(np.abs(np.where(np.isfinite(v), v, 0)).astype(dtype)), 0).astype(np.float64)
+
+    smoothed, tolerance = [None] * T, [None] * T
+    log_w = np.asarray(log_weights[-1]).astype(np.float64)
+    top = log_w.max(axis=1, keepdims=True)
+    lse = top + np.log(np.exp(log_w - top).sum(axis=1, keepdims=True))
+    smoothed[-1] = (log_w - lse).astype(dtype)
+    tolerance[-1] = 4.0 * float(np.finfo(dtype).eps) * (np.abs(lse) + np.abs(log_w - lse))
+    for t in range(T - 2, -1, -1):
+        loc, nxt, log_w = locations(t), latents[t + 1], log_weights[t]
+        den = pairwise_lse(nxt, loc, scale, log_w)[0].astype(dtype)
+        out = pairwise_lse(loc, nxt, scale, smoothed[t + 1], den, log_w)[0].astype(dtype)
+        smoothed[t] = out
+        den_tolerance = pairwise_lse_bound(nxt, loc, scale, log_w) + last_place(den)
+        tolerance[t] = (tolerance[t + 1].max(axis=1, keepdims=True) + den_tolerance.max(axis=1, keepdims=True) +
+                        pairwise_lse_bound(loc, nxt, scale, smoothed[t + 1], den, log_w) + last_place(out))
+    return (smoothed, tolerance) if return_tolerance else smoothed

@@ -61,7 +61,8 @@ extern "C" {
  *                added aesmc_affine_normal_initial_step (K20: the first timestep's draw, emission location and
  *                log-weight in one launch).
  *                Additive since, version unchanged: aesmc_resample_step_stratified (K2's stratified sibling: one uniform
- *                per particle); aesmc_backward_sample (K21: one step of backward simulation, FFBS).
+ *                per particle); aesmc_backward_sample (K21: one step of backward simulation, FFBS);
+ *                aesmc_pairwise_lse (K22: the pairwise log-sum-exp of the marginal smoother, FFBSm).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -315,6 +316,46 @@ int aesmc_backward_sample(int dtype, const void *log_w, const aesmc_view3 *loc, 
                           const void *scale, int64_t scale_stride, const double *u, int64_t *out_idx,
                           const aesmc_view3 *payload, void *out_payload, int32_t *flags, int64_t B, int64_t K, int64_t M,
                           int64_t D, int64_t P, void *stream);
+
+/* K22 — a pairwise Gaussian log-sum-exp: the building block of the marginal particle smoother (FFBSm; Huerzeler &
+ * Kuensch 1998; Doucet, Godsill & Andrieu 2000), which re-weights the particles the filter stored instead of drawing
+ * trajectories from them (K21).  The reference has no such call site.  For every batch row b and row point r:
+ *   out[b,r] = row_add[b,r] + log sum_c exp( term[b,c] - 1/2 sum_d ((rows[b,r,d] - cols[b,c,d]) / scale[d])^2 )
+ *   rows     T [B,R,D] view               the row points (`stride_k` steps along r)
+ *   cols     T [B,C,D] view               the columns (`stride_k` steps along c)
+ *   scale    T, D values                  read with the element stride `scale_stride`: 0 (one value) or 1
+ *   col_a    T [B,C] dense                a log-weight per column; -inf: the column is absent
+ *   col_sub  T [B,C] dense or NULL        subtracted from col_a (NULL: 0)
+ *   row_add  T [B,R] dense or NULL        added to the result (NULL: 0)
+ *   out      T [B,R] dense
+ * One backward step of FFBSm is two launches: the denominators den[b,j] (rows = the particles of step t+1, cols = the
+ * transition's locations of step t's particles, col_a = log_w_t), then the smoothed log-weights of step t (rows = the
+ * locations, cols = the particles of step t+1, col_a = the smoothed log-weights of step t+1, col_sub = den, row_add =
+ * log_w_t).  The Normal's normalising constant cancels between the two and is never formed; so does a constant in log_w_t.
+ * T is float32 or float64 (`dtype`); D == 0 (rows / cols / scale may be NULL) means no distance term.  All arithmetic is
+ * in float64 whatever T is:
+ *   inv[d]    = 1 / (double)scale[d]
+ *   q[r,c]    = sum_d (((double)rows[b,r,d] - (double)cols[b,c,d]) * inv[d])^2          (d ascending)
+ *   term[c]   = col_a[b,c] == -inf ? -inf : (double)col_a[b,c] - (double)col_sub[b,c]
+ *   s[r,c]    = term[c] - 0.5 * q[r,c]
+ *   out[b,r]  = (T)( (double)row_add[b,r] + (smax[r] + log sum_c exp(s[r,c] - smax[r])) ),   smax[r] = max_c s[r,c]
+ * with K2's float64 exp of a non-positive number, and ONE rounding to T, at the end.  The order of the sum over c, the
+ * reference value the exponentials are taken against while the maximum is not yet known, and the contraction of
+ * multiply-adds are the kernel's: the result lies within
+ *   2^-52 * ( (D + 4) * max_c (|term[c]| + q[r,c] / 2) + C + 8 )          (max over the columns with s[r,c] >= smax[r] - 40)
+ * of the exact value (aesmc_amd/testing/smoothing.py: pairwise_lse_bound), before the rounding to T.
+ * Special values, per (b, r); row points and batch rows never affect one another:
+ *   a NaN among s[r,:] (from any operand, `scale` included) or in row_add[b,r]: AESMC_FLAG_NAN_LOG_WEIGHT, out = NaN;
+ *   else smax[r] == +inf (a col_sub of -inf under a present column: a denominator without mass): AESMC_FLAG_DEGENERATE_ROW,
+ *        out = +inf;
+ *   else smax[r] == -inf (every column absent or infinitely far): out = -inf and NO flag — a point of zero weight.
+ * No workspace; R and C are independent and not bounded by LDS.  D above 256 or R, C above 2^30 - 1 return
+ * AESMC_ERR_UNSUPPORTED and launch nothing; B R == 0 is a no-op; C == 0 with row points to sum for is
+ * AESMC_ERR_INVALID_ARGUMENT.
+ */
+int aesmc_pairwise_lse(int dtype, const aesmc_view3 *rows, const aesmc_view3 *cols, const void *scale,
+                       int64_t scale_stride, const void *col_a, const void *col_sub, const void *row_add, void *out,
+                       int32_t *flags, int64_t B, int64_t R, int64_t C, int64_t D, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
