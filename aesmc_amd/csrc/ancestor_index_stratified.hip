@@ -21,7 +21,8 @@
 // particles before it are reached by the last position.  Every other comparison is a measure-zero knife edge, as in the
 // systematic kernels.
 //
-// Two kernels, as for the systematic scheme:
+// Two kernels, as for the systematic scheme, and built from the same phases (ancestor_index.hpp: row max, CDF, the tail
+// from first[] to the indices, the stored CDF and its search); what is written here is what only this scheme has:
 //   * ancestor_index_stratified_inv_kernel (K <= 32768, one workgroup per batch row): ancestor_index_inv_kernel's
 //     structure — CDF entries in registers, inversion per SOURCE particle, int32 max-scan over the markers.  Only the
 //     inversion differs: the positions are not an arithmetic progression, but pos[k] lies in stratum k, so the first
@@ -78,43 +79,19 @@ __global__ __launch_bounds__(kMaxThreads) void ancestor_index_stratified_inv_ker
 
   // ---- load once, row max + NaN scan ---------------------------------------------------------
   T v[C];
-  constexpr int NV = Vec16<T>::N;
-  if (C % NV == 0 && j0 + C <= K && (((uintptr_t)(lw + j0)) & 15u) == 0) {
-    using V = typename Vec16<T>::type;                       // the lane's C values as 16-byte loads
-#pragma unroll
-    for (int q = 0; q < C / NV; ++q) {
-      const V packed = reinterpret_cast<const V *>(lw + j0)[q];
-#pragma unroll
-      for (int r = 0; r < NV; ++r) v[q * NV + r] = Vec16<T>::get(packed, r);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < C; ++i) v[i] = (j0 + i < K) ? lw[j0 + i] : Num<T>::neg_inf();
-  }
-  T m = Num<T>::neg_inf();
-  int has_nan = 0;
-#pragma unroll
-  for (int i = 0; i < C; ++i) {
-    has_nan |= (v[i] != v[i]);
-    m = Num<T>::max(m, v[i]);
-  }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    m = Num<T>::max(m, __shfl_xor(m, off, kWave));
-    has_nan |= __shfl_xor(has_nan, off, kWave);
-  }
+  load_blocked<T, C>(lw, j0, K, v);
+  T m;
+  int has_nan;
+  lane_max_nan<T, C>(v, m, has_nan);
+  wave_max_nan(m, has_nan);
   if (lane == 0) {
     scratch[wave] = (double)m;
     scratch_i[wave] = has_nan;
   }
   __syncthreads();
-  double dm = scratch[0];
-  has_nan = scratch_i[0];
-  for (int w = 1; w < nwaves; ++w) {
-    dm = fmax(dm, scratch[w]);
-    has_nan |= scratch_i[w];
-  }
-  // (no barrier here: the scan below publishes into scratch slots of its own, kScanSlot onwards)
+  const RowMax all = collect_max_nan(scratch, scratch_i, nwaves);
+  const double dm = all.dm;
+  has_nan = all.has_nan;
   const bool degenerate = has_nan || !(dm > -__builtin_huge_val() && dm < __builtin_huge_val());
   if (degenerate) {  // same conventions as the systematic kernels: see include/aesmc_hip.h, K2
     if (tid == 0) {
@@ -130,36 +107,10 @@ __global__ __launch_bounds__(kMaxThreads) void ancestor_index_stratified_inv_ker
     return;
   }
 
-  // ---- float64 weights, blocked inclusive scan: ancestor_index_inv_kernel's, operation for operation --------------
+  // ---- float64 weights, blocked inclusive scan: the systematic kernels' CDF, bit for bit --------
   double s[C];
-  double run = 0.0;
-#pragma unroll
-  for (int i = 0; i < C; ++i) {
-    run += (j0 + i < K) ? exp_nonpositive((double)v[i] - dm) : 0.0;
-    s[i] = run;
-  }
-  double incl = run;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const double y = __shfl_up(incl, off, kWave);
-    if (lane >= off) incl += y;
-  }
-  double base = __shfl_up(incl, 1, kWave);
-  if (lane == 0) base = 0.0;
-  double *scan = scratch + kScanSlot;                          // [16] wavefront totals, [16] / [17]: see below
-  if (lane == kWave - 1) scan[wave] = incl;
-  // The CDF's last entry is the normaliser, so that c[K-1] == 1.0 exactly: its owner publishes the two terms only it
-  // has, and every lane adds the earlier wavefronts' totals in the owner's own order (see ancestor_index_inv_kernel).
-  const int last_wave = ((K - 1) / C) / kWave;
-  if (j0 <= K - 1 && K - 1 < j0 + C) {
-    scan[16] = base;
-    scan[17] = s[K - 1 - j0];
-  }
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) base += scan[w];
-  double total = scan[16];
-  for (int w = 0; w < last_wave; ++w) total += scan[w];
-  total += scan[17];
+  const RowScan scan = blocked_cdf<T, C>(v, dm, j0, K, lane, wave, scratch, s);
+  const double base = scan.base, total = scan.total;
   const double inv_total = 1.0 / total;
   // by-product: logsumexp of the row (the step's contribution to log Z), float64 inside
   if (out_lse != nullptr && tid == 0) out_lse[row] = (T)(dm + ::log(total));
@@ -213,102 +164,10 @@ __global__ __launch_bounds__(kMaxThreads) void ancestor_index_stratified_inv_ker
     for (int i = 0; i < C; ++i)
       if (j0 + i < K) first[i] = j0 + i < reached ? min(first[i], K - 1) : K;
   }
-  if (lane == 0) first_of_lane[wave] = first[0];            // the next wavefront's first entry, via LDS
-  int wave_min = K;
-  if (out_child_end != nullptr) {                           // (each wavefront's smallest first entry: see the clamp below)
-    wave_min = wave_suffix_min(first[0], lane);             // min over lanes >= this one, this wavefront
-    if (lane == 0) first_of_lane[16 + wave] = wave_min;
-  }
-  if constexpr (C % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < C / 4; ++q) reinterpret_cast<int4 *>(marker + j0)[q] = make_int4(0, 0, 0, 0);
-  } else {
-#pragma unroll
-    for (int i = 0; i < C; ++i) marker[j0 + i] = 0;
-  }
-  __syncthreads();
-  int next_lane_first = __shfl_down(first[0], 1, kWave);     // the next lane's first entry, in-register
-  if (lane == kWave - 1) next_lane_first = (wave + 1 < nwaves) ? first_of_lane[wave + 1] : K;
-  if (out_child_end != nullptr) {
-    // The children ranges must be monotone; across lanes first[] can descend by one on a knife-edge position (two lanes
-    // holding the same partial sum associated differently: ancestor_index_inv_kernel says how).  The indices the markers
-    // produce are those of first[]'s SUFFIX MINIMUM; the ranges are made to say the same.
-    int bound = __shfl_down(wave_min, 1, kWave);                       // min over the lanes BEHIND this one
-    if (lane == kWave - 1) bound = K;
-    for (int w = wave + 1; w < nwaves; ++w) bound = min(bound, first_of_lane[16 + w]);
-#pragma unroll
-    for (int i = 0; i < C; ++i) first[i] = min(first[i], bound);
-    next_lane_first = min(next_lane_first, bound);
-    // first[j] = how many positions precede the CDF at j = where the children of particles 0..j end
-    int32_t *ends = out_child_end + row * (int64_t)K + j0;
-    if (C % 4 == 0 && (K & 3) == 0 && j0 + C <= K && (reinterpret_cast<uintptr_t>(out_child_end) & 15u) == 0) {
-#pragma unroll
-      for (int q = 0; q < C / 4; ++q)
-        reinterpret_cast<int4 *>(ends)[q] = make_int4(first[4 * q], first[4 * q + 1], first[4 * q + 2], first[4 * q + 3]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < C; ++i)
-        if (j0 + i < K) ends[i] = first[i];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < C; ++i) {
-    const int j = j0 + i;
-    if (j < K) {
-      int next = (i + 1 < C) ? first[i + 1 < C ? i + 1 : i] : next_lane_first;
-      if (j == K - 1) next = K;
-      if (first[i] < next) marker[first[i]] = j + 1;       // distinct j write distinct slots; first[i] < next <= K
-    }
-  }
-  __syncthreads();
-
-  // ---- idx[k] = running maximum of the markers ------------------------------------------------
+  // ---- markers, max-scan, stores: idx[k] and the children ranges ---------------------------------
   int best[C];
-  if constexpr (C % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < C / 4; ++q) {
-      const int4 packed = reinterpret_cast<const int4 *>(marker + j0)[q];
-      best[4 * q] = packed.x;
-      best[4 * q + 1] = packed.y;
-      best[4 * q + 2] = packed.z;
-      best[4 * q + 3] = packed.w;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < C; ++i) best[i] = marker[j0 + i];
-  }
-  int acc = 0;
-#pragma unroll
-  for (int i = 0; i < C; ++i) {
-    acc = max(acc, best[i]);
-    best[i] = acc;
-  }
-  int incl_max = acc;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int y = __shfl_up(incl_max, off, kWave);
-    if (lane >= off) incl_max = max(incl_max, y);
-  }
-  int before = __shfl_up(incl_max, 1, kWave);
-  if (lane == 0) before = 0;
-  if (lane == kWave - 1) scratch_i[wave] = incl_max;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) before = max(before, scratch_i[w]);
-#pragma unroll
-  for (int i = 0; i < C; ++i) best[i] = max(before, best[i]);
-  if (j0 + C <= K && (((uintptr_t)(idx + j0)) & 15u) == 0) {
-#pragma unroll
-    for (int i = 0; i < C; i += 2) {
-      longlong2 pair;
-      pair.x = (int64_t)best[i];
-      pair.y = (int64_t)best[i + 1];
-      *reinterpret_cast<longlong2 *>(idx + j0 + i) = pair;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-      if (j0 + i < K) idx[j0 + i] = (int64_t)best[i];
-  }
+  indices_from_first<C>(first, best, K, j0, lane, wave, nwaves, marker, first_of_lane, scratch_i, out_child_end, row, idx,
+                        true);
 }
 
 // ---- the stored-CDF form (K > 32768): ancestor_index_kernel on the stratified positions ---------------------------------
@@ -331,30 +190,19 @@ __global__ __launch_bounds__(kMaxThreads) void ancestor_index_stratified_kernel(
   int64_t *idx = out_idx + row * (int64_t)K;
 
   // ---- pass 1: row max, NaN detection ---------------------------------------------------------
-  T m = Num<T>::neg_inf();
-  int has_nan = 0;
-  for (int k = tid; k < K; k += nt) {
-    T v = lw[k];
-    has_nan |= (v != v);
-    m = Num<T>::max(m, v);
-  }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    m = Num<T>::max(m, __shfl_xor(m, off, kWave));
-    has_nan |= __shfl_xor(has_nan, off, kWave);
-  }
   int *scratch_i = reinterpret_cast<int *>(scratch + 32);
+  T m;
+  int has_nan;
+  strided_max_nan(lw, K, tid, nt, m, has_nan);
+  wave_max_nan(m, has_nan);
   if (lane == 0) {
     scratch[wave] = (double)m;
     scratch_i[wave] = has_nan;
   }
   __syncthreads();
-  double dm = scratch[0];
-  has_nan = scratch_i[0];
-  for (int w = 1; w < nwaves; ++w) {
-    dm = fmax(dm, scratch[w]);
-    has_nan |= scratch_i[w];
-  }
+  const RowMax all = collect_max_nan(scratch, scratch_i, nwaves);
+  const double dm = all.dm;
+  has_nan = all.has_nan;
   __syncthreads();  // scratch is reused below
 
   const bool degenerate = has_nan || !(dm > -__builtin_huge_val() && dm < __builtin_huge_val());
@@ -364,57 +212,8 @@ __global__ __launch_bounds__(kMaxThreads) void ancestor_index_stratified_kernel(
     return;
   }
 
-  // ---- pass 2: float64 weights, blocked scan (round r covers nt * kChunk particles; `carry`: the earlier rounds) ----
-  const int per_round = nt * kChunk;
-  double carry = 0.0;
-  for (int round_base = 0; round_base < K; round_base += per_round) {
-    const int first = round_base + tid * kChunk;
-    double s[kChunk];
-    double run = 0.0;
-#pragma unroll
-    for (int i = 0; i < kChunk; ++i) {
-      const int k = first + i;
-      run += (k < K) ? exp_nonpositive((double)lw[k < K ? k : 0] - dm) : 0.0;
-      s[i] = run;
-    }
-    double incl = run;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const double y = __shfl_up(incl, off, kWave);
-      if (lane >= off) incl += y;
-    }
-    double excl = __shfl_up(incl, 1, kWave);  // exclusive prefix of this lane inside its wavefront
-    if (lane == 0) excl = 0.0;
-    if (lane == kWave - 1) scratch[wave] = incl;
-    __syncthreads();
-    double base = carry, round_total = 0.0;
-    for (int w = 0; w < nwaves; ++w) {
-      if (w == wave) base = carry + round_total;
-      round_total += scratch[w];
-    }
-    base += excl;
-#pragma unroll
-    for (int i = 0; i < kChunk; ++i) {
-      const int k = first + i;
-      if (k < K) cdf[cdf_slot(k)] = base + s[i];
-    }
-    carry += round_total;
-    __syncthreads();  // scratch is rewritten by the next round
-  }
-
-  // ---- pass 3: normalise by the row's last entry (every lane rereads only what it wrote) -------------
-  __syncthreads();
-  const double total = cdf[cdf_slot(K - 1)];
-  __syncthreads();
-  const double inv_total = 1.0 / total;
-  for (int round_base = 0; round_base < K; round_base += per_round) {
-    const int first = round_base + tid * kChunk;
-#pragma unroll
-    for (int i = 0; i < kChunk; ++i) {
-      const int k = first + i;
-      if (k < K) cdf[cdf_slot(k)] = divide_with_reciprocal(cdf[cdf_slot(k)], total, inv_total);
-    }
-  }
+  // ---- passes 2, 3: the normalised float64 CDF, stored ------------------------------------------
+  store_normalised_cdf<T, kChunk>(lw, K, dm, cdf, scratch, tid, nt, lane, wave, nwaves);
   // the last position at the clamp's value (row-uniform, never with drawn uniforms): its answer in the contract's order
   const double dK = (double)K;
   const double inv_K = 1.0 / dK;
@@ -422,87 +221,31 @@ __global__ __launch_bounds__(kMaxThreads) void ancestor_index_stratified_kernel(
   if (top && tid == 0) scratch_i[0] = sequential_top_count(lw, K, dm);      // (scratch_i: read last in front of pass 2)
   __syncthreads();
 
-  // ---- pass 4: idx[k] = #{ j : c[j] <= pos[k] }; pos[] is non-decreasing, so each search gallops from the last ------
+  // ---- pass 4: idx[k] = #{ j : c[j] <= pos[k] }; the last position at the clamp answers `reached` ----------------------
   const int reached = top ? scratch_i[0] : 0;
-  for (int round_base = 0; round_base < K; round_base += per_round) {
-    const int first = round_base + tid * kChunk;
-    if (first >= K) break;
-    int64_t found[kChunk];
-    int answer = 0;
-#pragma unroll
-    for (int i = 0; i < kChunk; ++i) {
-      const int k = first + i;
-      const double pos = stratified_position(ur[k < K ? k : K - 1], k, dK, inv_K);
-      int left, right;
-      if (i == 0) {
-        left = 0;
-        right = K;
-      } else {  // gallop from the previous particle's answer
-        left = answer;
-        int probe = answer, step = 1;
-        while (probe < K && cdf[cdf_slot(probe)] <= pos) {
-          left = probe + 1;
-          probe += step;
-          step <<= 1;
-        }
-        right = probe < K ? probe : K;
-      }
-      while (left < right) {
-        const int mid = (left + right) >> 1;
-        if (cdf[cdf_slot(mid)] <= pos)
-          left = mid + 1;
-        else
-          right = mid;
-      }
-      answer = left;
-      found[i] = (int64_t)((top && k == K - 1) ? reached : left);
-    }
-    if (first + kChunk <= K && (((uintptr_t)(idx + first)) & 15u) == 0) {
-#pragma unroll
-      for (int i = 0; i < kChunk; i += 2) {
-        longlong2 pair;
-        pair.x = found[i];
-        pair.y = found[i + 1];
-        *reinterpret_cast<longlong2 *>(idx + first + i) = pair;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < kChunk; ++i)
-        if (first + i < K) idx[first + i] = found[i];
-    }
-  }
+  search_stored_cdf<kChunk>(
+      cdf, idx, K, tid, nt, [=](int k) { return stratified_position(ur[k < K ? k : K - 1], k, dK, inv_K); }, top, reached);
 }
 
 template <typename T, int C>
 static int launch_stratified_inv(const void *log_w, const double *u, int64_t *idx, void *out_lse, int32_t *child_end,
                                  int32_t *flags, int64_t B, int64_t K, hipStream_t s) {
   const int nt = pick_threads(K, C);
-  const size_t lds = (size_t)kScratchDoubles * sizeof(double) + (size_t)(nt * C + nt + 8) * sizeof(int);
-  // raise the dynamic-LDS cap once per device and instantiation (a process may drive several GPUs)
-  static bool attr_set[64] = {};
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 64) return AESMC_ERR_LAUNCH;
-  if (!attr_set[device]) {
-    if (hipFuncSetAttribute((const void *)ancestor_index_stratified_inv_kernel<T, C>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return AESMC_ERR_LAUNCH;
-    attr_set[device] = true;
-  }
-  hipLaunchKernelGGL((ancestor_index_stratified_inv_kernel<T, C>), dim3((unsigned)B), dim3(nt), lds, s,
+  if (raise_dynamic_lds_cap<ancestor_index_stratified_inv_kernel<T, C>>() != AESMC_OK) return AESMC_ERR_LAUNCH;
+  hipLaunchKernelGGL((ancestor_index_stratified_inv_kernel<T, C>), dim3((unsigned)B), dim3(nt), inv_lds_bytes(nt, C), s,
                      (const T *)log_w, u, idx, flags, (int)K, (T *)out_lse, child_end);
   return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
 }
 
-// Particles per lane grow with the row so that one workgroup (<= 1024 lanes) covers it, as for the systematic kernels;
-// beyond 32768 particles the CDF goes through the caller's workspace and the by-products are the host's to compose.
+// Four particles per lane up to 4096 (the systematic ladder stops them at 2048); beyond 32768 particles the CDF goes
+// through the caller's workspace and the by-products are the host's to compose.
 template <typename T>
 static int launch_stratified(const void *log_w, const double *u, int64_t *idx, void *out_lse, int32_t *child_end,
                              int32_t *flags, int64_t B, int64_t K, void *ws, size_t ws_bytes, hipStream_t s) {
-  if (K <= 512) return launch_stratified_inv<T, 2>(log_w, u, idx, out_lse, child_end, flags, B, K, s);
-  if (K <= 4096) return launch_stratified_inv<T, 4>(log_w, u, idx, out_lse, child_end, flags, B, K, s);
-  if (K <= 8192) return launch_stratified_inv<T, 8>(log_w, u, idx, out_lse, child_end, flags, B, K, s);
-  if (K <= 16384) return launch_stratified_inv<T, 16>(log_w, u, idx, out_lse, child_end, flags, B, K, s);
-  if (K <= kInvMaxParticles) return launch_stratified_inv<T, 32>(log_w, u, idx, out_lse, child_end, flags, B, K, s);
+  if (K <= kInvMaxParticles)
+    return launch_by_row_length(K, 4096, [&](auto c) {
+      return launch_stratified_inv<T, decltype(c)::value>(log_w, u, idx, out_lse, child_end, flags, B, K, s);
+    });
   if (out_lse != nullptr || child_end != nullptr) return AESMC_ERR_UNSUPPORTED;
   if (ws == nullptr || ws_bytes < aesmc_workspace_bytes(B, K)) return AESMC_ERR_WORKSPACE;
   const size_t lds = (size_t)kScratchDoubles * sizeof(double);

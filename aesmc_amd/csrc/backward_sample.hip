@@ -12,12 +12,14 @@
 //   draw      per trajectory one wavefront adds the chunk sums up, finds the chunk in which u * total is crossed and
 //             rescans that one chunk with a wavefront prefix scan: two passes plus a sliver of L / K of one.
 //
-// Every score is formed by the same instruction sequence wherever it is formed (`score`, `score_tile`: d ascending,
-// ((t - l) * inv) squared into a fused multiply-add), so the particle that holds the maximum has w == 1 exactly in pass 2
-// and in the rescan.  The drawn particle always has positive weight: a crossing is only accepted on one, and a chunk
-// whose sum says "crossed in here" while the rescan's own order of additions does not (a difference in the last place)
-// yields its last particle of positive weight — which is also the clamp of the contract when u * total rounds to the total.
+// Every score is formed by the one function gaussian_scores (pairwise_gaussian.hpp: d ascending, ((t - l) * inv) squared
+// into a fused multiply-add; `score_tile` is its N = kTile, the rescan's `score` its N = 1), so the particle that holds
+// the maximum has w == 1 exactly in pass 2 and in the rescan.  The drawn particle always has positive weight: a crossing
+// is only accepted on one, and a chunk whose sum says "crossed in here" while the rescan's own order of additions does
+// not (a difference in the last place) yields its last particle of positive weight — which is also the clamp of the
+// contract when u * total rounds to the total.
 #include "ancestor_index.hpp"
+#include "pairwise_gaussian.hpp"
 
 namespace aesmc {
 
@@ -43,36 +45,17 @@ template <typename T>
 __device__ __forceinline__ void score_tile(const BackwardArgs<T> &a, const double *tgt, const double *inv, int64_t b,
                                            int k, double (&s)[kTile]) {
   const double lw = (double)a.log_w[b * a.K + k];
-  double q[kTile];
-#pragma unroll
-  for (int j = 0; j < kTile; ++j) q[j] = 0.0;
-  const T *row = a.loc + b * a.loc_b + (int64_t)k * a.loc_k;
-  for (int d = 0; d < a.D; ++d) {
-    const double l = (double)row[(int64_t)d * a.loc_d];
-    const double iv = inv[d];
-#pragma unroll
-    for (int j = 0; j < kTile; ++j) {
-      const double diff = (tgt[d * kTile + j] - l) * iv;
-      q[j] = __builtin_fma(diff, diff, q[j]);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kTile; ++j) s[j] = __builtin_fma(-0.5, q[j], lw);
+  gaussian_scores<T, kTile>(a.loc + b * a.loc_b + (int64_t)k * a.loc_k, a.loc_d, tgt, kTile, inv, a.D, lw, s);
 }
 
-// the same for ONE trajectory of the tile (the rescan): the same operations in the same order, hence the same bits
+// the same for ONE trajectory of the tile (the rescan): the same function on column j of the tile, hence the same bits
 template <typename T>
 __device__ __forceinline__ double score(const BackwardArgs<T> &a, const double *tgt, const double *inv, int64_t b, int k,
                                         int j) {
   const double lw = (double)a.log_w[b * a.K + k];
-  double q = 0.0;
-  const T *row = a.loc + b * a.loc_b + (int64_t)k * a.loc_k;
-  for (int d = 0; d < a.D; ++d) {
-    const double l = (double)row[(int64_t)d * a.loc_d];
-    const double diff = (tgt[d * kTile + j] - l) * inv[d];
-    q = __builtin_fma(diff, diff, q);
-  }
-  return __builtin_fma(-0.5, q, lw);
+  double s[1];
+  gaussian_scores<T, 1>(a.loc + b * a.loc_b + (int64_t)k * a.loc_k, a.loc_d, tgt + j, kTile, inv, a.D, lw, s);
+  return s[0];
 }
 
 template <typename T>
@@ -88,13 +71,8 @@ __global__ __launch_bounds__(kBackThreads) void backward_sample_kernel(const Bac
   const int m0 = (int)(blockIdx.x % a.tiles) * kTile;
 
   // the tile's targets (a trajectory beyond M repeats the last one and is never written) and 1 / scale
-  for (int i = tid; i < a.D * kTile; i += kBackThreads) {
-    const int d = i / kTile, j = i % kTile;
-    const int m = min(m0 + j, a.M - 1);
-    tgt[i] = (double)a.target[b * a.target_b + (int64_t)m * a.target_m + (int64_t)d * a.target_d];
-  }
-  for (int d = tid; d < a.D; d += kBackThreads) inv[d] = 1.0 / (double)a.scale[(int64_t)d * a.scale_stride];
-  __syncthreads();
+  stage_tile<T, kTile>(a.target + b * a.target_b, a.target_m, a.target_d, m0, a.M, a.scale, a.scale_stride, a.D, tid,
+                       kBackThreads, tgt, inv);
 
   // ---- pass 1: maxima -------------------------------------------------------------------------------------------
   double smax[kTile];
@@ -197,12 +175,7 @@ __global__ __launch_bounds__(kBackThreads) void backward_sample_kernel(const Bac
           const int k = k0 + lane;
           double w = 0.0;
           if (k < k_end) w = exp_nonpositive(score(a, tgt, inv, b, k, j) - top);
-          double c = w;      // inclusive prefix sum over the lanes
-#pragma unroll
-          for (int d = 1; d < kWave; d <<= 1) {
-            const double other = __shfl_up(c, d, kWave);
-            if (lane >= d) c += other;
-          }
+          const double c = wave_inclusive_add(w, lane);
           const unsigned long long weighs = __ballot(w > 0.0);
           const unsigned long long crosses = __ballot(w > 0.0 && run + c > thr);
           if (weighs != 0) positive = k0 + 63 - __builtin_clzll(weighs);

@@ -22,9 +22,10 @@
 // figures in profiles/ffbsm_pairwise_lse.txt): tiles of 16 row points, workgroups of four wavefronts (each takes every
 // fourth run of 64 columns; their (reference, sum) pairs are merged through LDS) and the two-pass form (maxima first,
 // then the sums: K21's passes 1 and 2).  All are slower at R = C = K: 1.07 - 1.14 x, 1.10 - 1.15 x and 1.23 - 1.41 x.
-// Every form computes a score by the same instruction sequence (K21's: d ascending, ((r - c) * inv) squared into a fused
-// multiply-add).
+// Every form computes a score by the function K21 uses (gaussian_scores of pairwise_gaussian.hpp: d ascending,
+// ((r - c) * inv) squared into a fused multiply-add).
 #include "ancestor_index.hpp"
+#include "pairwise_gaussian.hpp"
 
 namespace aesmc {
 
@@ -49,21 +50,7 @@ __device__ __forceinline__ void pairwise_scores(const PairwiseArgs<T> &a, const 
     const double sub = (double)a.col_sub[at];
     term = term == -__builtin_huge_val() ? term : term - sub;
   }
-  double q[kRows];
-#pragma unroll
-  for (int j = 0; j < kRows; ++j) q[j] = 0.0;
-  const T *col = a.cols + b * a.cols_b + (int64_t)c * a.cols_c;
-  for (int d = 0; d < a.D; ++d) {
-    const double v = (double)col[(int64_t)d * a.cols_d];
-    const double iv = inv[d];
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-      const double diff = (tile[d * kRows + j] - v) * iv;
-      q[j] = __builtin_fma(diff, diff, q[j]);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kRows; ++j) s[j] = __builtin_fma(-0.5, q[j], term);
+  gaussian_scores<T, kRows>(a.cols + b * a.cols_b + (int64_t)c * a.cols_c, a.cols_d, tile, kRows, inv, a.D, term, s);
 }
 
 // the largest x of the wavefront (fmax drops a NaN operand), held in scalar registers: the same in every lane
@@ -91,13 +78,8 @@ __global__ __launch_bounds__(kWaves *kWave) void pairwise_lse_kernel(const Pairw
   const int r0 = (int)(blockIdx.x % a.tiles) * kRows;
 
   // the tile's row points (one beyond R repeats the last one and is never written) and 1 / scale
-  for (int i = tid; i < a.D * kRows; i += kThreads) {
-    const int d = i / kRows, j = i % kRows;
-    const int r = min(r0 + j, a.R - 1);
-    tile[i] = (double)a.rows[b * a.rows_b + (int64_t)r * a.rows_r + (int64_t)d * a.rows_d];
-  }
-  for (int d = tid; d < a.D; d += kThreads) inv[d] = 1.0 / (double)a.scale[(int64_t)d * a.scale_stride];
-  __syncthreads();
+  stage_tile<T, kRows>(a.rows + b * a.rows_b, a.rows_r, a.rows_d, r0, a.R, a.scale, a.scale_stride, a.D, tid, kThreads,
+                       tile, inv);
 
   double ref[kRows], sum[kRows];      // ref: the same in every lane of a wavefront
   int nan_bits = 0;
