@@ -2041,6 +2041,65 @@ class HipKernels:
                      tuple(keep) + (col_a, col_sub, row_add, out) + tuple(views))
         return out
 
+    # ---- K23 -----------------------------------------------------------------------------------
+    PAIRWISE_MEAN_MAX_PAYLOAD = 256
+
+    @staticmethod
+    def pairwise_mean_covers(rows, cols, scale, col_a, payload, col_sub=None, row_add=None):
+        """Whether `pairwise_mean` takes these operands: what `pairwise_lse_covers` takes, and a payload [B,C,*] of the same
+        dtype on the same device with 1 .. 256 values per column (a [B,C] payload has one)."""
+        if not HipKernels.pairwise_lse_covers(rows, cols, scale, col_a, col_sub, row_add):
+            return False
+        if not (torch.is_tensor(payload) and payload.dtype == col_a.dtype and payload.device == col_a.device and
+                payload.dim() >= 2 and tuple(payload.shape[:2]) == tuple(col_a.shape)):
+            return False
+        P = 1
+        for size in payload.shape[2:]:
+            P *= size
+        return 1 <= P <= HipKernels.PAIRWISE_MEAN_MAX_PAYLOAD
+
+    def pairwise_mean(self, rows, cols, scale, col_a, payload, col_sub=None, row_add=None):
+        """The pairwise Gaussian softmax mean (aesmc_pairwise_mean, K23), with s[b,r,c] the score `pairwise_lse` sums:
+            out[b,r,p] = sum_c softmax_c(s[b,r,:])[c] * payload[b,c,p]
+            lse[b,r]   = pairwise_lse(rows, cols, scale, col_a, col_sub, row_add)[b,r]
+        Operands as `pairwise_lse` takes them; payload [B,C,*] (trailing dims flattened to P <= 256 values).  Returns
+        (out [B,R,P], lse [B,R]) in col_a's dtype.  Views are taken as they are (element strides)."""
+        tag = self._rows_operand(col_a, "col_a")
+        if not self.pairwise_mean_covers(rows, cols, scale, col_a, payload, col_sub, row_add):
+            raise ValueError("aesmc_amd: pairwise_mean does not take these operands (see pairwise_mean_covers)")
+        B, C = col_a.shape
+        R = rows.size(1)
+        for t in (rows, cols, payload, col_sub, row_add):
+            if t is not None:
+                _require_hip(t, "pairwise operand")
+        col_a = col_a.contiguous()
+        col_sub = None if col_sub is None else col_sub.contiguous()
+        row_add = None if row_add is None else row_add.contiguous()
+        payload, sp, P = self._view3(payload)
+        out = torch.empty((B, R, P), dtype=col_a.dtype, device=col_a.device)
+        lse = torch.empty((B, R), dtype=col_a.dtype, device=col_a.device)
+        if lse.numel() == 0:
+            return out, lse
+        views, keep, D, scale_stride = [None, None], [rows, cols], 0, 0
+        if all(size > 0 for size in rows.shape[2:]):
+            (rows, sr, D), (cols, sc, _) = self._view3(rows), self._view3(cols)
+            _require_hip(scale, "scale")
+            scale = scale.reshape(-1).contiguous()
+            scale_stride = 0 if scale.numel() == 1 else 1
+            views = [_lib.View3(_ptr(rows), *sr), _lib.View3(_ptr(cols), *sc)]
+            keep = [rows, cols, scale]
+        views.append(_lib.View3(_ptr(payload), *sp))
+        esz = col_a.element_size()
+        refs = [ctypes.byref(v) if v is not None else None for v in views]
+        self._launch(col_a.device, self._lib.aesmc_pairwise_mean,
+                     (tag, refs[0], refs[1], _ptr(scale) if D else 0, scale_stride, _ptr(col_a), _ptr(col_sub),
+                      _ptr(row_add), refs[2], _ptr(out), _ptr(lse), _ptr(self.flags(col_a.device)), B, R, C, D, P,
+                      self._stream(col_a)),
+                     lambda: B * esz * ((R + C) * D + C * P + R * P + C * (2 if col_sub is not None else 1) +
+                                        R * (2 if row_add is not None else 1)),
+                     tuple(keep) + (col_a, col_sub, row_add, payload, out, lse) + tuple(views))
+        return out, lse
+
 
 _provider = None
 _provider_lock = threading.Lock()

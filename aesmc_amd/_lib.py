@@ -100,6 +100,8 @@ SIGNATURES = {
                                      ctypes.POINTER(View3), _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "aesmc_pairwise_lse": (_i32, [_i32, ctypes.POINTER(View3), ctypes.POINTER(View3), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                   _i64, _i64, _i64, _i64, _vp]),
+    "aesmc_pairwise_mean": (_i32, [_i32, ctypes.POINTER(View3), ctypes.POINTER(View3), _vp, _i64, _vp, _vp, _vp,
+                                   ctypes.POINTER(View3), _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,
@@ -145,6 +147,7 @@ TEST_HOOKS = {
     "aesmc_test_last_logweight_backward_form": (_i32, []),
     "aesmc_test_last_affine_backward_particles_per_lane": (_i32, []),
     "aesmc_test_set_pairwise_lse_form": (_i32, [_i32, _i32, _i32]),
+    "aesmc_test_set_pairwise_mean_form": (_i32, [_i32]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
-// What the pairwise Gaussian kernels share (K21, backward_sample.hip; K22, pairwise_lse.hip): the score of a particle
-// (column) against a tile of points held in LDS, and the staging of that tile.  ONE definition of the score, so that it
-// has the same bits wherever it is formed — K21 rests on that: the particle that holds a trajectory's maximum must have
-// w == 1 exactly both in the chunk sums (N = kTile) and in the rescan of one chunk (N = 1).
+// What the pairwise Gaussian kernels share (K21, backward_sample.hip; K22, pairwise_lse.hip; K23, pairwise_mean.hip): the
+// score of a particle (column) against a tile of points held in LDS, and the staging of that tile.  ONE definition of the
+// score, so that it has the same bits wherever it is formed — K21 rests on that: the particle that holds a trajectory's
+// maximum must have w == 1 exactly both in the chunk sums (N = kTile) and in the rescan of one chunk (N = 1).
 #pragma once
 #include "common.hpp"
 
@@ -41,6 +41,38 @@ __device__ __forceinline__ void stage_tile(const T *points, int64_t stride_r, in
   }
   for (int d = tid; d < D; d += threads) inv[d] = 1.0 / (double)scale[(int64_t)d * scale_stride];
   __syncthreads();
+}
+
+// ---- what the pairwise kernels over [B,R] x [B,C] share (K22, pairwise_lse.hip; K23, pairwise_mean.hip) ----------------
+template <typename T> struct PairwiseArgs {
+  const T *rows, *cols, *scale;
+  int64_t rows_b, rows_r, rows_d, cols_b, cols_c, cols_d, scale_stride;
+  const T *col_a, *col_sub, *row_add;
+  T *out;
+  int32_t *flags;
+  int R, C, D, tiles;
+};
+
+// s[j] for the tile's kRows row points and column c of batch row b
+template <typename T, int kRows>
+__device__ __forceinline__ void pairwise_scores(const PairwiseArgs<T> &a, const double *tile, const double *inv, int64_t b,
+                                                int c, double (&s)[kRows]) {
+  const int64_t at = b * a.C + c;
+  double term = (double)a.col_a[at];
+  if (a.col_sub != nullptr) {      // (launch-uniform)  an absent column stays absent whatever col_sub holds
+    const double sub = (double)a.col_sub[at];
+    term = term == -__builtin_huge_val() ? term : term - sub;
+  }
+  gaussian_scores<T, kRows>(a.cols + b * a.cols_b + (int64_t)c * a.cols_c, a.cols_d, tile, kRows, inv, a.D, term, s);
+}
+
+// the largest x of the wavefront (fmax drops a NaN operand), held in scalar registers: the same in every lane
+__device__ __forceinline__ double wave_max_uniform(double x) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off, kWave));
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x));
+  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
+  return __hiloint2double(hi, lo);
 }
 
 }  // namespace aesmc

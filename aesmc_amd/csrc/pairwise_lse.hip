@@ -31,37 +31,6 @@ namespace aesmc {
 
 constexpr int kLseMaxDim = 256;      // D the entry accepts: the row tile is kRows * D float64 of LDS (16 KiB at 8 rows)
 
-template <typename T> struct PairwiseArgs {
-  const T *rows, *cols, *scale;
-  int64_t rows_b, rows_r, rows_d, cols_b, cols_c, cols_d, scale_stride;
-  const T *col_a, *col_sub, *row_add;
-  T *out;
-  int32_t *flags;
-  int R, C, D, tiles;
-};
-
-// s[j] for the tile's kRows row points and column c of batch row b
-template <typename T, int kRows>
-__device__ __forceinline__ void pairwise_scores(const PairwiseArgs<T> &a, const double *tile, const double *inv, int64_t b,
-                                                int c, double (&s)[kRows]) {
-  const int64_t at = b * a.C + c;
-  double term = (double)a.col_a[at];
-  if (a.col_sub != nullptr) {      // (launch-uniform)  an absent column stays absent whatever col_sub holds
-    const double sub = (double)a.col_sub[at];
-    term = term == -__builtin_huge_val() ? term : term - sub;
-  }
-  gaussian_scores<T, kRows>(a.cols + b * a.cols_b + (int64_t)c * a.cols_c, a.cols_d, tile, kRows, inv, a.D, term, s);
-}
-
-// the largest x of the wavefront (fmax drops a NaN operand), held in scalar registers: the same in every lane
-__device__ __forceinline__ double wave_max_uniform(double x) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off, kWave));
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
-  return __hiloint2double(hi, lo);
-}
-
 template <typename T, int kRows, int kWaves, bool kTwoPass>
 __global__ __launch_bounds__(kWaves *kWave) void pairwise_lse_kernel(const PairwiseArgs<T> a) {
   extern __shared__ __align__(16) double lds[];      // D * (kRows + 1) float64, sized by the launch

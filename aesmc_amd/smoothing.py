@@ -1,5 +1,5 @@
 """Smoothing from the particles an SMC run has already stored: p(x_0..x_{T-1} | y_0..y_{T-1}) instead of the filter's
-p(x_t | y_0..y_t).  Two smoothers, both over `infer(..., return_original_latents=True, return_log_weights=True)`:
+p(x_t | y_0..y_t).  Three smoothers, all over `infer(..., return_original_latents=True, return_log_weights=True)`:
 
 `backward_simulate` / `smooth` — forward filtering / backward SIMULATION (FFBS; Godsill, Doucet & West 2004): M equally
     weighted draws from the JOINT smoothing distribution.  O(M K) pairs per step; use it when whole trajectories are
@@ -14,6 +14,11 @@ p(x_t | y_0..y_t).  Two smoothers, both over `infer(..., return_original_latents
     means, variances or any E[f(x_t) | all observations] — no Monte-Carlo noise on top of the filter's.  The cost is
     quadratic in earnest: at B = 1024, K = 4096, T = 100 it is 2 * 99 * 1024 * 4096^2 = 3.4e12 pairs per call — seconds,
     not milliseconds (profiles/ffbsm_pairwise_lse.txt).
+`two_slice_expectation` / `two_slice_smooth` — the TWO-SLICE smoother: E[g(x_{t+1}) f(x_t)^T | y_0..y_{T-1}] for every
+    pair of neighbouring steps, AND the marginal smoother's weights, from one backward pass.  The lag-one cross moment
+    E[x_{t+1} x_t^T] of an EM M-step for the transition, the statistic of a Fisher-identity score, any smoothed additive
+    functional (examples/lgssm_em.py).  O(K^2) pairs per step, twice, like the marginal smoother
+    (profiles/ffbsm_pairwise_mean.txt).
 
 The smoothed posterior `infer(..., return_latents=True)` gives is the genealogy (`inference.get_resampled_latents`): every
 final particle traced back through the ancestor indices.  Over a long sequence the genealogy collapses — after a hundred
@@ -29,7 +34,15 @@ The marginal smoother sums where backward simulation draws:
     w[t|T][i] = w[t][i] * sum_j w[t+1|T][j] f(x[t+1][j] | x[t][i]) / (sum_l w[t][l] f(x[t+1][j] | x[t][l]))
 
 two launches of kernel K22 per step (`aesmc_pairwise_lse`: a pairwise particle x particle log-sum-exp, O(B K^2 D), nothing
-of size [K,K] stored): the denominators, then the weights.
+of size [K,K] stored): the denominators, then the weights.  The two-slice weights fall out of the same recursion:
+
+    W[t][i,j] = w[t][i] f(x[t+1][j] | x[t][i]) w[t+1|T][j] / den[j],       den[j] = sum_l w[t][l] f(x[t+1][j] | x[t][l])
+    E[g(x_{t+1}) f(x_t)^T | y] = sum_j w[t+1|T][j] g(x[t+1][j]) m[j]^T
+    m[j] = sum_i softmax_i(log w[t][i] + log f(x[t+1][j] | x[t][i])) f(x[t][i])
+
+m[j] is the mean of a payload under the backward kernel of particle j — the pass that forms den[j], carrying a vector per
+column: kernel K23 (`aesmc_pairwise_mean`, O(B K^2 (D + P)), nothing of size [K,K] stored) in place of the first of K22's
+two launches, den[j] being its normaliser.
 
 The reference has no counterpart; this module adds to its interface and changes none of it.
 """
@@ -242,3 +255,99 @@ def marginal_smooth(observations, initial, transition, emission, proposal, num_p
                           return_log_weight=False, return_log_weights=True, resampling=resampling)
     smoothed = marginal_log_weights(out["original_latents"], out["log_weights"], transition, observations=observations)
     return out["original_latents"], smoothed, out["log_marginal_likelihood"]
+
+
+def _feature(function, time, latent, limit, what):
+    """`function(time, latent)` (None: the latent itself) as a [B,K,n] tensor of the latent's dtype: trailing dims flattened."""
+    value = latent if function is None else function(time, latent)
+    if not torch.is_tensor(value) or value.dim() < 2 or tuple(value.shape[:2]) != tuple(latent.shape[:2]):
+        raise ValueError("two_slice_expectation: {} must return a tensor [batch_size, num_particles, ...], got {}".format(
+            what, tuple(value.shape) if torch.is_tensor(value) else type(value).__name__))
+    value = _lazy.real(value).detach()
+    if value.dtype != latent.dtype or value.device != latent.device:
+        raise ValueError("two_slice_expectation: {} must keep the latents' dtype and device, got {} on {}".format(
+            what, value.dtype, value.device))
+    value = value.reshape(value.shape[0], value.shape[1], -1) if value.dim() != 3 else value
+    if limit is not None and not 1 <= value.shape[2] <= limit:
+        _refuse("{} of {} values per particle (1 <= P <= {})".format(what, value.shape[2], limit))
+    return value
+
+
+def two_slice_expectation(latents, log_weights, transition, observations=None, previous=None, following=None):
+    """The two-slice particle smoother over the particles of one SMC run:
+
+        expectations[t][b,q,p] = E[ following_q(x_{t+1}) previous_p(x_t) | y_0..y_{T-1} ],     t = 0 .. T-2
+
+    and the marginal smoother's log-weights, from ONE backward pass.
+
+    latents, log_weights, transition, observations: as `marginal_log_weights` takes them, with the same contract for the
+        transition — for t = T-2 ... 0 it is called ONCE on the stored particles, as `transition(previous_latents=
+        latents[:t+1], time=t+1, previous_observations=observations[:t+1])` with plain tensors; MARKOV MODELS ONLY:
+        `previous_latents[-1]` must be all of the latents the transition reads.
+    previous, following: None — the latent itself, trailing dims flattened; or a callable `(time, latent [batch_size,
+        num_particles, ...]) -> tensor [batch_size, num_particles, ...]` in the latents' dtype, flattened to P (at most
+        256, else NotImplementedError) and Q (any number of) values.  Per step, each is called once, on plain detached
+        tensors: `previous(t, latents[t])` and `following(t + 1, latents[t + 1])`.
+
+    Returns (expectations, smoothed): T-1 tensors [batch_size, Q, P] in the latents' dtype (an empty list for T = 1), and
+    T tensors [batch_size, num_particles], exactly what `marginal_log_weights` documents.  With the defaults
+    `expectations[t]` is E[x_{t+1} x_t^T | y]; `previous = lambda t, x: x.new_ones(x.shape[0], x.shape[1], 1)` reproduces
+    E[following(x_{t+1}) | y] (the marginal means under smoothed[t+1]), `following = ones` likewise E[previous(x_t) | y]
+    under smoothed[t].
+
+    Per step: one launch of kernel K23 (the backward kernel's mean m[j] of `previous` for every particle j of step t+1,
+    and the denominators), one of K22 (the smoothed log-weights of step t) and the contraction sum_j exp(smoothed[t+1][j])
+    following_j (x) m_j as a float64 batched product, rounded once — O(batch_size num_particles^2 (D + P)) per step, in
+    float64, nothing of size [num_particles, num_particles] stored.  Deterministic: no random stream is consumed, and
+    batch rows are independent, so it works unchanged inside `distributed.shard_scope`.
+
+    Covered and refused as in `backward_simulate`.  NaN log-weights, particles, locations or features raise
+    FloatingPointError; a particle of step t+1 that no particle of step t can reach RuntimeError — read once, at the end
+    (one synchronisation per call).  Not capturable into a hipGraph."""
+    num_timesteps = len(latents)
+    if num_timesteps == 0 or len(log_weights) != num_timesteps:
+        raise ValueError("two_slice_expectation: latents and log_weights must be equally long and not empty, got {} and {}"
+                         .format(num_timesteps, len(log_weights)))
+    if any(isinstance(latent, dict) for latent in latents):
+        _refuse("dict latents")
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            latents = [_lazy.real(latent).detach() for latent in latents]
+            log_weights = [_lazy.real(log_weight).detach() for log_weight in log_weights]
+            smoothed = [None] * num_timesteps
+            expectations = [None] * (num_timesteps - 1)
+            smoothed[-1] = math.lognormexp(log_weights[-1], dim=1)
+            for time in range(num_timesteps - 2, -1, -1):
+                distribution = transition(
+                    previous_latents=latents[:time + 1], time=time + 1,
+                    previous_observations=None if observations is None else observations[:time + 1])
+                loc, scale = _transition_terms(distribution, latents[time])
+                after = latents[time + 1]
+                payload = _feature(previous, time, latents[time], _kernels.HipKernels.PAIRWISE_MEAN_MAX_PAYLOAD,
+                                   "a `previous` feature")
+                outer = _feature(following, time + 1, after, None, "a `following` feature")
+                means, denominators = provider.pairwise_mean(after, loc, scale, log_weights[time], payload)
+                smoothed[time] = provider.pairwise_lse(loc, after, scale, smoothed[time + 1], col_sub=denominators,
+                                                       row_add=log_weights[time])
+                weighted = outer.double() * torch.exp(smoothed[time + 1].double()).unsqueeze(-1)
+                expectations[time] = torch.bmm(weighted.transpose(1, 2), means.double()).to(after.dtype)
+            inference._raise_for_flags(provider.read_flags(log_weights[-1].device))
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return expectations, smoothed
+
+
+def two_slice_smooth(observations, initial, transition, emission, proposal, num_particles, resampling=None, previous=None,
+                     following=None):
+    """Runs the SMC filter (`inference.infer("smc", ...)`, keeping the particles as drawn and every step's log-weights)
+    and then `two_slice_expectation` over what it stored.  Returns (original_latents, smoothed_log_weights, expectations,
+    log_marginal_likelihood): T tensors [batch_size, num_particles, ...], T tensors [batch_size, num_particles], T-1
+    tensors [batch_size, Q, P] and the filter's [batch_size] estimate."""
+    out = inference.infer("smc", observations, initial, transition, emission, proposal, num_particles,
+                          return_log_marginal_likelihood=True, return_latents=False, return_original_latents=True,
+                          return_log_weight=False, return_log_weights=True, resampling=resampling)
+    expectations, smoothed = two_slice_expectation(out["original_latents"], out["log_weights"], transition,
+                                                   observations=observations, previous=previous, following=following)
+    return out["original_latents"], smoothed, expectations, out["log_marginal_likelihood"]

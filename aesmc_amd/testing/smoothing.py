@@ -2,7 +2,8 @@
 written without regard to the kernel's structure (no tiles, no chunks, no passes) — what the tests hold the HIP result to,
 exactly — and of the whole backward pass that `aesmc_amd.smoothing.backward_simulate` makes of it.  Below it the same
 for the marginal smoother: the pairwise log-sum-exp (aesmc_pairwise_lse), the bound its kernel is held to, and the
-backward recursion that `aesmc_amd.smoothing.marginal_log_weights` makes of it.
+backward recursion that `aesmc_amd.smoothing.marginal_log_weights` makes of it; and for the two-slice smoother: the
+pairwise softmax mean (aesmc_pairwise_mean), its bound, and the recursion of `aesmc_amd.smoothing.two_slice_expectation`.
 
 One backward step of forward filtering / backward simulation (Godsill, Doucet & West 2004): trajectory m, whose state at
 t+1 is target[b,m], draws particle k of step t with probability proportional to
@@ -223,3 +224,149 @@ def marginal_pass(latents, log_weights, locations, scale, return_tolerance=False
         tolerance[t] = (tolerance[t + 1].max(axis=1, keepdims=True) + den_tolerance.max(axis=1, keepdims=True) +
                         pairwise_lse_bound(loc, nxt, scale, smoothed[t + 1], den, log_w) + last_place(out))
     return (smoothed, tolerance) if return_tolerance else smoothed
+
+
+# ---- the two-slice smoother: E[g(x_{t+1}) f(x_t)^T | y_0..y_{T-1}] from the same recursion ----------------------------------
+def _payload_operand(payload, B, C):
+    payload = np.asarray(payload)
+    if payload.shape[:2] != (B, C):
+        raise ValueError("one payload per column: payload must be [{}, {}, ...], got {}".format(B, C, payload.shape))
+    return payload.astype(np.float64).reshape(B, C, -1)
+
+
+def _softmax_weights(s, add):
+    """(w [R,C] = exp(s - smax) with the kernels' underflow, nan [R], smax [R], finite [R]) of one batch row."""
+    nan = np.isnan(s).any(axis=1) | np.isnan(add)
+    with np.errstate(invalid="ignore", over="ignore"):
+        smax = np.max(np.where(np.isnan(s), -np.inf, s), axis=1)
+        finite = np.isfinite(smax) & ~nan
+        x = s - np.where(finite, smax, 0.0)[:, None]
+        w = np.where(x > EXP_UNDERFLOW, np.exp(np.minimum(x, 0.0)), 0.0)
+    return np.where(finite[:, None], w, 0.0), nan, smax, finite
+
+
+def pairwise_mean(rows, cols, scale, col_a, payload, col_sub=None, row_add=None):
+    """Operands as `pairwise_lse` takes them, payload [B,C,...] (trailing dims flattened to P values) ->
+    (out float64 [B,R,P], lse float64 [B,R], flags):
+
+        s[b,r,c]   = term[b,c] - 1/2 sum_d ((rows[b,r,d] - cols[b,c,d]) / scale[d])^2        (term as pairwise_lse forms it)
+        out[b,r,p] = sum_c softmax_c(s[b,r,:])[c] * payload[b,c,p]
+        lse[b,r]   = pairwise_lse(rows, cols, scale, col_a, col_sub, row_add)[b,r]
+
+    in float64 whatever the operands' dtype is: sum_c e_c payload_c / sum_c e_c with e_c = exp(s_c - max s), a true
+    division.  Conventions, per row point (row points and batch rows never affect one another):
+      a column with col_a == -inf is absent: its payload is SELECTED out (replaced by zero, not multiplied by a zero weight),
+        so whatever it holds (NaN, inf) never reaches a result.  The payload of a present column must be finite;
+      a NaN among the row point's scores or in its row_add: FLAG_NAN_LOG_WEIGHT, its P values and its lse NaN;
+      else a largest score of +inf: FLAG_DEGENERATE_ROW, lse +inf and its P values NaN (there are no weights to average with);
+      else every score -inf: out 0, lse -inf and no flag — a point of zero weight."""
+    lse, flags = pairwise_lse(rows, cols, scale, col_a, col_sub, row_add)
+    rows, cols, inv, col_a, col_sub, row_add = _pairwise_operands(rows, cols, scale, col_a, col_sub, row_add)
+    B, R = rows.shape[:2]
+    C = cols.shape[1]
+    payload = _payload_operand(payload, B, C)
+    out = np.empty((B, R, payload.shape[2]), dtype=np.float64)
+    for b in range(B):
+        s, _, _ = _pairwise_scores(rows[b], cols[b], inv, col_a[b], None if col_sub is None else col_sub[b])
+        w, nan, smax, finite = _softmax_weights(s, np.zeros(R) if row_add is None else row_add[b])
+        held = np.where((col_a[b] == -np.inf)[:, None], 0.0, payload[b])
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            mean = (w[:, :, None] * held[None, :, :]).sum(axis=1) / w.sum(axis=1)[:, None]
+        mean = np.where((smax == -np.inf)[:, None] & ~nan[:, None], 0.0, np.where(finite[:, None], mean, np.nan))
+        out[b] = mean
+    return out, lse, flags
+
+
+def pairwise_mean_bound(rows, cols, scale, col_a, payload, col_sub=None, row_add=None):
+    """[B,R,P] float64: how far a float64 evaluation of `pairwise_mean`'s `out` in another order (other tiles, a running
+    reference instead of the maximum, fused against separately rounded multiply-adds, matrix cores against the vector
+    pipe) may lie from this one, derived and not measured:
+
+        bound[b,r,p] = 2 * pairwise_lse_bound[b,r] * sum_c softmax_c(s[b,r,:])[c] * |payload[b,c,p]|
+
+    out = N / Z with N = sum_c e_c v_c and Z = sum_c e_c.  Let delta = eps * (D + 4) * max_c (|term| + q / 2) bound the
+    move of a score that matters, as in `pairwise_lse_bound`: every e_c moves by the factor exp(+-delta) (plus exp's own
+    few eps and one for the product with v_c, the `+ 8` there), so N moves by at most delta' * sum_c e_c |v_c| and Z by
+    delta' * Z; the C additions of either sum, in any order, move it by at most eps * C times the sum of the magnitudes.
+    Both together are pairwise_lse_bound = eps * ((D + 4) * size + C + 8), once for N — relative to sum_c e_c |v_c| — and
+    once for Z; divided by Z that is twice the bound times sum_c softmax_c |v_c|, to first order.  The payload enters
+    through its magnitude under the row point's own weights, so cancellation in N is covered.  Zero where the result is not
+    finite or the payload under the weights is zero (conventions and exact zeros, held exactly)."""
+    scores = pairwise_lse_bound(rows, cols, scale, col_a, col_sub, row_add)
+    rows, cols, inv, col_a, col_sub, row_add = _pairwise_operands(rows, cols, scale, col_a, col_sub, row_add)
+    B, R = rows.shape[:2]
+    payload = _payload_operand(payload, B, cols.shape[1])
+    bound = np.zeros((B, R, payload.shape[2]), dtype=np.float64)
+    for b in range(B):
+        s, _, _ = _pairwise_scores(rows[b], cols[b], inv, col_a[b], None if col_sub is None else col_sub[b])
+        w, _, _, finite = _softmax_weights(s, np.zeros(R) if row_add is None else row_add[b])
+        held = np.abs(np.where((col_a[b] == -np.inf)[:, None], 0.0, payload[b]))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            size = (w[:, :, None] * held[None, :, :]).sum(axis=1) / w.sum(axis=1)[:, None]
+        bound[b] = np.where(finite[:, None], 2.0 * scores[b][:, None] * np.where(finite[:, None], size, 0.0), 0.0)
+    return bound
+
+
+def two_slice_pass(latents, log_weights, locations, scale, previous=None, following=None, return_tolerance=False):
+    """The whole backward recursion of the two-slice smoother: latents, log_weights, locations, scale as `marginal_pass`
+    takes them; previous / following: None (the latent itself, trailing dims flattened) or callables (time, latent
+    [B,K,...]) -> array [B,K,...], flattened to P and Q values — previous is called with (t, latents[t]), following with
+    (t + 1, latents[t + 1]), once per step.  Returns (expectations, smoothed): T-1 arrays [B,Q,P] and T arrays [B,K], in
+    log_weights' dtype:
+
+        m[j], den[j] = pairwise_mean(x[t+1], loc, scale, log_w[t], previous(t, x[t]))          (one launch)
+        ls[t]        = pairwise_lse(loc, x[t+1], scale, ls[t+1], den, log_w[t])                (one launch: marginal_pass's)
+        E[t][q,p]    = sum_j exp(ls[t+1][j]) following(t+1, x[t+1])[j,q] m[j,p]
+                     = E[following_q(x_{t+1}) previous_p(x_t) | y_0..y_{T-1}]
+
+    every launch rounded to that dtype as the device's launches round theirs, the contraction in float64 and rounded once.
+    `return_tolerance`: also (T-1 x [B,Q,P], T x [B,K]) float64, how far an evaluation that keeps every launch within its
+    bound (and, in float32, within one unit in the last place of the rounding) may lie from this one.  The smoothed
+    log-weights' is `marginal_pass`'s.  The expectations': m[j,p] moves by pairwise_mean_bound plus its last place, the
+    weight exp(ls[t+1][j]) by the factor exp(+-tau_j) with tau the smoothed log-weights' tolerance (to first order tau_j,
+    doubled to cover the second), the K additions and the products by eps * (K + 4) times the sum of the magnitudes, and
+    the result by its last place."""
+    T = len(latents)
+    dtype = np.asarray(log_weights[-1]).dtype
+
+    def last_place(v):      # of the rounding to the dtype: float64 results are not rounded again
+        if dtype == np.float64:
+            return np.zeros(v.shape)
+        return np.where(np.isfinite(v), np.spacing(np.abs(np.where(np.isfinite(v), v, 0)).astype(dtype)), 0).astype(np.float64)
+
+    def feature(function, time, latent):
+        latent = np.asarray(latent)
+        value = latent if function is None else np.asarray(function(time, latent))
+        if value.shape[:2] != latent.shape[:2]:
+            raise ValueError("a feature must be [batch_size, num_particles, ...], got {}".format(value.shape))
+        return value.reshape(value.shape[0], value.shape[1], -1)
+
+    smoothed, tolerance = [None] * T, [None] * T
+    expectations, expectation_tolerance = [None] * (T - 1), [None] * (T - 1)
+    log_w = np.asarray(log_weights[-1]).astype(np.float64)
+    top = log_w.max(axis=1, keepdims=True)
+    lse = top + np.log(np.exp(log_w - top).sum(axis=1, keepdims=True))
+    smoothed[-1] = (log_w - lse).astype(dtype)
+    tolerance[-1] = 4.0 * float(np.finfo(dtype).eps) * (np.abs(lse) + np.abs(log_w - lse))
+    for t in range(T - 2, -1, -1):
+        loc, nxt, log_w = locations(t), latents[t + 1], log_weights[t]
+        f = feature(previous, t, latents[t]).astype(dtype)
+        g = feature(following, t + 1, nxt).astype(np.float64)
+        mean, den, _ = pairwise_mean(nxt, loc, scale, log_w, f)
+        mean, den = mean.astype(dtype), den.astype(dtype)
+        out = pairwise_lse(loc, nxt, scale, smoothed[t + 1], den, log_w)[0].astype(dtype)
+        smoothed[t] = out
+        den_tolerance = pairwise_lse_bound(nxt, loc, scale, log_w) + last_place(den)
+        tolerance[t] = (tolerance[t + 1].max(axis=1, keepdims=True) + den_tolerance.max(axis=1, keepdims=True) +
+                        pairwise_lse_bound(loc, nxt, scale, smoothed[t + 1], den, log_w) + last_place(out))
+        weight = np.exp(smoothed[t + 1].astype(np.float64))
+        m64 = mean.astype(np.float64)
+        value = np.einsum("bj,bjq,bjp->bqp", weight, g, m64)
+        expectations[t] = value.astype(dtype)
+        mean_tolerance = pairwise_mean_bound(nxt, loc, scale, log_w, f) + last_place(mean)
+        tau = tolerance[t + 1]
+        moved = mean_tolerance + np.abs(m64) * (2.0 * tau * (1.0 + tau) + (nxt.shape[1] + 4) * EPSILON)[:, :, None]
+        expectation_tolerance[t] = np.einsum("bj,bjq,bjp->bqp", weight, np.abs(g), moved) + last_place(value)
+    if return_tolerance:
+        return expectations, smoothed, (expectation_tolerance, tolerance)
+    return expectations, smoothed

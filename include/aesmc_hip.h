@@ -62,7 +62,8 @@ extern "C" {
  *                log-weight in one launch).
  *                Additive since, version unchanged: aesmc_resample_step_stratified (K2's stratified sibling: one uniform
  *                per particle); aesmc_backward_sample (K21: one step of backward simulation, FFBS);
- *                aesmc_pairwise_lse (K22: the pairwise log-sum-exp of the marginal smoother, FFBSm).
+ *                aesmc_pairwise_lse (K22: the pairwise log-sum-exp of the marginal smoother, FFBSm);
+ *                aesmc_pairwise_mean (K23: the pairwise softmax mean of the two-slice smoother).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -356,6 +357,41 @@ int aesmc_backward_sample(int dtype, const void *log_w, const aesmc_view3 *loc, 
 int aesmc_pairwise_lse(int dtype, const aesmc_view3 *rows, const aesmc_view3 *cols, const void *scale,
                        int64_t scale_stride, const void *col_a, const void *col_sub, const void *row_add, void *out,
                        int32_t *flags, int64_t B, int64_t R, int64_t C, int64_t D, void *stream);
+
+/* K23 — a pairwise Gaussian softmax mean: the building block of the two-slice particle smoother, which gives
+ * E[g(x_{t+1}) f(x_t)^T | y_0..y_{T-1}] (the lag-one cross moment of an EM M-step, the statistic of a Fisher-identity
+ * score) from the particles the filter stored.  The reference has no such call site.  With K22's operands and scores
+ * s[r,c] (above), for every batch row b and row point r:
+ *   out[b,r,p] = sum_c softmax_c(s[r,:])[c] * payload[b,c,p]
+ *   lse[b,r]   = what aesmc_pairwise_lse writes for the same operands, bit for bit
+ *   payload  T [B,C,P] view               `stride_k` steps along c, `stride_d` along p
+ *   out      T [B,R,P] dense
+ *   lse_out  T [B,R] dense or NULL
+ * One backward step of the two-slice smoother is one launch of K23 (rows = the particles of step t+1, cols = the
+ * transition's locations of step t's particles, col_a = log_w_t, payload = f(x_t): m[j] = the mean of f under the backward
+ * kernel of particle j, lse = the denominators den[j]), one of K22 (the smoothed log-weights of step t, as above) and
+ * the contraction sum_j w[t+1|T][j] g(x[t+1][j]) m[j]^T, which is the caller's.
+ * All arithmetic is in float64 whatever T is, with K2's float64 exp of a non-positive number:
+ *   e[r,c]     = exp(s[r,c] - smax[r]),   payload0[c,p] = col_a[b,c] == -inf ? 0 : (double)payload[b,c,p]
+ *   out[b,r,p] = (T)( (sum_c e[r,c] * payload0[c,p]) / (sum_c e[r,c]) )
+ * ONE rounding to T, at the end.  The order of the sums over c and the reference value the exponentials are taken against
+ * while the maximum is not yet known are the kernel's: the result lies within
+ *   2 * lse_bound[b,r] * sum_c softmax_c(s[r,:])[c] * |payload0[c,p]|        (lse_bound: K22's, above)
+ * of the exact value (aesmc_amd/testing/smoothing.py: pairwise_mean_bound), before the rounding to T.
+ * Special values, per (b, r); row points and batch rows never affect one another:
+ *   an absent column (col_a == -inf) never reaches a result whatever its payload holds (NaN, inf): it is selected out,
+ *        not multiplied by zero.  The payload of a PRESENT column must be finite;
+ *   a NaN among s[r,:] or in row_add[b,r]: AESMC_FLAG_NAN_LOG_WEIGHT, out[b,r,:] = NaN and lse = NaN;
+ *   else smax[r] == +inf: AESMC_FLAG_DEGENERATE_ROW, lse = +inf and out[b,r,:] = NaN (no weights to average with);
+ *   else smax[r] == -inf: out[b,r,:] = 0, lse = -inf and NO flag — a point of zero weight.
+ * No workspace.  D above 256, P above 256 or R, C above 2^30 - 1 return AESMC_ERR_UNSUPPORTED and launch nothing; P < 1
+ * and a NULL payload / out are AESMC_ERR_INVALID_ARGUMENT; B R == 0 is a no-op; C == 0 with row points to average for is
+ * AESMC_ERR_INVALID_ARGUMENT.  Every check runs before any launch.
+ */
+int aesmc_pairwise_mean(int dtype, const aesmc_view3 *rows, const aesmc_view3 *cols, const void *scale,
+                        int64_t scale_stride, const void *col_a, const void *col_sub, const void *row_add,
+                        const aesmc_view3 *payload, void *out, void *lse_out, int32_t *flags, int64_t B, int64_t R,
+                        int64_t C, int64_t D, int64_t P, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
