@@ -2100,6 +2100,54 @@ class HipKernels:
                      tuple(keep) + (col_a, col_sub, row_add, payload, out, lse) + tuple(views))
         return out, lse
 
+    # ---- K24 -----------------------------------------------------------------------------------
+    PAIRWISE_ARGMAX_MAX_DIM = 256
+
+    @staticmethod
+    def pairwise_argmax_covers(rows, cols, scale, col_a, col_sub=None, row_add=None):
+        """Whether `pairwise_argmax` takes these operands: what `pairwise_lse_covers` takes."""
+        return HipKernels.pairwise_lse_covers(rows, cols, scale, col_a, col_sub, row_add)
+
+    def pairwise_argmax(self, rows, cols, scale, col_a, col_sub=None, row_add=None):
+        """The pairwise Gaussian max and argmax (aesmc_pairwise_argmax, K24), with s[b,r,c] the score `pairwise_lse` sums:
+            out[b,r] = row_add[b,r] + max_c s[b,r,c]          arg[b,r] = the smallest c that attains the maximum
+        Operands as `pairwise_lse` takes them.  Returns (out [B,R] in col_a's dtype, arg int64 [B,R]); arg == C: no column
+        (a NaN, a +inf or an all -inf row point).  Views are taken as they are (element strides)."""
+        tag = self._rows_operand(col_a, "col_a")
+        if not self.pairwise_argmax_covers(rows, cols, scale, col_a, col_sub, row_add):
+            raise ValueError("aesmc_amd: pairwise_argmax does not take these operands (see pairwise_argmax_covers)")
+        B, C = col_a.shape
+        R = rows.size(1)
+        for t in (rows, cols, col_sub, row_add):
+            if t is not None:
+                _require_hip(t, "pairwise operand")
+        col_a = col_a.contiguous()
+        col_sub = None if col_sub is None else col_sub.contiguous()
+        row_add = None if row_add is None else row_add.contiguous()
+        out = torch.empty((B, R), dtype=col_a.dtype, device=col_a.device)
+        arg = torch.empty((B, R), dtype=torch.int64, device=col_a.device)
+        if out.numel() == 0:
+            return out, arg
+        views, keep, D, scale_stride = [None, None], [rows, cols], 0, 0
+        if all(size > 0 for size in rows.shape[2:]):
+            (rows, sr, D), (cols, sc, _) = self._view3(rows), self._view3(cols)
+            _require_hip(scale, "scale")
+            scale = scale.reshape(-1).contiguous()
+            scale_stride = 0 if scale.numel() == 1 else 1
+            views = [_lib.View3(_ptr(rows), *sr), _lib.View3(_ptr(cols), *sc)]
+            keep = [rows, cols, scale]
+        esz = col_a.element_size()
+        refs = [ctypes.byref(v) if v is not None else None for v in views]
+        self._launch(col_a.device, self._lib.aesmc_pairwise_argmax,
+                     (tag, refs[0], refs[1], _ptr(scale) if D else 0, scale_stride, _ptr(col_a), _ptr(col_sub),
+                      _ptr(row_add), _ptr(out), _ptr(arg), _ptr(self.flags(col_a.device)), B, R, C, D,
+                      self._stream(col_a)),
+                     lambda: B * esz * ((R + C) * D + C * (2 if col_sub is not None else 1) +
+                                        R * (2 if row_add is not None else 1)) + 8 * B * R,
+                     tuple(keep) + (col_a, col_sub, row_add, out, arg) + tuple(views))
+        return out, arg
+
+
 
 _provider = None
 _provider_lock = threading.Lock()

@@ -1,5 +1,5 @@
 """Smoothing from the particles an SMC run has already stored: p(x_0..x_{T-1} | y_0..y_{T-1}) instead of the filter's
-p(x_t | y_0..y_t).  Three smoothers, all over `infer(..., return_original_latents=True, return_log_weights=True)`:
+p(x_t | y_0..y_t).  Four smoothers, all over `infer(..., return_original_latents=True, return_log_weights=True)`:
 
 `backward_simulate` / `smooth` — forward filtering / backward SIMULATION (FFBS; Godsill, Doucet & West 2004): M equally
     weighted draws from the JOINT smoothing distribution.  O(M K) pairs per step; use it when whole trajectories are
@@ -19,6 +19,13 @@ p(x_t | y_0..y_t).  Three smoothers, all over `infer(..., return_original_latent
     E[x_{t+1} x_t^T] of an EM M-step for the transition, the statistic of a Fisher-identity score, any smoothed additive
     functional (examples/lgssm_em.py).  O(K^2) pairs per step, twice, like the marginal smoother
     (profiles/ffbsm_pairwise_mean.txt).
+`map_trajectory` / `map_smooth` — the MAP sequence estimate (Godsill, Doucet & West 2001): the single most probable path
+    through the stored particles, argmax over all K^T of them of p(x_0..x_{T-1}, y_0..y_{T-1}), by a Viterbi (max-product)
+    recursion, and that path's joint log-density.  Use it when ONE trajectory is wanted that is itself probable — on a
+    multimodal posterior the smoothed means are near no probable path, and the best genealogy line or the best of M
+    backward-simulated paths searches K or M of the K^T.  It needs the particles only, NO `log_weights`: the filter's
+    weights answer "how much mass", this asks "which path", from the model's densities alone.  O(K^2) pairs per step,
+    once, deterministic (profiles/map_pairwise_argmax.txt).
 
 The smoothed posterior `infer(..., return_latents=True)` gives is the genealogy (`inference.get_resampled_latents`): every
 final particle traced back through the ancestor indices.  Over a long sequence the genealogy collapses — after a hundred
@@ -42,7 +49,12 @@ of size [K,K] stored): the denominators, then the weights.  The two-slice weight
 
 m[j] is the mean of a payload under the backward kernel of particle j — the pass that forms den[j], carrying a vector per
 column: kernel K23 (`aesmc_pairwise_mean`, O(B K^2 (D + P)), nothing of size [K,K] stored) in place of the first of K22's
-two launches, den[j] being its normaliser.
+two launches, den[j] being its normaliser.  The MAP trajectory maximises where the marginal smoother sums:
+
+    delta[t][j] = log g(y_t | x[t][j]) + max_i ( delta[t-1][i] + log f(x[t][j] | x[t-1][i]) )
+
+one launch of kernel K24 per step (`aesmc_pairwise_argmax`: K22's scores, their maximum and its smallest column, O(B K^2 D),
+nothing of size [K,K] stored), forwards in time, then a walk back along the stored arguments.
 
 The reference has no counterpart; this module adds to its interface and changes none of it.
 """
@@ -57,6 +69,7 @@ from . import state
 from .linear_gaussian import AffineNormal
 
 MAX_LATENT_DIM = 256
+_LOG_2PI = 1.8378770664093453      # log(2 pi)
 _COVERED = ("covered: a transition that returns an AffineNormal or a torch.distributions.Normal in FULLY_EXPANDED "
             "batch-shape mode, its location shaped like the latent [batch_size, num_particles, ...] with at most {} "
             "values per particle, its scale one value or one per latent dimension (not varying over batch or "
@@ -351,3 +364,114 @@ def two_slice_smooth(observations, initial, transition, emission, proposal, num_
     expectations, smoothed = two_slice_expectation(out["original_latents"], out["log_weights"], transition,
                                                    observations=observations, previous=previous, following=following)
     return out["original_latents"], smoothed, expectations, out["log_marginal_likelihood"]
+
+
+def map_trajectory(latents, initial, transition, emission, observations, return_indices=False):
+    """The MAP sequence estimate over the particles of one SMC run (the particle Viterbi recursion of Godsill, Doucet &
+    West 2001): of all K^T paths through the stored particles, the one of largest joint density p(x_0..x_{T-1},
+    y_0..y_{T-1}).
+
+    latents: what `infer("smc", ..., return_original_latents=True)` returned as `original_latents` — T tensors
+        [batch_size, num_particles, ...] (the particles as drawn, before resampling); the steps may hold different
+        numbers of particles.  No log-weights are needed.
+    initial, transition, emission: the model's callables, each called ONCE per step on plain detached tensors, forwards
+        in time: `initial()` once; `emission(latents=latents[:t+1], time=t, previous_observations=observations[:t])` for
+        t = 0 ... T-1, without the `previous_observations` keyword at t = 0 — exactly how `infer` calls it; and
+        `transition(previous_latents=latents[:t+1], time=t+1, previous_observations=observations[:t+1])` for t = 0 ...
+        T-2, as the other smoothers call it.  MARKOV MODELS ONLY: `previous_latents[-1]` must be all of the latents the
+        transition reads, and `latents[-1]` all the emission reads.
+    observations: length-T sequence of [batch_size, ...] tensors.
+    return_indices: also return which stored particle the path passes through, T int64 tensors [batch_size].
+
+    Returns (trajectory, log_joint): T tensors [batch_size, ...] gathered from `latents` (the stored values exactly,
+    detached), and [batch_size] in the latents' dtype, log p(x*_{0..T-1}, y_{0..T-1}) of that path with the transition's
+    normalising constant included.  With `return_indices`: (trajectory, log_joint, indices).  Ties go to the smallest
+    particle index.
+
+    The transition is covered and refused as in `backward_simulate`.  The initial and emission log-densities go through
+    `state.log_prob` (with `state.expand_observation`), O(batch_size num_particles) per step: any distribution
+    `state.log_prob` takes is covered, the emission need not be Normal.  The recursion is carried in FLOAT64 whatever the
+    latents' dtype (the per-step operands are upcast: O(batch_size num_particles D) memory beside O(batch_size
+    num_particles^2 D) work) — with float32 deltas the rounding would be of the size of real gaps between candidate paths,
+    and the path would depend on it.  T - 1 launches of kernel K24, one more without a distance term for the final
+    maximum, T - 1 gathers for the walk back.  Deterministic: no random stream is consumed, and batch rows are
+    independent, so it works unchanged inside `distributed.shard_scope`.
+
+    NaN densities, particles or locations raise FloatingPointError, a density of +inf RuntimeError, a batch row whose
+    best path has log_joint == -inf (no path of positive density) RuntimeError — read once, at the end (one
+    synchronisation per call).  Not capturable into a hipGraph."""
+    num_timesteps = len(latents)
+    if num_timesteps == 0 or len(observations) != num_timesteps:
+        raise ValueError("map_trajectory: latents and observations must be equally long and not empty, got {} and {}"
+                         .format(num_timesteps, len(observations)))
+    if any(isinstance(latent, dict) for latent in latents):
+        _refuse("dict latents")
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            latents = [_lazy.real(latent).detach() for latent in latents]
+            first = latents[0]
+            batch_size, dtype, wide = first.shape[0], first.dtype, torch.float64
+
+            def density(distribution, value, num_particles):      # [batch_size, num_particles] float64
+                return _lazy.real(state.log_prob(distribution, value)).detach().expand(batch_size, num_particles).to(wide)
+
+            def emission_term(time):
+                history = latents[:time + 1]
+                if time == 0:
+                    distribution = emission(latents=history, time=0)
+                else:
+                    distribution = emission(latents=history, time=time, previous_observations=observations[:time])
+                num_particles = latents[time].shape[1]
+                return density(distribution, state.expand_observation(observations[time], num_particles), num_particles)
+
+            delta = density(initial(), first, first.shape[1]) + emission_term(0)
+            arguments = [None] * num_timesteps
+            for time in range(1, num_timesteps):
+                distribution = transition(previous_latents=latents[:time], time=time,
+                                          previous_observations=observations[:time])
+                loc, scale = _transition_terms(distribution, latents[time - 1])
+                current = latents[time]
+                if current.dim() != loc.dim() or tuple(current.shape[2:]) != tuple(loc.shape[2:]) or \
+                        current.dtype != dtype:
+                    _refuse("latents of shape {} {} after latents of shape {} {}".format(
+                        tuple(current.shape), current.dtype, tuple(loc.shape), dtype))
+                dim = 1
+                for size in current.shape[2:]:
+                    dim *= size
+                scale = scale.to(wide)
+                # the transition's normalising constant: - sum_d log scale[d] - D/2 log(2 pi), a 0-dim tensor
+                constant = -(torch.log(scale).sum() * (dim // scale.numel())) - 0.5 * dim * _LOG_2PI
+                delta, arguments[time] = provider.pairwise_argmax(current.to(wide), loc.to(wide), scale, delta,
+                                                                  row_add=emission_term(time) + constant)
+            nothing = delta.new_empty((batch_size, 1, 0))
+            best, last = provider.pairwise_argmax(nothing, delta.new_empty(delta.shape + (0,)), None, delta)
+            log_joint = best[:, 0]
+            rows = torch.arange(batch_size, device=delta.device)
+            indices, trajectory = [None] * num_timesteps, [None] * num_timesteps
+            index = last[:, 0].clamp(max=delta.shape[1] - 1)      # ("no column" is clamped, never dereferenced)
+            for time in range(num_timesteps - 1, -1, -1):
+                indices[time], trajectory[time] = index, latents[time][rows, index]
+                if time > 0:
+                    index = arguments[time].gather(1, index.unsqueeze(1)).squeeze(1).clamp(max=latents[time - 1].shape[1] - 1)
+            inference._raise_for_flags(provider.read_flags(delta.device))
+            if bool((log_joint == -float("inf")).any()):          # (after the one synchronisation: nothing is pending)
+                raise RuntimeError("map_trajectory: no path of positive density through the stored particles (log_joint "
+                                   "== -inf) in batch row(s) {}".format(
+                                       torch.nonzero(log_joint == -float("inf")).reshape(-1).tolist()))
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    log_joint = log_joint.to(dtype)
+    return (trajectory, log_joint, indices) if return_indices else (trajectory, log_joint)
+
+
+def map_smooth(observations, initial, transition, emission, proposal, num_particles, resampling=None):
+    """Runs the SMC filter (`inference.infer("smc", ...)` with the other smoothers' settings, keeping the particles as
+    drawn) and then `map_trajectory` over what it stored.  Returns (trajectory, log_joint, log_marginal_likelihood): T
+    tensors [batch_size, ...], the path's joint log-density [batch_size] and the filter's [batch_size] estimate."""
+    out = inference.infer("smc", observations, initial, transition, emission, proposal, num_particles,
+                          return_log_marginal_likelihood=True, return_latents=False, return_original_latents=True,
+                          return_log_weight=False, return_log_weights=True, resampling=resampling)
+    trajectory, log_joint = map_trajectory(out["original_latents"], initial, transition, emission, observations)
+    return trajectory, log_joint, out["log_marginal_likelihood"]

@@ -3,7 +3,9 @@ written without regard to the kernel's structure (no tiles, no chunks, no passes
 exactly — and of the whole backward pass that `aesmc_amd.smoothing.backward_simulate` makes of it.  Below it the same
 for the marginal smoother: the pairwise log-sum-exp (aesmc_pairwise_lse), the bound its kernel is held to, and the
 backward recursion that `aesmc_amd.smoothing.marginal_log_weights` makes of it; and for the two-slice smoother: the
-pairwise softmax mean (aesmc_pairwise_mean), its bound, and the recursion of `aesmc_amd.smoothing.two_slice_expectation`.
+pairwise softmax mean (aesmc_pairwise_mean), its bound, and the recursion of `aesmc_amd.smoothing.two_slice_expectation`;
+and for the MAP trajectory: the pairwise max and argmax (aesmc_pairwise_argmax), its bound, and the Viterbi recursion of
+`aesmc_amd.smoothing.map_trajectory`.
 
 One backward step of forward filtering / backward simulation (Godsill, Doucet & West 2004): trajectory m, whose state at
 t+1 is target[b,m], draws particle k of step t with probability proportional to
@@ -370,3 +372,167 @@ def two_slice_pass(latents, log_weights, locations, scale, previous=None, follow
     if return_tolerance:
         return expectations, smoothed, (expectation_tolerance, tolerance)
     return expectations, smoothed
+
+
+# ---- the MAP trajectory (particle Viterbi; Godsill, Doucet & West 2001): the max-plus twin of the marginal smoother ---------
+NEAR_THE_ARGMAX = 1.0      # columns further below a row point's maximum cannot become it by rounding
+
+
+def pairwise_argmax(rows, cols, scale, col_a, col_sub=None, row_add=None):
+    """Operands as `pairwise_lse` takes them -> (out float64 [B,R], arg int64 [B,R], flags):
+
+        s[b,r,c] = term[b,c] - 1/2 sum_d ((rows[b,r,d] - cols[b,c,d]) / scale[d])^2          (term as pairwise_lse forms it)
+        out[b,r] = row_add[b,r] + max_c s[b,r,c]
+        arg[b,r] = the SMALLEST c with s[b,r,c] == max_c s[b,r,c]
+
+    in float64 whatever the operands' dtype is.  Conventions, per row point (row points and batch rows never affect one
+    another); arg == C means "no column":
+      a NaN among the row point's scores or in its row_add: FLAG_NAN_LOG_WEIGHT, out NaN, arg C;
+      else a largest score of +inf: FLAG_DEGENERATE_ROW, out +inf, arg C;
+      else every score -inf: out -inf, arg C and no flag — a point nothing reaches."""
+    rows, cols, inv, col_a, col_sub, row_add = _pairwise_operands(rows, cols, scale, col_a, col_sub, row_add)
+    B, R = rows.shape[:2]
+    C = cols.shape[1]
+    out = np.empty((B, R), dtype=np.float64)
+    arg = np.empty((B, R), dtype=np.int64)
+    flags = 0
+    for b in range(B):
+        s, _, _ = _pairwise_scores(rows[b], cols[b], inv, col_a[b], None if col_sub is None else col_sub[b])
+        add = np.zeros(R) if row_add is None else row_add[b]
+        nan = np.isnan(s).any(axis=1) | np.isnan(add)
+        held = np.where(np.isnan(s), -np.inf, s)
+        smax, first = held.max(axis=1), held.argmax(axis=1)          # (argmax: the first of equal values)
+        finite = np.isfinite(smax) & ~nan
+        with np.errstate(invalid="ignore"):
+            value = np.where(finite, add + np.where(finite, smax, 0.0), smax)      # +inf and -inf as they are
+        out[b] = np.where(nan, np.nan, value)
+        arg[b] = np.where(finite, first, C)
+        if nan.any():
+            flags |= FLAG_NAN_LOG_WEIGHT
+        if (~nan & (smax == np.inf)).any():
+            flags |= FLAG_DEGENERATE_ROW
+    return out, arg, flags
+
+
+def pairwise_argmax_bound(rows, cols, scale, col_a, col_sub=None, row_add=None):
+    """[B,R] float64: how far a float64 evaluation of `pairwise_argmax`'s `out` in another order (fused against separately
+    rounded multiply-adds, another order of the D additions, a reciprocal scale against a true division) may lie from
+    this one, derived and not measured.  With eps = 2^-52 = 2 u (u the unit roundoff) and D values per point
+
+        bound[b,r] = eps * ( (D + 4) * max_c (|term[b,c]| + q[r,c] / 2)  +  4 )  +  eps * |out[b,r]|
+
+    the maximum over the columns whose score lies within 1 of the row point's largest.  The derivation, to first order,
+    for one score s = term - q / 2 with q = sum_d t_d, t_d = ((r_d - c_d) / scale_d)^2:
+      * term = col_a - col_sub is one float64 subtraction of the same two numbers in every evaluation: no difference;
+      * the D products and D - 1 additions of q cost at most D u q in either of two evaluations, whether a product is
+        rounded before it is added or fused into the addition, and in any order (every partial sum is at most q): the two
+        differ by at most 2 D u q = D eps q, and the score by half of that, D eps q / 2;
+      * the scaled difference is (r_d - c_d) * (1 / scale_d) in one evaluation (two roundings after the subtraction's) and
+        (r_d - c_d) / scale_d in another (one): they differ by at most 3 u relatively, their squares by 6 u = 3 eps, the
+        score by 3 eps q / 2;
+      * the last step, term - q / 2, is one rounding in either evaluation (the halving is exact): eps |s| <= eps (|term| +
+        q / 2) between the two.
+    Together eps ((D + 3) q / 2 + |term| + q / 2) <= eps (D + 4) (|term| + q / 2).  The maximum of scores that each move by at
+    most x moves by at most x, and only columns that can be the maximum of either evaluation count: those within
+    NEAR_THE_ARGMAX = 1 of it, far more than any rounding.  The terms of second order are at most ((D + 4) eps)^2 times
+    the same size: below the `+ 4` eps for every D <= 256 while the size stays under 4 / (260^2 eps) = 2.6e11.  The
+    addition of row_add is one rounding in either evaluation, eps |out| between the two.  No sum over c: no C term.
+    Zero where the result is not finite (those are conventions, held exactly)."""
+    out, _, _ = pairwise_argmax(rows, cols, scale, col_a, col_sub, row_add)
+    rows, cols, inv, col_a, col_sub, row_add = _pairwise_operands(rows, cols, scale, col_a, col_sub, row_add)
+    B, R, D = rows.shape
+    bound = np.zeros((B, R), dtype=np.float64)
+    for b in range(B):
+        s, term, q = _pairwise_scores(rows[b], cols[b], inv, col_a[b], None if col_sub is None else col_sub[b])
+        with np.errstate(invalid="ignore"):
+            smax = np.max(np.where(np.isnan(s), -np.inf, s), axis=1)
+            finite = np.isfinite(smax) & np.isfinite(out[b])
+            near = s >= (smax - NEAR_THE_ARGMAX)[:, None]
+            size = np.where(near, np.abs(term)[None, :] + 0.5 * q, 0.0).max(axis=1)
+        size = np.where(finite, size, 0.0)
+        bound[b] = np.where(finite, EPSILON * ((D + 4) * size + 4 + np.abs(np.where(finite, out[b], 0.0))), 0.0)
+    return bound
+
+
+def pairwise_argmax_gap(rows, cols, scale, col_a, col_sub=None):
+    """[B,R] float64: the winner's score minus the runner-up's (the largest score of any OTHER column; 0 for a tie, +inf
+    with one column or where every other column is absent), NaN where `pairwise_argmax` gives no column.  What decides
+    whether `arg` may be demanded exactly of an evaluation that is held to `pairwise_argmax_bound`: a gap above twice
+    the bound leaves no choice."""
+    _, arg, _ = pairwise_argmax(rows, cols, scale, col_a, col_sub)
+    rows, cols, inv, col_a, col_sub, _ = _pairwise_operands(rows, cols, scale, col_a, col_sub, None)
+    B, R = rows.shape[:2]
+    C = cols.shape[1]
+    gap = np.full((B, R), np.nan)
+    for b in range(B):
+        s, _, _ = _pairwise_scores(rows[b], cols[b], inv, col_a[b], None if col_sub is None else col_sub[b])
+        for r in np.flatnonzero(arg[b] < C):
+            others = np.delete(s[r], arg[b, r])
+            with np.errstate(invalid="ignore"):
+                gap[b, r] = s[r, arg[b, r]] - (others.max() if others.size else -np.inf)
+    return gap
+
+
+def viterbi_pass(latents, initial_log_prob, emission_log_probs, locations, scale, return_tolerance=False):
+    """The whole MAP recursion (max-product over the stored particles), in float64 whatever the operands' dtype is:
+    latents T x [B,K_t,...], initial_log_prob [B,K_0] = log mu(x[0]), emission_log_probs T x [B,K_t] = log g(y_t | x[t]),
+    locations(t) -> the transition's location [B,K_t,...] of step t's stored particles for time t+1, scale one value or
+    one per latent dimension.
+
+        delta[0][i] = log mu(x[0][i]) + log g(y_0 | x[0][i])
+        delta[t][j] = log g(y_t | x[t][j]) + cst + max_i ( delta[t-1][i] - 1/2 |x[t][j] - loc[t-1][i]|^2 )
+        psi[t][j]   = the arg of that max                            (one pairwise_argmax; |.|^2 in units of the scale)
+        cst         = - sum_d log scale[d] - D/2 log(2 pi)
+        i[T-1] = argmax delta[T-1] (the smallest index),   i[t-1] = psi[t][i[t]]
+
+    Returns (indices T x int64 [B], log_joint float64 [B]): the stored particle the most probable path passes through at
+    every step, and log p(x*_{0..T-1}, y_{0..T-1}) of that path = max delta[T-1].  An index equal to the step's particle
+    count means "no path" (log_joint is then not finite).
+    `return_tolerance`: also (tolerance T x [B,K_t] float64, margin [B] float64).  The tolerance says how far an
+    evaluation that keeps every launch within `pairwise_argmax_bound` may lie from this one's delta: max-plus moves by
+    at most the largest move of its terms, so a step's tolerance is the largest of the step before plus its own bound
+    plus what forming its row_add may differ by — four units in the last place of sum_d |log scale[d]| + D/2 log(2 pi)
+    (another log) and of row_add itself; the first step is one addition of the same two numbers (one unit in the last
+    place is granted).  log_joint's is the largest of the last step's.  The margin is the smallest gap between winner
+    and runner-up over the choices that make the path — the final argmax and the psi look-ups ON the best path: while it
+    exceeds twice the largest tolerance, every such evaluation finds the same path."""
+    T = len(latents)
+    wide = lambda v: np.asarray(v).astype(np.float64)
+    x = [wide(latent) for latent in latents]
+    B = x[0].shape[0]
+    D = int(np.prod(x[0].shape[2:], dtype=np.int64))
+    scale64 = np.broadcast_to(wide(scale).reshape(-1), (D,))
+    log_scales, half_log_2pi = np.log(scale64), 0.5 * D * np.log(2.0 * np.pi)
+    cst = -log_scales.sum() - half_log_2pi
+    cst_slack = 4.0 * EPSILON * (np.abs(log_scales).sum() + half_log_2pi)
+
+    delta, psi, tolerance = [None] * T, [None] * T, [None] * T
+    delta[0] = wide(initial_log_prob) + wide(emission_log_probs[0])
+    with np.errstate(invalid="ignore"):
+        tolerance[0] = EPSILON * np.where(np.isfinite(delta[0]), np.abs(delta[0]), 0.0)
+    for t in range(1, T):
+        loc = wide(locations(t - 1))
+        row_add = wide(emission_log_probs[t]) + cst
+        delta[t], psi[t], _ = pairwise_argmax(x[t], loc, scale64, delta[t - 1], None, row_add)
+        own = pairwise_argmax_bound(x[t], loc, scale64, delta[t - 1], None, row_add)
+        with np.errstate(invalid="ignore"):
+            forming = cst_slack + 4.0 * EPSILON * np.where(np.isfinite(row_add), np.abs(row_add), 0.0)
+        tolerance[t] = tolerance[t - 1].max(axis=1, keepdims=True) + own + forming
+    nothing = np.zeros((B, 1, 0))
+    last = delta[-1]
+    log_joint, final, _ = pairwise_argmax(nothing, np.zeros((B, last.shape[1], 0)), None, last)
+    log_joint, final = log_joint[:, 0], final[:, 0]
+    margin = pairwise_argmax_gap(nothing, np.zeros((B, last.shape[1], 0)), None, last)[:, 0]
+    indices = [None] * T
+    indices[-1] = final
+    rows_of = np.arange(B)
+    for t in range(T - 1, 0, -1):
+        at = np.minimum(indices[t], x[t].shape[1] - 1)          # ("no column" is clamped, never dereferenced)
+        previous = psi[t][rows_of, at]
+        indices[t - 1] = np.where(indices[t] < x[t].shape[1], previous, x[t - 1].shape[1])
+        chosen = x[t][rows_of, at][:, None]                     # [B,1,...]: the path's particle of step t
+        gap = pairwise_argmax_gap(chosen, wide(locations(t - 1)), scale64, delta[t - 1])[:, 0]
+        margin = np.minimum(margin, gap)                        # (NaN where there is no path: it stays NaN)
+    if return_tolerance:
+        return indices, log_joint, (tolerance, margin)
+    return indices, log_joint

@@ -63,7 +63,8 @@ extern "C" {
  *                Additive since, version unchanged: aesmc_resample_step_stratified (K2's stratified sibling: one uniform
  *                per particle); aesmc_backward_sample (K21: one step of backward simulation, FFBS);
  *                aesmc_pairwise_lse (K22: the pairwise log-sum-exp of the marginal smoother, FFBSm);
- *                aesmc_pairwise_mean (K23: the pairwise softmax mean of the two-slice smoother).
+ *                aesmc_pairwise_mean (K23: the pairwise softmax mean of the two-slice smoother);
+ *                aesmc_pairwise_argmax (K24: the pairwise max and argmax of the MAP trajectory, particle Viterbi).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -392,6 +393,37 @@ int aesmc_pairwise_mean(int dtype, const aesmc_view3 *rows, const aesmc_view3 *c
                         int64_t scale_stride, const void *col_a, const void *col_sub, const void *row_add,
                         const aesmc_view3 *payload, void *out, void *lse_out, int32_t *flags, int64_t B, int64_t R,
                         int64_t C, int64_t D, int64_t P, void *stream);
+
+/* K24 — a pairwise Gaussian max and argmax: the building block of the MAP trajectory (the particle Viterbi recursion of
+ * Godsill, Doucet & West 2001), which finds the single most probable path through the particles the filter stored.  The
+ * reference has no such call site.  With K22's operands and scores s[r,c] (above: term[c] is -inf where col_a == -inf
+ * whatever col_sub holds, D == 0 means no distance term, all arithmetic in float64 whatever T is), for every batch row b
+ * and row point r:
+ *   out[b,r] = (T)( (double)row_add[b,r] + smax[r] ),   smax[r] = max_c s[r,c]
+ *   arg[b,r] = min{ c : s[r,c] == smax[r] }
+ *   out      T [B,R] dense
+ *   arg      int64 [B,R] dense or NULL    NULL: the maximum only
+ * Ties go to the SMALLEST column index, exactly: every column's score chain is independent of its neighbours, so columns
+ * with identical operands have identical bits.
+ * One step of the recursion is one launch (rows = the particles of step t, cols = the transition's locations of step
+ * t-1's particles, col_a = delta[t-1], row_add = the emission's log-density plus the transition's normalising constant:
+ * out = delta[t], arg = psi[t]); a launch with D == 0 and one row point is the maximum of col_a and its smallest index.
+ * ONE rounding to T, at the end.  The contraction of multiply-adds and the order of the D additions are the kernel's: the
+ * result lies within
+ *   2^-52 * ( (D + 4) * max_c (|term[c]| + q[r,c] / 2) + 4 + |out[b,r]| )     (max over the columns with s[r,c] >= smax[r] - 1)
+ * of the exact value (aesmc_amd/testing/smoothing.py: pairwise_argmax_bound), before the rounding to T.
+ * Special values, per (b, r); row points and batch rows never affect one another; arg == C means "no column" (K21's
+ * convention for idx == K):
+ *   a NaN among s[r,:] (from any operand, `scale` included) or in row_add[b,r]: AESMC_FLAG_NAN_LOG_WEIGHT, out = NaN, arg = C;
+ *   else smax[r] == +inf: AESMC_FLAG_DEGENERATE_ROW, out = +inf, arg = C;
+ *   else smax[r] == -inf (every column absent or infinitely far): out = -inf, arg = C and NO flag.
+ * No workspace; R and C are independent and not bounded by LDS.  D above 256 or R, C above 2^30 - 1 return
+ * AESMC_ERR_UNSUPPORTED and launch nothing; B R == 0 is a no-op; C == 0 with row points to maximise for is
+ * AESMC_ERR_INVALID_ARGUMENT.
+ */
+int aesmc_pairwise_argmax(int dtype, const aesmc_view3 *rows, const aesmc_view3 *cols, const void *scale,
+                          int64_t scale_stride, const void *col_a, const void *col_sub, const void *row_add, void *out,
+                          int64_t *arg, int32_t *flags, int64_t B, int64_t R, int64_t C, int64_t D, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
