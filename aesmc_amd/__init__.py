@@ -50,6 +50,7 @@ else:
 
 from . import inference  # noqa: F401
 from . import losses  # noqa: F401
+from . import marginal_filter  # noqa: F401
 from . import math  # noqa: F401
 from . import settings  # noqa: F401
 from . import smoothing  # noqa: F401

@@ -2147,6 +2147,83 @@ class HipKernels:
                      tuple(keep) + (col_a, col_sub, row_add, out, arg) + tuple(views))
         return out, arg
 
+    # ---- K25 -----------------------------------------------------------------------------------
+    PAIRWISE_PASS_MAX_DIM = 256
+
+    @staticmethod
+    def pairwise_pass_covers(own, others, scale, own_term, other_term, own_gain=None, other_gain=None):
+        """Whether `pairwise_pass` takes these operands: float32 / float64 throughout and all on one device, own [B,N,*]
+        and others [B,M,*] with the same trailing dims of at most 256 values (none: no distance term, scale may be None), at
+        least one other, a scale of one value or one per value, own_term / own_gain [B,N] and other_term / other_gain
+        [B,M]."""
+        if not (torch.is_tensor(own_term) and own_term.dim() == 2 and own_term.dtype in _DTYPE_TAG):
+            return False
+        same = lambda t: torch.is_tensor(t) and t.dtype == own_term.dtype and t.device == own_term.device
+        if not (same(other_term) and other_term.dim() == 2 and other_term.size(0) == own_term.size(0) and
+                other_term.size(1) > 0):
+            return False
+        if not (same(own) and same(others) and own.dim() >= 2 and others.dim() == own.dim() and
+                tuple(own.shape[:2]) == tuple(own_term.shape) and tuple(others.shape[:2]) == tuple(other_term.shape) and
+                tuple(others.shape[2:]) == tuple(own.shape[2:])):
+            return False
+        if own_gain is not None and not (same(own_gain) and tuple(own_gain.shape) == tuple(own_term.shape)):
+            return False
+        if other_gain is not None and not (same(other_gain) and tuple(other_gain.shape) == tuple(other_term.shape)):
+            return False
+        D = 1
+        for size in own.shape[2:]:
+            D *= size
+        if D == 0:
+            return scale is None or same(scale)
+        return D <= HipKernels.PAIRWISE_PASS_MAX_DIM and same(scale) and scale.dim() <= 1 and scale.numel() in (1, D)
+
+    def pairwise_pass(self, own, others, scale, own_term, other_term, own_gain=None, other_gain=None, want_mass=True,
+                      want_pull=True, want_spread=True):
+        """The pairwise Gaussian weighted pass (aesmc_pairwise_pass, K25), the backward of `pairwise_lse`:
+            w[n,m]        = exp(own_term[b,n] + other_term[b,m] - 1/2 sum_d ((own[b,n,d] - others[b,m,d]) / scale[d])^2)
+                            * own_gain[b,n] * other_gain[b,m]
+            mass[b,n]     = sum_m w[n,m]
+            pull[b,n,d]   = sum_m w[n,m] (others[b,m,d] - own[b,n,d]) / scale[d]^2
+            spread[b,n,d] = sum_m w[n,m] ((own[b,n,d] - others[b,m,d]) / scale[d])^2
+        own [B,N,*], others [B,M,*] (trailing dims flattened; a [B,N,0] tensor: no distance term, mass only), scale one
+        value or one per value, own_term / own_gain [B,N], other_term / other_gain [B,M]; a gain of None: 1.  Returns
+        (mass [B,N], pull [B,N,D], spread [B,N,D]) in own_term's dtype, None for what was not wanted.  Views are taken as
+        they are (element strides)."""
+        tag = self._rows_operand(own_term, "own_term")
+        if not self.pairwise_pass_covers(own, others, scale, own_term, other_term, own_gain, other_gain):
+            raise ValueError("aesmc_amd: pairwise_pass does not take these operands (see pairwise_pass_covers)")
+        (B, N), M = own_term.shape, other_term.size(1)
+        for t in (own, others, other_term, own_gain, other_gain):
+            if t is not None:
+                _require_hip(t, "pairwise operand")
+        own_term, other_term = own_term.contiguous(), other_term.contiguous()
+        own_gain = None if own_gain is None else own_gain.contiguous()
+        other_gain = None if other_gain is None else other_gain.contiguous()
+        views, keep, D, scale_stride = [None, None], [own, others], 0, 0
+        if all(size > 0 for size in own.shape[2:]):
+            (own, so, D), (others, st, _) = self._view3(own), self._view3(others)
+            _require_hip(scale, "scale")
+            scale = scale.reshape(-1).contiguous()
+            scale_stride = 0 if scale.numel() == 1 else 1
+            views = [_lib.View3(_ptr(own), *so), _lib.View3(_ptr(others), *st)]
+            keep = [own, others, scale]
+        new = lambda *shape: torch.empty(shape, dtype=own_term.dtype, device=own_term.device)
+        mass = new(B, N) if want_mass else None
+        pull = new(B, N, D) if want_pull else None
+        spread = new(B, N, D) if want_spread else None
+        if B * N == 0 or not (want_mass or (D > 0 and (want_pull or want_spread))):
+            return mass, pull, spread
+        esz = own_term.element_size()
+        refs = [ctypes.byref(v) if v is not None else None for v in views]
+        self._launch(own_term.device, self._lib.aesmc_pairwise_pass,
+                     (tag, refs[0], refs[1], _ptr(scale) if D else 0, scale_stride, _ptr(own_term), _ptr(other_term),
+                      _ptr(own_gain), _ptr(other_gain), _ptr(mass), _ptr(pull) if D else 0, _ptr(spread) if D else 0,
+                      _ptr(self.flags(own_term.device)), B, N, M, D, self._stream(own_term)),
+                     lambda: B * esz * ((N + M) * D + N * (1 if own_gain is None else 2) + M * (1 if other_gain is None else 2) +
+                                        N * ((1 if want_mass else 0) + D * ((1 if want_pull else 0) + (1 if want_spread else 0)))),
+                     tuple(keep) + (own_term, other_term, own_gain, other_gain, mass, pull, spread) + tuple(views))
+        return mass, pull, spread
+
 
 
 _provider = None

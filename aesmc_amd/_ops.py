@@ -430,6 +430,80 @@ def ancestor_index(log_weight, uniforms):
     return _kernels.get().ancestor_index(log_weight.detach(), uniforms)
 
 
+# ---- the pairwise Gaussian log-sum-exp (K22) and its backward (K25) ----------------------------------
+class _PairwiseLse(torch.autograd.Function):
+    """out[b,r] = row_add[b,r] + log sum_c exp(col_a[b,c] - col_sub[b,c] - 1/2 |rows[b,r] - cols[b,c]|^2) (kernel K22; |.|
+    in units of the scale).  The backward is two launches of K25 over the STORED result — L = out - row_add is the
+    normaliser, nothing is recomputed or rescaled — in float64 whatever the operands' dtype is (they are widened: O(B (R +
+    C) D) beside the O(B R C D) of a launch), rounded once:
+        the row points own the columns (own_term = -L, other_term = col_a - col_sub, own_gain = grad):
+            grad_rows = pull, grad_scale[d] = sum_{b,r} spread[b,r,d] / scale[d];
+        the columns own the row points (own_term = col_a - col_sub, other_term = -L, other_gain = grad):
+            grad_col_a = mass, grad_col_sub = -mass, grad_cols = pull;
+        grad_row_add = grad.
+    A side nobody needs is not launched, `spread` is not formed unless the scale needs a gradient.  First order only."""
+
+    @staticmethod
+    def forward(ctx, rows, cols, scale, col_a, col_sub, row_add):
+        out = _kernels.get().pairwise_lse(rows, cols, scale, col_a, col_sub, row_add)
+        ctx.save_for_backward(rows, cols, scale, col_a, col_sub, row_add, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        rows, cols, scale, col_a, col_sub, row_add, out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        k = _kernels.get()
+        wide = lambda t: None if t is None else t.to(torch.float64)
+        minus_inf = -float("inf")
+        has_distance = scale is not None and all(size > 0 for size in rows.shape[2:])
+        L = wide(out) if row_add is None else wide(out) - wide(row_add)
+        term = wide(col_a)
+        if col_sub is not None:      # an absent column stays absent whatever col_sub holds
+            term = torch.where(term == minus_inf, term, term - wide(col_sub))
+        g = wide(grad)
+        grad_rows = grad_cols = grad_scale = grad_a = grad_sub = None
+        need_scale = need[2] and has_distance
+        if has_distance and (need[0] or need_scale):
+            _, pull, spread = k.pairwise_pass(wide(rows), wide(cols), wide(scale), -L, term, own_gain=g, want_mass=False,
+                                              want_pull=need[0], want_spread=need_scale)
+            if need[0]:
+                grad_rows = pull.reshape(rows.shape).to(rows.dtype)
+            if need_scale:
+                total = spread.sum(dim=(0, 1)) / wide(scale).reshape(-1)
+                grad_scale = (total.sum() if scale.numel() == 1 else total).reshape(scale.shape).to(scale.dtype)
+        elif need[0]:
+            grad_rows = torch.zeros_like(rows)
+        need_cols = need[1] and has_distance
+        if need_cols or need[3] or (need[4] and col_sub is not None):
+            # a row point without a finite forward value takes part in no column's sum (it gets zeros in its own)
+            absent_or_minus_l = torch.where(torch.isfinite(L), -L, torch.full_like(L, minus_inf))
+            mass, pull, _ = k.pairwise_pass(wide(cols), wide(rows), wide(scale), term, absent_or_minus_l, other_gain=g,
+                                            want_mass=need[3] or need[4], want_pull=need_cols, want_spread=False)
+            if need_cols:
+                grad_cols = pull.reshape(cols.shape).to(cols.dtype)
+            if need[3]:
+                grad_a = mass.to(col_a.dtype)
+            if need[4] and col_sub is not None:
+                grad_sub = (-mass).to(col_sub.dtype)
+        if need[1] and not has_distance:
+            grad_cols = torch.zeros_like(cols)
+        if need[2] and scale is not None and not has_distance:
+            grad_scale = torch.zeros_like(scale)
+        return grad_rows, grad_cols, grad_scale, grad_a, grad_sub, (grad if need[5] and row_add is not None else None)
+
+
+def pairwise_lse(rows, cols, scale, col_a, col_sub=None, row_add=None):
+    """The pairwise Gaussian log-sum-exp [B,R] (kernel K22; operands as `HipKernels.pairwise_lse` takes them),
+    differentiable in all six operands: the forward is that launch, bit for bit; the backward two launches of K25 plus
+    the reduction for the scale.  First order only: differentiating the backward raises."""
+    operands = (rows, cols, scale, col_a, col_sub, row_add)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands):
+        return _PairwiseLse.apply(*operands)
+    return _kernels.get().pairwise_lse(*[None if t is None else t.detach() for t in operands])
+
+
 # ---- linear-Gaussian particle propagation (K8 / K9 / K10) --------------------------------------------
 
 class _ParticleAffine(torch.autograd.Function):

@@ -324,7 +324,10 @@ def infer(inference_algorithm, observations, initial, transition, emission,
           return_latents=True, return_original_latents=False,
           return_log_weight=True, return_log_weights=False,
           return_ancestral_indices=False, resampling=None):
-    """Runs 'is' or 'smc' inference (aesmc/inference.py:8-193).
+    """Runs 'is' or 'smc' inference (aesmc/inference.py:8-193), or 'mpf': the marginal particle filter
+    (`aesmc_amd.marginal_filter`, no counterpart in the reference — the SMC draw, weighted against the whole predictive
+    mixture; Normal transition and proposal, tensor latents, Markov models, and QUADRATIC in num_particles: meant for
+    hundreds of particles, see that module).
 
     observations: length-T sequence of [batch_size, ...] tensors (or dicts of them).
     initial():                                   -> Distribution (or dict of them)
@@ -359,6 +362,11 @@ def infer(inference_algorithm, observations, initial, transition, emission,
         # (`_syncfree.scope`: distributions the callables build with Python-number parameters / default validate_args
         #  neither copy from the host nor synchronise with it — the reference's own model style, test/models/lgssm.py)
         with state.deferring_draws(), _syncfree.scope():
+            if inference_algorithm == "mpf":      # the marginal particle filter: a loop of its own (quadratic in num_particles)
+                from . import marginal_filter
+                return marginal_filter.run(observations, initial, transition, emission, proposal, num_particles,
+                                           return_log_marginal_likelihood, return_latents, return_original_latents,
+                                           return_log_weight, return_log_weights, return_ancestral_indices, resampling)
             return _infer(inference_algorithm, observations, initial, transition, emission, proposal,
                           num_particles, return_log_marginal_likelihood, return_latents,
                           return_original_latents, return_log_weight, return_log_weights,

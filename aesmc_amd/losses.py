@@ -3,17 +3,20 @@ import torch
 
 from . import inference
 
-_ALGORITHM_TO_INFERENCE = {"iwae": "is", "aesmc": "smc"}
+_ALGORITHM_TO_INFERENCE = {"iwae": "is", "aesmc": "smc", "vmpf": "mpf"}
 
 
 def get_loss(observations, num_particles, algorithm, initial, transition,
              emission, proposal):
     """Negative batch mean of the log-marginal-likelihood estimate: algorithm 'iwae' uses
-    importance sampling, 'aesmc' uses SMC (aesmc/losses.py:5-65).  The callables follow the
-    contract documented at `aesmc_amd.inference.infer`.  Call `.backward()` on the result."""
+    importance sampling, 'aesmc' uses SMC (aesmc/losses.py:5-65); 'vmpf' (no counterpart in the reference) uses the
+    marginal particle filter, `infer("mpf", ...)` — the variational marginal particle filter objective of Lai, Domke &
+    Sheldon 2022: quadratic in num_particles (meant for hundreds), Normal transition and proposal, see
+    `aesmc_amd.marginal_filter`.  The callables follow the contract documented at `aesmc_amd.inference.infer`.  Call
+    `.backward()` on the result."""
     if algorithm not in _ALGORITHM_TO_INFERENCE:
         # the reference falls through to an unbound local here (losses.py:45-50)
-        raise UnboundLocalError("algorithm must be iwae or aesmc. currently = {}".format(algorithm))
+        raise UnboundLocalError("algorithm must be iwae, aesmc or vmpf. currently = {}".format(algorithm))
     result = inference.infer(
         inference_algorithm=_ALGORITHM_TO_INFERENCE[algorithm], observations=observations,
         initial=initial, transition=transition, emission=emission, proposal=proposal,

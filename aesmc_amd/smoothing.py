@@ -80,39 +80,48 @@ def _refuse(what):
     raise NotImplementedError("aesmc_amd.smoothing: {} is not implemented; {}".format(what, _COVERED))
 
 
-def _transition_terms(distribution, latent):
-    """(loc [B,K,...], scale of 1 or D values) of a covered transition distribution over `latent`'s particles."""
+def _normal_terms(distribution, latent, refuse, what="transition", detach=True):
+    """(loc [B,K,...], scale of 1 or D values) of a covered Normal over `latent`'s particles — the recognition this module
+    and `aesmc_amd.marginal_filter` share.  `refuse(text)` raises the caller's NotImplementedError; `what` names the
+    callable in its text; `detach`: the smoothers post-process, the marginal filter differentiates."""
     if isinstance(distribution, dict):
-        _refuse("a dict of transition distributions")
+        refuse("a dict of {} distributions".format(what))
     if type(distribution) not in (AffineNormal, torch.distributions.Normal):
-        _refuse("a transition distribution of type {}".format(type(distribution).__name__))
+        refuse("a {} distribution of type {}".format(what, type(distribution).__name__))
     loc, scale = distribution.loc, distribution.scale      # (an AffineNormal's location: kernel K8, once)
     batch_size, num_particles = latent.shape[:2]
     if state.get_batch_shape_mode(distribution, batch_size, num_particles) != state.BatchShapeMode.FULLY_EXPANDED:
-        _refuse("a transition that is not in FULLY_EXPANDED batch-shape mode")
-    loc = _lazy.real(loc).detach()
+        refuse("a {} that is not in FULLY_EXPANDED batch-shape mode".format(what))
+    loc = _lazy.real(loc)
+    loc = loc.detach() if detach else loc
     if tuple(loc.shape) != tuple(latent.shape) or loc.dtype != latent.dtype:
-        _refuse("a transition location of shape {} {} for latents of shape {} {}".format(
-            tuple(loc.shape), loc.dtype, tuple(latent.shape), latent.dtype))
+        refuse("a {} location of shape {} {} for latents of shape {} {}".format(
+            what, tuple(loc.shape), loc.dtype, tuple(latent.shape), latent.dtype))
     dim = 1
     for size in latent.shape[2:]:
         dim *= size
     if dim > MAX_LATENT_DIM:
-        _refuse("a latent of {} values per particle (D > {})".format(dim, MAX_LATENT_DIM))
-    scale = _lazy.real(scale).detach()
+        refuse("a latent of {} values per particle (D > {})".format(dim, MAX_LATENT_DIM))
+    scale = _lazy.real(scale)
+    scale = scale.detach() if detach else scale
     if tuple(scale.shape) != tuple(latent.shape):
         try:
             scale = scale.expand(latent.shape)
         except RuntimeError:
-            _refuse("a scale of shape {} for latents of shape {}".format(tuple(scale.shape), tuple(latent.shape)))
+            refuse("a scale of shape {} for latents of shape {}".format(tuple(scale.shape), tuple(latent.shape)))
     if any(size != 1 and stride != 0 for size, stride in zip(scale.shape[:2], scale.stride()[:2])):
-        _refuse("a scale that varies over batch or particle (a particle-dependent scale)")
+        refuse("a scale that varies over batch or particle (a particle-dependent scale)")
     per_dim = scale[0, 0]
     if all(size == 1 or stride == 0 for size, stride in zip(per_dim.shape, per_dim.stride())):
         values = per_dim.reshape(-1)[:1]      # one value for the whole latent
     else:
         values = per_dim.reshape(-1)
     return loc, values.to(latent.dtype)
+
+
+def _transition_terms(distribution, latent):
+    """(loc [B,K,...], scale of 1 or D values) of a covered transition distribution over `latent`'s particles."""
+    return _normal_terms(distribution, latent, _refuse)
 
 
 def backward_simulate(latents, log_weights, transition, num_trajectories=None, observations=None, uniforms=None,

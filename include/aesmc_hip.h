@@ -64,7 +64,8 @@ extern "C" {
  *                per particle); aesmc_backward_sample (K21: one step of backward simulation, FFBS);
  *                aesmc_pairwise_lse (K22: the pairwise log-sum-exp of the marginal smoother, FFBSm);
  *                aesmc_pairwise_mean (K23: the pairwise softmax mean of the two-slice smoother);
- *                aesmc_pairwise_argmax (K24: the pairwise max and argmax of the MAP trajectory, particle Viterbi).
+ *                aesmc_pairwise_argmax (K24: the pairwise max and argmax of the MAP trajectory, particle Viterbi);
+ *                aesmc_pairwise_pass (K25: the backward of K22, for the marginal particle filter's objective).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -424,6 +425,57 @@ int aesmc_pairwise_mean(int dtype, const aesmc_view3 *rows, const aesmc_view3 *c
 int aesmc_pairwise_argmax(int dtype, const aesmc_view3 *rows, const aesmc_view3 *cols, const void *scale,
                           int64_t scale_stride, const void *col_a, const void *col_sub, const void *row_add, void *out,
                           int64_t *arg, int32_t *flags, int64_t B, int64_t R, int64_t C, int64_t D, void *stream);
+
+/* K25 — a pairwise Gaussian weighted pass: the backward of K22, and through it of the marginal particle filter's
+ * log-weights (Klaas, de Freitas & Doucet 2005; as a training objective: Lai, Domke & Sheldon 2022).  The reference has no
+ * such call site.  `own` are the points a result belongs to, `others` the points summed over.  For every batch row b and
+ * own point n:
+ *   w[n,m]        = exp( own_term[b,n] + other_term[b,m] - 1/2 sum_d ((own[b,n,d] - others[b,m,d]) / scale[d])^2 )
+ *                   * own_gain[b,n] * other_gain[b,m]
+ *   mass[b,n]     = sum_m w[n,m]
+ *   pull[b,n,d]   = sum_m w[n,m] * (others[b,m,d] - own[b,n,d]) / scale[d]^2
+ *   spread[b,n,d] = sum_m w[n,m] * ((own[b,n,d] - others[b,m,d]) / scale[d])^2
+ *   own         T [B,N,D] view              `stride_k` steps along n
+ *   others      T [B,M,D] view              `stride_k` steps along m
+ *   scale       T, D values                 read with the element stride `scale_stride`: 0 (one value) or 1
+ *   own_term    T [B,N] dense               not finite: the own point gets zeros and no flag
+ *   other_term  T [B,M] dense               -inf: the other is absent
+ *   own_gain    T [B,N] dense or NULL       NULL: 1
+ *   other_gain  T [B,M] dense or NULL       NULL: 1
+ *   mass        T [B,N] dense or NULL
+ *   pull        T [B,N,D] dense or NULL
+ *   spread      T [B,N,D] dense or NULL
+ * With L = out - row_add of a K22 launch, term = col_a - col_sub (-inf where col_a is -inf) and g the gradient arriving at
+ * `out`, K22's backward is two launches.  The row points own the columns (own_term = -L, other_term = term, own_gain = g):
+ * grad_rows = pull, grad_scale[d] = sum_{b,r} spread[b,r,d] / scale[d] (the caller's reduction), mass = g.  The columns own
+ * the row points (own_term = term, other_term = -L, -inf where L is not finite, other_gain = g): grad_col_a = mass,
+ * grad_col_sub = -mass, grad_cols = pull.  grad_row_add = g.  The normaliser is an operand: every exponent of a finite own
+ * point is <= about 0, nothing is rescaled.
+ * T is float32 or float64 (`dtype`); D == 0 (own / others / scale may be NULL) means no distance term and `mass` alone.  All
+ * arithmetic is in float64 whatever T is, the exponent K22's chain (inv[d] = 1 / (double)scale[d], d ascending), the
+ * sums formed from the differences (own - others) * inv, never from raw moments, with K2's float64 exp, and ONE rounding
+ * to T, at the end.  The order of the sums over m and the contraction of multiply-adds are the kernel's: every output
+ * X = sum_m t_m lies within
+ *   2^-52 * ( (D + 4) * max_m (|own_term| + |other_term[m]| + q[n,m] / 2) + M + 16 ) * sum_m |t_m|
+ * (max over the others whose exponent is within 40 of the own point's largest) of the exact value, plus the floor that
+ * float64's gradual underflow below 2^-1022 sets (aesmc_amd/testing/marginal_filter.py: pairwise_pass_bound), before the
+ * rounding to T.
+ * Special values, per (b, n); own points and batch rows never affect one another:
+ *   an absent other (other_term == -inf) never reaches a result whatever it holds (NaN, inf): it is selected out, not
+ *        multiplied by zero.  The coordinates of a PRESENT other and of an own point with a finite own_term are finite or NaN;
+ *   own_term not finite (-inf: an absent column; +inf, NaN: a row point whose forward value was -inf, +inf or NaN, and
+ *        which K22 has flagged where there was something to flag): mass, pull, spread = 0 and NO flag;
+ *   else a NaN or +inf exponent, or a NaN weight, against a present other (a NaN other_term, coordinate, scale or gain):
+ *        AESMC_FLAG_NAN_LOG_WEIGHT, and mass, pull, spread of that own point = NaN.
+ * No workspace, no atomics; N and M are independent and not bounded by LDS.  D above 256 or N, M above 2^30 - 1 return
+ * AESMC_ERR_UNSUPPORTED and launch nothing; NULL terms, no output to write (mass NULL and, for D > 0, pull and spread NULL
+ * too) are AESMC_ERR_INVALID_ARGUMENT; B N == 0 is a no-op; M == 0 with own points to sum for is
+ * AESMC_ERR_INVALID_ARGUMENT.  Every check runs before any launch.
+ */
+int aesmc_pairwise_pass(int dtype, const aesmc_view3 *own, const aesmc_view3 *others, const void *scale,
+                        int64_t scale_stride, const void *own_term, const void *other_term, const void *own_gain,
+                        const void *other_gain, void *mass, void *pull, void *spread, int32_t *flags, int64_t B,
+                        int64_t N, int64_t M, int64_t D, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
