@@ -62,6 +62,66 @@ def _on_device(device):
     return torch.cuda.device(device)
 
 
+class PackedAncestors:
+    """What a resampling step hands to the launches that consume its ancestry INSIDE the library, on the lean route of
+    `infer` (`settings.packed_ancestors`): `words` int32 [B,K] holding aesmc_resample_step_packed's uint32 words — the
+    ancestor index in the low half, where the particle's children end in the high half (`has_ranges`; else 0) — 4 bytes
+    per particle where the int64 indices and int32 ranges are 12.  K16 and K14's rows form read the words as they are;
+    everything else asks for `index()` / `child_end()`: ONE unpack launch (aesmc_unpack_ancestors), memoised — the int64
+    [B,K] tensor `ancestor_index` would have returned (tagged sorted) and the int32 ranges.  Nothing else unpacks: the
+    handle is not a tensor and forwards no tensor attributes.  Three explicit conveniences for a wrapper around the
+    provider's `resample_step` that records or overrides a step's ancestors — `clone()` and `cpu()` (copies of the int64
+    indices) and `copy_()` (the indices overwritten, the words following) — each an unpack, none used by the package."""
+    __slots__ = ("words", "has_ranges", "_idx", "_ends", "_aesmc_sorted")
+
+    def __init__(self, words, has_ranges):
+        self.words, self.has_ranges = words, bool(has_ranges)
+        self._idx = self._ends = None
+        self._aesmc_sorted = True
+
+    shape = property(lambda self: self.words.shape)
+    device = property(lambda self: self.words.device)
+
+    def index(self):
+        if self._idx is None:
+            self._idx, self._ends = get().unpack_ancestors(self.words, self.has_ranges)
+            self._idx._aesmc_sorted = True
+            if self._ends is not None:
+                self._idx._aesmc_child_end = self._ends
+        return self._idx
+
+    def child_end(self):
+        if not self.has_ranges:
+            return None
+        self.index()
+        return self._ends
+
+    def clone(self):
+        return self.index().clone()
+
+    def cpu(self):
+        return self.index().cpu()
+
+    def copy_(self, source):
+        """`Tensor.copy_` on the int64 indices (non-decreasing along the particles, as every resampler's): the words
+        follow, and the ranges — where each particle's children end — are formed again from the new indices."""
+        idx = self.index()
+        idx.copy_(source)
+        wide = idx.clone()
+        if self.has_ranges:
+            B, K = idx.shape
+            position = torch.arange(K, device=idx.device).unsqueeze(0).expand(B, K).contiguous()
+            self._ends.copy_(torch.searchsorted(idx.contiguous(), position, right=True))
+            wide |= self._ends.to(torch.int64) << 16
+        self.words.copy_(torch.where(wide >= 2 ** 31, wide - 2 ** 32, wide))
+        return self
+
+
+def as_index(index):
+    """The int64 ancestor indices behind `index`: a `PackedAncestors` unpacks (once), a tensor is returned as it is."""
+    return index.index() if type(index) is PackedAncestors else index
+
+
 class KernelTimer:
     """Optional per-kernel timing for bench.py's `roofline` leg.  While installed on the provider
     it keeps a bounded random sample of the launches made (the C-ABI entry point with its operands);
@@ -137,6 +197,8 @@ class KernelTimer:
                         idx, dst = keep[1], keep[5]
                         if idx is None:
                             continue
+                        if idx.dtype == torch.int32:      # the packed words: the index is the low half
+                            idx = idx & 0xffff
                         rows = idx.numel()
                         unique = int((idx[:, 1:] != idx[:, :-1]).sum().item()) + idx.size(0)
                         payload = dst.numel() * dst.element_size() / rows
@@ -424,19 +486,50 @@ class HipKernels:
         return all((x * esz) % 4 == 0 for x in (payload.stride(0), payload.stride(1))) and \
             payload.data_ptr() % 4 == 0
 
-    def resample_step(self, log_w, u, payload=None, want_lse=False, want_child_end=False):
+    def step_packs(self, B, K, log_w):
+        """Host-only: does aesmc_resample_step_packed take rows of K particles — whole wavefronts of the lean kernel's
+        particles per lane, and more than 512 particles: exactly where `resample_step` without a payload runs that kernel
+        itself (the header's rule), so the packed and the unpacked step are one kernel body with two output forms."""
+        if not 512 < K <= self.lds_max_particles or B < 1 or log_w.data_ptr() % 16:
+            return False
+        per_lane = 4 if (K <= 4096 and K % 256 == 0) else (4 if K <= 2048 else (8 if K <= 8192 else (16 if K <= 16384 else 32)))
+        return K % (64 * per_lane) == 0 and K // per_lane <= 1024
+
+    def unpack_ancestors(self, words, want_child_end=True):
+        """(idx int64 [B,K], child_end int32 [B,K] or None) of the packed words: one launch (aesmc_unpack_ancestors)."""
+        B, K = words.shape
+        idx = torch.empty((B, K), dtype=torch.int64, device=words.device)
+        ends = torch.empty((B, K), dtype=torch.int32, device=words.device) if want_child_end else None
+        if idx.numel():
+            self._launch(words.device, self._lib.aesmc_unpack_ancestors,
+                         (_ptr(words), _ptr(idx), _ptr(ends), B, K, self._stream(words)),
+                         lambda: B * K * (12 + (4 if ends is not None else 0)), (words, idx, ends), name="unpack_ancestors")
+        return idx, ends
+
+    def resample_step(self, log_w, u, payload=None, want_lse=False, want_child_end=False, packed=False):
         """The fused step: (idx, lse, resampled payload) from one launch — idx as `ancestor_index`,
         lse = logsumexp over particles [B] when `want_lse`, payload[b, idx[b,k]] as `gather` when a
         payload tensor [B,K,...] is given (else None).  Returns None when the launch does not cover
         the operands (more particles than one workgroup holds, payload rows not 4-byte multiples):
         the caller then runs `ancestor_index` / `gather` / `logweight_lse` separately.
         u [B,K] (stratified resampling): the stratified launch, which has no payload tail — `moved` is None whatever
-        payload was offered and the caller gathers with the indices."""
+        payload was offered and the caller gathers with the indices.
+        `packed` (no payload, systematic): where `step_packs` holds, idx comes back as a `PackedAncestors` — the indices
+        and, with `want_child_end`, the ranges in one word per particle."""
         tag, B, K, stratified = self._resampling_operands(log_w, u)
         if K > self.lds_max_particles:
             return None
         log_w = log_w.contiguous()
         u = u.contiguous()
+        if packed and payload is None and not stratified and self.step_packs(B, K, log_w):
+            words = torch.empty((B, K), dtype=torch.int32, device=log_w.device)
+            lse = torch.empty((B,), dtype=log_w.dtype, device=log_w.device) if want_lse else None
+            if self._launch(log_w.device, self._lib.aesmc_resample_step_packed,
+                            (tag, _ptr(log_w), _ptr(u), _ptr(words), _ptr(lse), 1 if want_child_end else 0,
+                             _ptr(self.flags(log_w.device)), B, K, self._stream(log_w)),
+                            lambda: B * K * (log_w.element_size() + 8) + 8 * B + (4 * B * K if want_child_end else 0),
+                            (log_w, u, words, lse, None, None, None), name="resample_step", decline=True):
+                return PackedAncestors(words, want_child_end), lse, None
         if stratified:
             if log_w.numel() == 0:
                 return None
@@ -504,6 +597,7 @@ class HipKernels:
         None."""
         if ancestors is None:
             return None
+        ancestors = as_index(ancestors)
         self._check_index(value, ancestors)
         if ancestors.shape != (B, K):
             raise ValueError("aesmc_amd: {} ancestors must be [{}, {}]".format(what, B, K))
@@ -512,6 +606,7 @@ class HipKernels:
     def gather(self, src, idx):
         """dst[b,k,...] = src[b, idx[b,k], ...]; src [B,K,...] any dtype, idx int64 [B,K]."""
         _require_hip(src, "value")
+        idx = as_index(idx)
         self._check_index(src, idx)
         assert idx.size() == src.size()[:2]
         B, K = idx.shape
@@ -535,6 +630,7 @@ class HipKernels:
         """grad_src[b,j,...] = sum over {k: idx[b,k]==j} of grad_out[b,k,...].  `sorted_index`
         promises idx non-decreasing along k (outputs of `ancestor_index`): segmented sum, no atomics."""
         _require_hip(grad_out, "grad")
+        idx = as_index(idx)
         self._check_index(grad_out, idx)
         tag = _tag(grad_out, "gradient of a resampled value")
         B, K = idx.shape
@@ -559,6 +655,8 @@ class HipKernels:
     def gather_backward_ranges(self, child_grad, child_end):
         """grad_src[b,k] = sum of child_grad[b, child_end[b,k-1] : child_end[b,k]] — torch.gather's backward stated with
         the children ranges instead of the indices (only for shapes the fused backward declines)."""
+        if type(child_end) is PackedAncestors:
+            child_end = child_end.child_end()
         B, K = child_end.shape
         ends = child_end.to(torch.int64)
         position = torch.arange(K, device=child_end.device).unsqueeze(0).expand(B, K).contiguous()
@@ -1264,7 +1362,13 @@ class HipKernels:
         x_src = self._dense16(x_src)
         if out_x.data_ptr() == x_src.data_ptr():
             raise ValueError("aesmc_amd: affine_propagate_drawn cannot write the draw over x_src")
-        ancestors = self._ancestors(x_src, ancestors, B, K, "affine_propagate_drawn")
+        words = None
+        if type(ancestors) is PackedAncestors:      # the item form reads the words as they are (4 B per particle)
+            if ancestors.words.shape != (B, K) or ancestors.words.device != x_src.device:
+                raise ValueError("aesmc_amd: affine_propagate_drawn ancestors must be [{}, {}] on {}".format(B, K, x_src.device))
+            words = ancestors.words
+        else:
+            ancestors = self._ancestors(x_src, ancestors, B, K, "affine_propagate_drawn")
         y_rows = self._unit_rows(y_rows)
         out = torch.empty((B, K), dtype=x_src.dtype, device=x_src.device)
         maps = [self._affine_map(*term, slot=slot) for slot, term in enumerate((transition, emission, proposal))]
@@ -1272,6 +1376,16 @@ class HipKernels:
         if self.WEIGHT_PAIRS and 2 <= dx <= 16:
             pairs = self._weight_pairs(maps, (transition[0], emission[0], proposal[0]), x_src.device,
                                        scales if self.SCALED_PAIRS else None)
+        if words is not None:
+            args = (_ptr(x_src), _ptr(words), _ptr(y_rows), y_rows.stride(0)) + self._map_args(maps, scales) + \
+                (_ptr(out_x), _ptr(out), _ptr(self.flags(x_src.device)), B, K, noise.seed, noise.offset, noise.threads,
+                 _ptr(noise.state), _ptr(pairs), self._stream(x_src))
+            if self._launch(x_src.device, self._lib.aesmc_affine_normal_propagate_drawn_packed, args,
+                            lambda: 4 * (B * K * (2 * dx + 1) + y_rows.numel()) + 8 * B * K,
+                            (x_src, words, None, y_rows, out, out_x, maps, scales, pairs),
+                            name="affine_normal_propagate_drawn", decline=True):
+                return out
+            ancestors = self._ancestors(x_src, ancestors, B, K, "affine_propagate_drawn")      # (another form: the int64 indices)
         args = (_ptr(x_src), _ptr(ancestors), _ptr(y_rows), y_rows.stride(0)) + self._map_args(maps, scales) + \
             (_ptr(out_x), _ptr(out), _ptr(self.flags(x_src.device)), B, K, noise.seed, noise.offset, noise.threads,
              _ptr(noise.state), _ptr(pairs), self._stream(x_src))
@@ -1541,6 +1655,22 @@ class HipKernels:
             chain["left"] = None
             if ancestors is None:
                 raise ValueError("aesmc_amd: affine_step_backward chains the weights' gradients only through ancestors")
+        # `ancestors` / `child_end` as `PackedAncestors` (this step's resampling, the next step's): the rows form of the
+        # kernel reads the words as they are; any other form, and any mix with plain tensors, gets them unpacked
+        words = child_words = None
+        if type(ancestors) is PackedAncestors and (child_grad is None or type(child_end) is PackedAncestors) and \
+                x.dim() == 3 and x.size(2) <= self.affine_max_dim and x.dtype == torch.float32 and \
+                ancestors.words.shape == x.shape[:2] and ancestors.words.device == x.device:
+            words = ancestors.words
+            if child_grad is not None:
+                if child_end.words.shape != x.shape[:2] or child_end.words.device != x.device or not child_end.has_ranges:
+                    raise ValueError("aesmc_amd: affine_step_backward child_end must hold the ranges of [{}, {}] particles on "
+                                     "{}".format(x.size(0), x.size(1), x.device))
+                child_words = child_end.words
+        else:
+            ancestors = as_index(ancestors)
+            if type(child_end) is PackedAncestors:
+                child_end = child_end.child_end()
         if x.dim() == 3 and x.size(2) > self.affine_max_dim:
             if chain is not None or child_grad is not None:
                 raise ValueError("aesmc_amd: a wide step's backward takes the summed gradient (no children ranges, no chain)")
@@ -1575,13 +1705,15 @@ class HipKernels:
                 raise ValueError("aesmc_amd: affine_step_backward folds the children's gradient only through ancestors")
             self._expect(child_grad, (B, K, dx), x, "child_grad")
             child_grad = self._dense16(child_grad)
-            if child_end is None or child_end.shape != (B, K) or child_end.dtype != torch.int32 or \
-                    child_end.device != x.device:
-                raise ValueError("aesmc_amd: affine_step_backward child_end must be int32 [{}, {}] on {}".format(B, K, x.device))
-            child_end = child_end.contiguous()
+            if child_words is None:
+                if child_end is None or child_end.shape != (B, K) or child_end.dtype != torch.int32 or \
+                        child_end.device != x.device:
+                    raise ValueError("aesmc_amd: affine_step_backward child_end must be int32 [{}, {}] on {}".format(B, K, x.device))
+                child_end = child_end.contiguous()
         # `x_prev` is the un-resampled latent when `ancestors` is given: the kernel fetches x_prev[b, ancestors[b,k]]
         # itself and slot 0 of the result is the gradient of those RESAMPLED rows (the caller sums children into ancestors)
-        ancestors = self._ancestors(x_prev, ancestors, B, K, "affine_step_backward")
+        if words is None:
+            ancestors = self._ancestors(x_prev, ancestors, B, K, "affine_step_backward")
         x_prev, x = self._dense16(x_prev), self._dense16(x)
         y_rows = self._unit_rows(y_rows)
         gx_prev = torch.empty((B, K, dx), dtype=x.dtype, device=x.device) if need[0] else None
@@ -1603,6 +1735,24 @@ class HipKernels:
             pairs_in = carry[2] if carry is not None and len(carry) > 2 and carry[2] else 0
             link = _lib.AffineChain(_ptr(carry[0]) if carry is not None else 0, carry[1] if carry is not None else 0,
                                     (2 if (need[9] or need[10] or need[11]) else 1) if defer else 0, 0, pairs_in, 0)
+        esz = x.element_size()
+        if words is not None:
+            args = (tag, _ptr(x_prev), _ptr(words)) + middle + (_ptr(child_grad), _ptr(child_words)) + tail + \
+                (_ptr(self.flags(x.device)), ctypes.byref(link) if link is not None else None, B, K, self._stream(x))
+            if self._launch(x.device, self._lib.aesmc_affine_step_backward_packed, args,
+                            lambda: esz * B * K * (2 * dx + 1 + (dx if grad_x is not None else 0) + (dx if gx_prev is not None else 0)) +
+                            8 * B * K + (esz * B * K * dx + 4 * B * K if child_grad is not None else 0),
+                            (x_prev, words, x, y_rows, lw, lse, grad_lse, grad_lw, grad_x, child_grad, child_words, outs,
+                             ws, maps, scales) + sums + (gx_prev, link, carry), name="affine_step_backward_resampled",
+                            decline=True):
+                if defer:
+                    handed_on = carry is not None and len(carry) > 2 and carry[2] and link.pairs_out == carry[2]
+                    chain["left"] = (ws, int(link.records), link.pairs_out or 0, carry[3] if handed_on else ws)
+                return self._affine_grad_slots(gx_prev, None, sums, need, offsets, scales)
+            # (not a shape of the rows form: the two arrays, one unpack launch per handle, and the entry that takes them)
+            ancestors = self._ancestors(x_prev, ancestors, B, K, "affine_step_backward")
+            if child_grad is not None:
+                child_end = child_end.child_end()
         if ancestors is not None:
             entry = self._lib.aesmc_affine_step_backward_resampled
             args = (tag, _ptr(x_prev), _ptr(ancestors)) + middle + (_ptr(child_grad), _ptr(child_end)) + tail + \
@@ -1610,7 +1760,6 @@ class HipKernels:
         else:
             entry = self._lib.aesmc_affine_step_backward
             args = (tag, _ptr(x_prev)) + middle + tail + (B, K, self._stream(x))
-        esz = x.element_size()
         nbytes = lambda: esz * B * K * (2 * dx + 1 + (dx if grad_x is not None else 0) + (dx if gx_prev is not None else 0)) + \
             (8 * B * K if ancestors is not None else 0) + (esz * B * K * dx + 4 * B * K if child_grad is not None else 0)
         if not self._launch(x.device, entry, args, nbytes,

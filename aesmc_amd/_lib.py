@@ -95,6 +95,13 @@ SIGNATURES = {
                                                      ctypes.POINTER(AffineChain), _i64, _i64, _vp]),
     "aesmc_affine_backward_collect": (_i32, [_i32, _vp, _i32, _i64, _i64, ctypes.POINTER(AffineLogweightGrads), _vp]),
     "aesmc_resample_step_ranges": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "aesmc_resample_step_packed": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _vp]),
+    "aesmc_unpack_ancestors": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    "aesmc_affine_normal_propagate_drawn_packed": (_i32, [_vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
+                                                          _vp, _vp, _i64, _i64, _u64, _u64, _i64, _vp, _vp, _vp]),
+    "aesmc_affine_step_backward_packed": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p] + [_vp] * 10 +
+                                                 [ctypes.POINTER(AffineLogweightGrads), _vp, _sz, _vp,
+                                                  ctypes.POINTER(AffineChain), _i64, _i64, _vp]),
     "aesmc_resample_step_stratified": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp]),
     "aesmc_backward_sample": (_i32, [_i32, _vp, ctypes.POINTER(View3), ctypes.POINTER(View3), _vp, _i64, _vp, _vp,
                                      ctypes.POINTER(View3), _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),

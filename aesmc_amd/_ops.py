@@ -380,9 +380,11 @@ class _ResampleStep(torch.autograd.Function):
         return grad_w, None, grad_payload, None, grad_carrier
 
 
-def resample_step(log_weight, uniforms, payload=None, want_lse=False, pending=None, want_child_end=False):
+def resample_step(log_weight, uniforms, payload=None, want_lse=False, pending=None, want_child_end=False, packed=False):
     """One resampling step: (ancestor indices [B,K], logsumexp over particles [B] or None,
-    payload[b, idx[b,k], ...] or None).  `uniforms` [B]: systematic resampling; [B,K]: stratified (the provider reads
+    payload[b, idx[b,k], ...] or None).  `packed` (the lean route of `infer`: no payload, no autograd node of the step's
+    own): where the packed launch covers the rows, the indices come back as a `_kernels.PackedAncestors` — one word per
+    particle for K16 / K14 to read as it is, `.index()` for everybody else.  `uniforms` [B]: systematic resampling; [B,K]: stratified (the provider reads
     the scheme off the shape; the stratified launch copies no payload: `moved` is None).  One launch when the fused kernel covers the operands;
     `moved` is None when it does not cover the payload (the caller gathers with the indices).
     `pending` (with want_lse): the PendingStep of the step that produced `log_weight` — the log-sum-exp
@@ -395,6 +397,7 @@ def resample_step(log_weight, uniforms, payload=None, want_lse=False, pending=No
     if payload is not None and not k.step_covers(log_weight, payload):
         payload = None
     bind = pending is not None and want_lse and torch.is_grad_enabled()
+    packs = {"packed": True} if (packed and payload is None and k.name == "hip") else {}      # (the product provider's own hand-off)
     wants_grad = torch.is_grad_enabled() and (
         (want_lse and log_weight.requires_grad and not bind) or
         (payload is not None and payload.requires_grad and payload.is_floating_point()))
@@ -402,7 +405,7 @@ def resample_step(log_weight, uniforms, payload=None, want_lse=False, pending=No
         # the log-sum-exp belongs to a step node: no autograd node here at all — `infer` ties the VALUE to the
         # node's carrier once, for all timesteps together (bind_rows)
         idx, lse, moved = k.resample_step(log_weight.detach(), uniforms, None if payload is None else payload.detach(),
-                                          want_lse, want_child_end=want_child_end)
+                                          want_lse, want_child_end=want_child_end, **packs)
         pending.box[0] = lse
         lse = LseOf(lse, pending)
     elif wants_grad and bind:
@@ -412,7 +415,7 @@ def resample_step(log_weight, uniforms, payload=None, want_lse=False, pending=No
         idx, lse, moved = _ResampleStep.apply(log_weight, uniforms, payload, want_lse)
     else:
         idx, lse, moved = k.resample_step(log_weight.detach(), uniforms,
-                                          None if payload is None else payload.detach(), want_lse)
+                                          None if payload is None else payload.detach(), want_lse, **packs)
         if pending is not None and lse is not None:
             lse = pending.bind(lse)
     idx._aesmc_sorted = True
@@ -420,6 +423,7 @@ def resample_step(log_weight, uniforms, payload=None, want_lse=False, pending=No
 
 
 def resample_gather(value, idx):
+    idx = _kernels.as_index(idx)
     if torch.is_grad_enabled() and value.requires_grad and value.is_floating_point():
         return _ResampleGather.apply(value, idx)
     return _kernels.get().gather(value, idx)
@@ -858,6 +862,9 @@ class _AffineStep(torch.autograd.Function):
         ctx.lse_box = pending.box
         ctx.own_link, ctx.parent_link, ctx.defer_shared = links
         child_end = None if ctx.parent_link is None else ctx.parent_link[1]
+        # (packed ancestry — `_kernels.PackedAncestors` — is saved as its words and wrapped again in backward)
+        ctx.packed = tuple((type(h) is _kernels.PackedAncestors, getattr(h, "has_ranges", False)) for h in (ancestors, child_end))
+        ancestors, child_end = [h.words if type(h) is _kernels.PackedAncestors else h for h in (ancestors, child_end)]
         ctx.save_for_backward(lw, x_value, ancestors, child_end, *[t for t in operands if t is not None])
         ctx.present = [t is not None for t in operands]
         return lw.new_empty((lw.size(0),)), x_value.view_as(x_value)     # the carrier's values are never read
@@ -865,6 +872,10 @@ class _AffineStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_lse, grad_x):
         lw, x_value, ancestors, parent_child_end = ctx.saved_tensors[:4]
+        if ctx.packed[0][0]:
+            ancestors = _kernels.PackedAncestors(ancestors, ctx.packed[0][1])
+        if ctx.packed[1][0]:
+            parent_child_end = _kernels.PackedAncestors(parent_child_end, ctx.packed[1][1])
         saved = iter(ctx.saved_tensors[4:])
         operands = [next(saved) if present else None for present in ctx.present]
         x_prev, _, y_rows, A, off_p, C, off_g, Q, off_q, s_p, s_g, s_q = operands
@@ -935,7 +946,10 @@ def affine_step(lw, operands, fold_gather_backward=False):
         own_link = StepLink(shared)
         if ancestors is not None:
             previous = getattr(inputs[0], "_aesmc_step_link", None)      # x_{t-1} is the previous step's output
-            child_end = getattr(ancestors, "_aesmc_child_end", None)
+            if type(ancestors) is _kernels.PackedAncestors:
+                child_end = ancestors if ancestors.has_ranges else None      # (the ranges are the high halves of the same words)
+            else:
+                child_end = getattr(ancestors, "_aesmc_child_end", None)
             if previous is not None and child_end is not None:
                 parent_link = (previous, child_end)
                 defer_shared = _CHAIN_SHARED and previous.shared is not None and torch.is_grad_enabled() and \

@@ -429,7 +429,12 @@ __device__ __forceinline__ double exp_nonpositive_s(double x, const ExpScalars &
 //  registers the loop's live state spilt 72 of them (31 - 33 us); as a kernel of its own at 107 registers, two workgroups
 //  per CU: 21.9 / 26.4 / 25.5 us for 2 / 3 / 4 rows per workgroup against 20.2 at B = 1024, 39.8 against 36.7 at B = 2048 —
 //  where two rounds of the plain kernel already overlap by themselves (0.46 of HBM): profiles/r05_k2_row_walk.txt.)
-template <typename T, int C>
+// PACKED: the hand-off to the launches that consume a step's ancestry inside the library (K16's gather, K14's rows form) —
+// ONE 32-bit word per particle, idx | child_end << 16 (the format holds K <= 65535; this kernel's rows end at
+// kInvMaxParticles = 32768, so both halves fit with room), at `out_idx` (read as uint32
+// words) in place of 8 + 4 bytes in two arrays; a non-null `out_child_end` then only says that the ranges are wanted (the
+// high halves are 0 otherwise) and is never written through.  The ranges stay in registers until the one store at the end.
+template <typename T, int C, bool PACKED = false>
 __global__ __launch_bounds__(kMaxThreads, C > 8 ? 1 : 8) void ancestor_index_rows_kernel(
     const T *__restrict__ log_w, const double *__restrict__ u, int64_t *__restrict__ out_idx, int32_t *flags, int K,
     T *__restrict__ out_lse, int32_t *__restrict__ out_child_end) {
@@ -445,7 +450,8 @@ __global__ __launch_bounds__(kMaxThreads, C > 8 ? 1 : 8) void ancestor_index_row
   const int nwaves = nt >> 6;
   const int64_t row = blockIdx.x;
   const T *lw = log_w + row * (int64_t)K;
-  int64_t *idx = out_idx + row * (int64_t)K;
+  int64_t *idx = out_idx + row * (int64_t)K;                                               // (PACKED: unused)
+  uint32_t *words = reinterpret_cast<uint32_t *>(out_idx) + row * (int64_t)K;              // (PACKED only)
   const int j0 = tid * C;
   const double ub = u[row];      // (needed after the scan; sent for now)
 
@@ -489,9 +495,13 @@ __global__ __launch_bounds__(kMaxThreads, C > 8 ? 1 : 8) void ancestor_index_row
       raise_flag(flags, has_nan ? AESMC_FLAG_NAN_LOG_WEIGHT : AESMC_FLAG_DEGENERATE_ROW);
       if (out_lse != nullptr) out_lse[row] = has_nan ? Num<T>::nan() : (T)dm;      // torch.logsumexp's values for such rows
     }
-    for (int i = 0; i < C; ++i) {
-      idx[j0 + i] = (int64_t)K;
-      if (out_child_end != nullptr) out_child_end[row * (int64_t)K + j0 + i] = 0;     // nobody has children
+    if constexpr (PACKED) {
+      for (int i = 0; i < C; ++i) words[j0 + i] = (uint32_t)K;      // the index K, nobody has children
+    } else {
+      for (int i = 0; i < C; ++i) {
+        idx[j0 + i] = (int64_t)K;
+        if (out_child_end != nullptr) out_child_end[row * (int64_t)K + j0 + i] = 0;     // nobody has children
+      }
     }
     return;
   }
@@ -574,10 +584,12 @@ __global__ __launch_bounds__(kMaxThreads, C > 8 ? 1 : 8) void ancestor_index_row
     if (lane == 0) scratch_i[32 + wave] = first[0];
     range_last = first[C - 1];
     if (__any(lane != kWave - 1 && range_last > next_lane_first) && lane == 0) *inverted = 1;
-    int32_t *ends = out_child_end + row * (int64_t)K + j0;
+    if constexpr (!PACKED) {
+      int32_t *ends = out_child_end + row * (int64_t)K + j0;
 #pragma unroll
-    for (int q = 0; q < C / 4; ++q)
-      reinterpret_cast<int4 *>(ends)[q] = make_int4(first[4 * q], first[4 * q + 1], first[4 * q + 2], first[4 * q + 3]);
+      for (int q = 0; q < C / 4; ++q)
+        reinterpret_cast<int4 *>(ends)[q] = make_int4(first[4 * q], first[4 * q + 1], first[4 * q + 2], first[4 * q + 3]);
+    }
   }
   // ---- markers: slot first[j] holds j + 1 for the LAST particle that starts there ---------------------------------------
   {
@@ -621,25 +633,42 @@ __global__ __launch_bounds__(kMaxThreads, C > 8 ? 1 : 8) void ancestor_index_row
   if (out_child_end != nullptr && *inverted != 0) {      // (uniform: read behind the barrier above)
     // the rare row: every entry clamped to the smallest first[] behind it — the later lanes of the wavefront by a reverse
     // scan over each lane's first entry, the later wavefronts' minima through LDS; the entries are read back from where
-    // this lane stored them
+    // this lane stored them (PACKED: they have not left yet — the high halves of the words to come, in registers)
     int32_t *ends = out_child_end + row * (int64_t)K + j0;
-    const int wave_min = wave_suffix_min(ends[0], lane);
+    const int wave_min = wave_suffix_min(PACKED ? first[0] : ends[0], lane);
     int bound = __shfl_down(wave_min, 1, kWave);
     if (lane == kWave - 1) bound = K;
     __syncthreads();      // (scratch_i[32 ..) was last read in front of the barrier above)
     if (lane == 0) scratch_i[32 + wave] = wave_min;
     __syncthreads();
     for (int w = wave + 1; w < nwaves; ++w) bound = min(bound, scratch_i[32 + w]);
-    for (int i = 0; i < C; ++i)
-      if (ends[i] > bound) ends[i] = bound;
+    if constexpr (PACKED) {
+#pragma unroll
+      for (int i = 0; i < C; ++i) first[i] = min(first[i], bound);
+    } else {
+      for (int i = 0; i < C; ++i)
+        if (ends[i] > bound) ends[i] = bound;
+    }
   }
   before = max(before, before_lanes);
+  if constexpr (PACKED) {
+    const bool ranges = out_child_end != nullptr;
 #pragma unroll
-  for (int i = 0; i < C; i += 2) {
-    longlong2 pair;
-    pair.x = (int64_t)max(before, best[i]);
-    pair.y = (int64_t)max(before, best[i + 1]);
-    *reinterpret_cast<longlong2 *>(idx + j0 + i) = pair;
+    for (int q = 0; q < C / 4; ++q) {
+      uint32_t w[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        w[r] = (uint32_t)max(before, best[4 * q + r]) | (ranges ? (uint32_t)first[4 * q + r] << 16 : 0u);
+      reinterpret_cast<uint4 *>(words + j0)[q] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < C; i += 2) {
+      longlong2 pair;
+      pair.x = (int64_t)max(before, best[i]);
+      pair.y = (int64_t)max(before, best[i + 1]);
+      *reinterpret_cast<longlong2 *>(idx + j0 + i) = pair;
+    }
   }
 }
 
@@ -717,6 +746,33 @@ static int launch_step(const void *log_w, const double *u, int64_t *idx, void *o
   const int64_t four_max = (K % 256 == 0 && payload.src == nullptr) ? 4096 : 2048;
   return launch_by_row_length(K, four_max, [&](auto c) {
     return launch_inv<T, decltype(c)::value>(log_w, u, idx, flags, B, K, s, out_lse, payload, child_end);
+  });
+}
+
+// The packed step: the lean form with the one-word output, exactly where — and at the particles per lane at which —
+// launch_step runs the lean form for a payload-free step, so that the packed and the unpacked step are one kernel body
+// with two output forms.  AESMC_ERR_UNSUPPORTED wherever that step runs the general kernel (rows of at most 512
+// particles: two per lane; rows that are not whole wavefronts of C; the general kernel forced): the caller takes the step
+// with the two arrays.
+template <typename T>
+static int launch_step_packed(const void *log_w, const double *u, uint32_t *words, void *out_lse, int32_t *flags, int64_t B,
+                              int64_t K, bool ranges, hipStream_t s) {
+  if (g_k2_form == 1) return AESMC_ERR_UNSUPPORTED;
+  return launch_by_row_length(K, K % 256 == 0 ? 4096 : 2048, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    if constexpr (C % 4 == 0) {
+      const int64_t lanes = K / C;
+      if (lanes * C != K || lanes % kWave != 0 || lanes > kMaxThreads || (reinterpret_cast<uintptr_t>(log_w) & 15u) != 0)
+        return (int)AESMC_ERR_UNSUPPORTED;
+      const size_t lds_rows = (size_t)kScratchDoubles * sizeof(double) + (size_t)(K + 4) * sizeof(int);
+      if (raise_dynamic_lds_cap<ancestor_index_rows_kernel<T, C, true>>() != AESMC_OK) return (int)AESMC_ERR_LAUNCH;
+      g_k2_last_form = 2;
+      hipLaunchKernelGGL((ancestor_index_rows_kernel<T, C, true>), dim3((unsigned)B), dim3((unsigned)lanes), lds_rows, s,
+                         (const T *)log_w, u, reinterpret_cast<int64_t *>(words), flags, (int)K, (T *)out_lse,
+                         ranges ? reinterpret_cast<int32_t *>(words) : nullptr);
+      return hipGetLastError() == hipSuccess ? (int)AESMC_OK : (int)AESMC_ERR_LAUNCH;
+    }
+    return (int)AESMC_ERR_UNSUPPORTED;
   });
 }
 
@@ -818,4 +874,17 @@ extern "C" int aesmc_resample_step_ranges(int dtype, const void *log_w, const do
   if (dtype == AESMC_F32) return launch_step<float>(log_w, u, out_idx, out_lse, flags, B, K, none, s, out_child_end);
   if (dtype == AESMC_F64) return launch_step<double>(log_w, u, out_idx, out_lse, flags, B, K, none, s, out_child_end);
   return AESMC_ERR_INVALID_ARGUMENT;
+}
+
+extern "C" int aesmc_resample_step_packed(int dtype, const void *log_w, const double *u, uint32_t *out_words, void *out_lse,
+                                          int want_child_end, int32_t *flags, int64_t B, int64_t K, void *stream) {
+  using namespace aesmc;
+  if (log_w == nullptr || u == nullptr || out_words == nullptr || B < 0 || K < 0 || (((uintptr_t)out_words) & 15u) != 0)
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (dtype != AESMC_F32 && dtype != AESMC_F64) return AESMC_ERR_INVALID_ARGUMENT;
+  if (B == 0 || K == 0) return AESMC_OK;
+  if (K > kInvMaxParticles || K > 65535 || B > 0x7fffffffLL) return AESMC_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == AESMC_F32) return launch_step_packed<float>(log_w, u, out_words, out_lse, flags, B, K, want_child_end != 0, s);
+  return launch_step_packed<double>(log_w, u, out_words, out_lse, flags, B, K, want_child_end != 0, s);
 }

@@ -1078,7 +1078,8 @@ static int launch_affine_logweight_backward(const void *xprev, const void *x, co
                                             int64_t K, hipStream_t stream, bool step = false,
                                             const void *gx_in = nullptr, const int64_t *anc_idx = nullptr,
                                             int32_t *flags = nullptr, const void *child_grad = nullptr,
-                                            const int32_t *child_end = nullptr, aesmc_affine_chain *chain = nullptr) {
+                                            const int32_t *child_end = nullptr, aesmc_affine_chain *chain = nullptr,
+                                            bool packed = false) {
   const int64_t N = B * K;
   const int64_t dx = mp->dout, dy = mg->dout;
   const int dp = lg_pad_dim(std::max(dx, dy));
@@ -1088,6 +1089,7 @@ static int launch_affine_logweight_backward(const void *xprev, const void *x, co
   // (the question is put for every float32 step: aesmc_test_last_step_backward_form reports this DECISION — a shape
   //  declined further down still reads 1; the rows form takes whole tiles only, which `covers` asks of K itself)
   if constexpr (sizeof(T) == 4) rows_form = step && affine_step_backward_rows_covers(mp, mg, mq, B, K);
+  if (packed && !rows_form) return AESMC_ERR_UNSUPPORTED;      // (only the rows form reads the packed words: the caller unpacks)
   int ppl = (sizeof(T) == 4 && dp <= 12 && !lg_few_tiles(N)) ? 2 : 1;
   // the step kernel is latency-bound: one particle per lane and three workgroups per CU where the registers
   // allow it without spills (d = 10: 322 -> 300 us; d = 8: no difference; d = 12: 448 -> 477, kept at two)
@@ -1131,6 +1133,7 @@ static int launch_affine_logweight_backward(const void *xprev, const void *x, co
   out.gat = lg_gather(anc_idx, flags, (size_t)dx * sizeof(T));
   out.child_grad = child_grad;
   out.child_end = child_end;
+  out.packed = packed ? 1 : 0;
   out.child_stage = child_stage ? 1 : 0;
   {
     size_t row_bytes = (size_t)dx * sizeof(T), align = 1;
@@ -1270,7 +1273,7 @@ static int affine_step_backward_entry(
     const aesmc_affine_map *emission, const aesmc_affine_map *proposal, const void *scale_p, const void *scale_g,
     const void *scale_q, const void *lw, const void *lse, const void *grad_lse, const void *grad_lw,
     const void *grad_x, const void *child_grad, const int32_t *child_end, const aesmc_affine_logweight_grads *out,
-    void *ws, size_t ws_bytes, int64_t B, int64_t K, void *stream, aesmc_affine_chain *chain);
+    void *ws, size_t ws_bytes, int64_t B, int64_t K, void *stream, aesmc_affine_chain *chain, bool packed = false);
 
 extern "C" int aesmc_affine_step_backward(
     int dtype, const void *x_prev, const void *x, const void *y, int64_t y_stride_b, const aesmc_affine_map *transition,
@@ -1309,13 +1312,45 @@ extern "C" int aesmc_affine_step_backward_resampled(
                                     out, ws, ws_bytes, B, K, stream, chain);
 }
 
+// aesmc_affine_step_backward_resampled with the ancestors and the children's ranges read out of the packed words of
+// aesmc_resample_step_packed: `ancestor_words` is THIS step's resampling (low halves), `child_words` the NEXT step's (high
+// halves; NULL with `child_grad`).  The rows form only — AESMC_ERR_UNSUPPORTED elsewhere, nothing launched: the caller
+// unpacks (aesmc_unpack_ancestors) and takes the entry above.
+extern "C" int aesmc_affine_step_backward_packed(
+    int dtype, const void *x_src, const uint32_t *ancestor_words, const void *x, const void *y, int64_t y_stride_b,
+    const aesmc_affine_map *transition, const aesmc_affine_map *emission, const aesmc_affine_map *proposal,
+    const void *scale_p, const void *scale_g, const void *scale_q, const void *lw, const void *lse,
+    const void *grad_lse, const void *grad_lw, const void *grad_x, const void *child_grad, const uint32_t *child_words,
+    const aesmc_affine_logweight_grads *out, void *ws, size_t ws_bytes, int32_t *flags, aesmc_affine_chain *chain,
+    int64_t B, int64_t K, void *stream) {
+  if (ancestor_words == nullptr || (((uintptr_t)ancestor_words) & 3u) != 0) return AESMC_ERR_INVALID_ARGUMENT;
+  if (chain != nullptr) {
+    chain->records = 0;
+    if (chain->carry != nullptr && (chain->carry_records <= 0 || chain->carry_records > kLgMaxGrid || chain->carry == ws ||
+                                    !aligned16(chain->carry)))
+      return AESMC_ERR_INVALID_ARGUMENT;
+    if (chain->defer != 0 && out != nullptr &&
+        (out->grad_weight_p != nullptr || out->grad_weight_g != nullptr || out->grad_weight_q != nullptr ||
+         out->grad_scales != nullptr))
+      return AESMC_ERR_INVALID_ARGUMENT;      // a deferring call writes none of them
+  }
+  if ((child_grad == nullptr) != (child_words == nullptr) || (((uintptr_t)child_words) & 3u) != 0 ||
+      (child_grad != nullptr && child_grad == (out != nullptr ? out->grad_x_prev : nullptr)))
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (K > 65535 || dtype != AESMC_F32) return (dtype == AESMC_F32 || dtype == AESMC_F64) ? AESMC_ERR_UNSUPPORTED : AESMC_ERR_INVALID_ARGUMENT;
+  return affine_step_backward_entry(dtype, x_src, reinterpret_cast<const int64_t *>(ancestor_words), flags, x, y, y_stride_b,
+                                    transition, emission, proposal, scale_p, scale_g, scale_q, lw, lse, grad_lse, grad_lw,
+                                    grad_x, child_grad, reinterpret_cast<const int32_t *>(child_words), out, ws, ws_bytes, B,
+                                    K, stream, chain, true);
+}
+
 static int affine_step_backward_entry(
     int dtype, const void *x_prev, const int64_t *ancestors, int32_t *flags, const void *x, const void *y,
     int64_t y_stride_b, const aesmc_affine_map *transition,
     const aesmc_affine_map *emission, const aesmc_affine_map *proposal, const void *scale_p, const void *scale_g,
     const void *scale_q, const void *lw, const void *lse, const void *grad_lse, const void *grad_lw,
     const void *grad_x, const void *child_grad, const int32_t *child_end, const aesmc_affine_logweight_grads *out,
-    void *ws, size_t ws_bytes, int64_t B, int64_t K, void *stream, aesmc_affine_chain *chain) {
+    void *ws, size_t ws_bytes, int64_t B, int64_t K, void *stream, aesmc_affine_chain *chain, bool packed) {
   if (out == nullptr) return AESMC_ERR_INVALID_ARGUMENT;
   // the draw leaves no gradient for x_t and the location gradients have no meaning here
   if (out->grad_x != nullptr || out->grad_loc_p != nullptr || out->grad_loc_g != nullptr || out->grad_loc_q != nullptr)
@@ -1352,11 +1387,11 @@ static int affine_step_backward_entry(
              ? launch_affine_logweight_backward<float>(x_prev, x, y, y_stride_b, transition, emission, proposal,
                                                        scale_p, scale_g, scale_q, lw, lse, grad_lse, grad_lw, out, ws,
                                                        ws_bytes, B, K, s, true, grad_x, ancestors, flags, child_grad,
-                                                       child_end, chain)
+                                                       child_end, chain, packed)
              : launch_affine_logweight_backward<double>(x_prev, x, y, y_stride_b, transition, emission, proposal,
                                                         scale_p, scale_g, scale_q, lw, lse, grad_lse, grad_lw, out, ws,
                                                         ws_bytes, B, K, s, true, grad_x, ancestors, flags, child_grad,
-                                                        child_end, chain);
+                                                        child_end, chain, packed);
 }
 
 extern "C" int aesmc_affine_backward_collect(int dtype, const void *ws, int32_t records, int64_t dx, int64_t dy,

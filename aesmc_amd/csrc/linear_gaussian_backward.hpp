@@ -103,6 +103,9 @@ struct LgBackwardOut {
   // kLgPairFloats floats; nullptr: a workspace of the older size — the location chains then run one output at a time)
   float *pairs;
   int pairs_ready;      // the pairs at `pairs` are an earlier call's of the same run (aesmc_affine_chain::pairs_in): not rebuilt
+  // step kernel, rows form: gat.idx and child_end point at the packed words of aesmc_resample_step_packed (uint32 per
+  // particle: the ancestor in the low half, the children's range in the high half) instead of int64 / int32 entries
+  int packed;
 };
 constexpr int kLgPairFloats = (kLgMaxDim / 2) * kLgMaxDim * 2;      // (== kPairFloats of linear_gaussian_fused.hpp)
 

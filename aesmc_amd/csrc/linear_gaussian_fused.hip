@@ -663,7 +663,8 @@ int launch_affine_propagate_item(const void *xsrc, const int64_t *anc_idx, const
                                  const aesmc_affine_map *mp, const aesmc_affine_map *mg, const aesmc_affine_map *mq,
                                  const void *sp, const void *sg, const void *sq, void *out_x, void *out_lw, int32_t *flags,
                                  int64_t B, int64_t K, uint64_t seed, uint64_t offset, int64_t threads,
-                                 const uint64_t *rng_state, const float *weight_pairs, hipStream_t stream);
+                                 const uint64_t *rng_state, const float *weight_pairs, hipStream_t stream,
+                                 bool anc_packed);      // (anc_packed: `anc_idx` points at the packed words of K2)
 
 int g_fused_form = [] {
   const char *v = measurement_knob("AESMC_K16_FORM");      // ("roles": the first form whatever the shape — linear_gaussian_noise.hip)
@@ -691,7 +692,7 @@ int launch_affine_propagate_fused(const void *xsrc, const int64_t *anc_idx, cons
   // One item per workgroup (linear_gaussian_item.hip); the same bits either way.
   if (g_fused_form == 2 || (g_fused_form == 0 && plan.items < kItemFormMaxItems)) {
     const int status = launch_affine_propagate_item(xsrc, anc_idx, y, y_sb, mp, mg, mq, sp, sg, sq, out_x, out_lw, flags, B,
-                                                    K, seed, offset, threads, rng_state, weight_pairs, stream);
+                                                    K, seed, offset, threads, rng_state, weight_pairs, stream, false);
     if (status != AESMC_ERR_UNSUPPORTED) {
       g_fused_last_form = 2;
       return status;

@@ -39,7 +39,11 @@ __device__ __forceinline__ float item_quotient(float n, float d, float r) {
 // DXC: the latent's extent (compile time).  DYC: the observation's, or 0 = run time (<= 16).  PAIRED: the maps' `w` point
 // at their interleaved copies (aesmc_affine_weight_pairs) and the chains of two outputs advance together, one
 // v_pk_fma_f32 per input (linear_gaussian_fused.hpp: the same bits as the v_fmac_f32 chains).
-template <int DXC, int DYC, bool GATHER, bool PAIRED>
+// GATHER: how x_{t-1}'s rows are reached — kItemNoGather as they lie, kItemGather64 through int64 ancestor indices,
+// kItemGatherPacked through the resampling launch's packed words (`anc_idx` read as uint32: the index is the low half,
+// 4 bytes per particle instead of 8; the high half — the children's range — is not this kernel's).
+constexpr int kItemNoGather = 0, kItemGather64 = 1, kItemGatherPacked = 2;
+template <int DXC, int DYC, int GATHER, bool PAIRED>
 __global__ __launch_bounds__(512, 4) void affine_propagate_item_kernel(
     const float *__restrict__ xsrc, const float *__restrict__ y, int64_t y_sb, LgMap mp, LgMap mg, LgMap mq,
     const float *__restrict__ sp_ptr, const float *__restrict__ sg_ptr, const float *__restrict__ sq_ptr,
@@ -78,7 +82,9 @@ __global__ __launch_bounds__(512, 4) void affine_propagate_item_kernel(
   // ---- the ancestor first: its round trip, and the row's behind it, fly under the draws ---------------------------
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   u32x2 araw;
-  if constexpr (GATHER) {
+  if constexpr (GATHER == kItemGatherPacked) {
+    araw = u32x2{reinterpret_cast<const uint32_t *>(anc_idx)[cur.nf + rr] & 0xffffu, 0u};
+  } else if constexpr (GATHER == kItemGather64) {
     araw = __builtin_bit_cast(u32x2, anc_idx[cur.nf + rr]);
   } else {
     const uint32_t k = cur.k0 + rr;
@@ -365,19 +371,25 @@ template <int DXC, int DYC, bool PAIRED>
 static int item_launch(dim3 grid, size_t lds, hipStream_t stream, const float *xsrc, const float *y, int64_t y_sb,
                        const LgMap &mp, const LgMap &mg, const LgMap &mq, const float *sp, const float *sg, const float *sq,
                        float *out_lw, uint32_t K, uint32_t Bn, float *out_x, const int64_t *anc, int32_t *flags,
-                       const PhiloxStream &ps, const FusedPlan &plan) {
-  static bool raised[2][64] = {};
-  if (anc != nullptr) {
+                       const PhiloxStream &ps, const FusedPlan &plan, bool anc_packed) {
+  static bool raised[3][64] = {};
+  if (anc != nullptr && anc_packed) {
     if (lds > 64 * 1024 &&
-        !lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_propagate_item_kernel<DXC, DYC, true, PAIRED>), raised[0]))
+        !lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_propagate_item_kernel<DXC, DYC, kItemGatherPacked, PAIRED>), raised[2]))
       return AESMC_ERR_LAUNCH;
-    hipLaunchKernelGGL((affine_propagate_item_kernel<DXC, DYC, true, PAIRED>), grid, dim3(512), lds, stream, xsrc, y, y_sb, mp,
+    hipLaunchKernelGGL((affine_propagate_item_kernel<DXC, DYC, kItemGatherPacked, PAIRED>), grid, dim3(512), lds, stream, xsrc, y,
+                       y_sb, mp, mg, mq, sp, sg, sq, out_lw, K, Bn, out_x, anc, flags, ps, plan);
+  } else if (anc != nullptr) {
+    if (lds > 64 * 1024 &&
+        !lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_propagate_item_kernel<DXC, DYC, kItemGather64, PAIRED>), raised[0]))
+      return AESMC_ERR_LAUNCH;
+    hipLaunchKernelGGL((affine_propagate_item_kernel<DXC, DYC, kItemGather64, PAIRED>), grid, dim3(512), lds, stream, xsrc, y, y_sb, mp,
                        mg, mq, sp, sg, sq, out_lw, K, Bn, out_x, anc, flags, ps, plan);
   } else {
     if (lds > 64 * 1024 &&
-        !lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_propagate_item_kernel<DXC, DYC, false, PAIRED>), raised[1]))
+        !lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_propagate_item_kernel<DXC, DYC, kItemNoGather, PAIRED>), raised[1]))
       return AESMC_ERR_LAUNCH;
-    hipLaunchKernelGGL((affine_propagate_item_kernel<DXC, DYC, false, PAIRED>), grid, dim3(512), lds, stream, xsrc, y, y_sb, mp,
+    hipLaunchKernelGGL((affine_propagate_item_kernel<DXC, DYC, kItemNoGather, PAIRED>), grid, dim3(512), lds, stream, xsrc, y, y_sb, mp,
                        mg, mq, sp, sg, sq, out_lw, K, Bn, out_x, anc, flags, ps, plan);
   }
   return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
@@ -428,7 +440,7 @@ int launch_affine_propagate_item(const void *xsrc, const int64_t *anc_idx, const
                                  const aesmc_affine_map *mp, const aesmc_affine_map *mg, const aesmc_affine_map *mq,
                                  const void *sp, const void *sg, const void *sq, void *out_x, void *out_lw, int32_t *flags,
                                  int64_t B, int64_t K, uint64_t seed, uint64_t offset, int64_t threads,
-                                 const uint64_t *rng_state, const float *weight_pairs, hipStream_t stream) {
+                                 const uint64_t *rng_state, const float *weight_pairs, hipStream_t stream, bool anc_packed) {
   const int64_t dx = mp->dout, dy = mg->dout;
   if (dx < 2 || dx > 16 || dy < 1 || dy > 16) return AESMC_ERR_UNSUPPORTED;
   const auto rows_contiguous = [](const aesmc_affine_map *m) {
@@ -453,7 +465,8 @@ int launch_affine_propagate_item(const void *xsrc, const int64_t *anc_idx, const
 #define ITEM_ARGS                                                                                                    \
   grid, lds, stream, static_cast<const float *>(xsrc), static_cast<const float *>(y), y_sb, p, gm, q,                  \
       static_cast<const float *>(sp), static_cast<const float *>(sg), static_cast<const float *>(sq),                  \
-      static_cast<float *>(out_lw), (uint32_t)K, (uint32_t)B, static_cast<float *>(out_x), anc_idx, flags, ps, plan
+      static_cast<float *>(out_lw), (uint32_t)K, (uint32_t)B, static_cast<float *>(out_x), anc_idx, flags, ps, plan,  \
+      anc_packed
 #define ITEM_CASE(D)                                                                                                 \
   case D:                                                                                                            \
     if (paired) return dy == D ? item_launch<D, D, true>(ITEM_ARGS) : item_launch<D, 0, true>(ITEM_ARGS);              \
@@ -494,4 +507,32 @@ extern "C" int aesmc_affine_weight_pairs_scaled(const aesmc_affine_map *transiti
   return launch_affine_weight_pairs(lg_map(transition), lg_map(emission), lg_map(proposal), static_cast<float *>(out_pairs),
                                     static_cast<hipStream_t>(stream), static_cast<const float *>(scale_p),
                                     static_cast<const float *>(scale_g), static_cast<const float *>(scale_q), true);
+}
+
+// K16 reading the ancestors out of the packed words of aesmc_resample_step_packed (the item form only: AESMC_ERR_UNSUPPORTED
+// where that form does not cover the launch or another form is forced — the caller unpacks and takes the int64 entry).
+extern "C" int aesmc_affine_normal_propagate_drawn_packed(
+    const void *x_src, const uint32_t *ancestor_words, const void *y, int64_t y_stride_b, const aesmc_affine_map *transition,
+    const aesmc_affine_map *emission, const aesmc_affine_map *proposal, const void *scale_p, const void *scale_g,
+    const void *scale_q, void *out_x, void *out_lw, int32_t *flags, int64_t B, int64_t K, uint64_t seed,
+    uint64_t offset, int64_t threads, const uint64_t *rng_state, const void *weight_pairs, void *stream) {
+  if ((reinterpret_cast<uintptr_t>(weight_pairs) & 15u) != 0) return AESMC_ERR_INVALID_ARGUMENT;
+  if (x_src == nullptr || ancestor_words == nullptr || y == nullptr || transition == nullptr || emission == nullptr ||
+      proposal == nullptr || scale_p == nullptr || scale_g == nullptr || scale_q == nullptr || out_lw == nullptr ||
+      out_x == nullptr || B < 0 || K < 0 || threads <= 0 || (threads % 256) != 0 || threads > 0x7fffffffLL || (offset & 3u) != 0)
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (!aligned16(x_src) || !aligned16(out_x) || out_x == x_src || (((uintptr_t)ancestor_words) & 3u) != 0 ||
+      (((uintptr_t)rng_state) & 7u) != 0)
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (!lg_map_ok(transition) || !lg_map_ok(emission) || !lg_map_ok(proposal)) return AESMC_ERR_UNSUPPORTED;
+  const int64_t dx = transition->dout;
+  if (transition->din != dx || proposal->dout != dx || proposal->din != dx || emission->din != dx)
+    return AESMC_ERR_UNSUPPORTED;
+  static const bool first_form = [] { const char *v = measurement_knob("AESMC_K16_FORM"); return v != nullptr && v[0] == 'r'; }();
+  if (K > 65535 || g_fused_form == 1 || first_form) return AESMC_ERR_UNSUPPORTED;
+  if (B == 0 || K == 0) return AESMC_OK;
+  return launch_affine_propagate_item(x_src, reinterpret_cast<const int64_t *>(ancestor_words), y, y_stride_b, transition,
+                                      emission, proposal, scale_p, scale_g, scale_q, out_x, out_lw, flags, B, K, seed, offset,
+                                      threads, rng_state, static_cast<const float *>(weight_pairs),
+                                      static_cast<hipStream_t>(stream), true);
 }

@@ -242,7 +242,10 @@ typedef const SbArgs __attribute__((address_space(4))) sb_cargs;
 
 // PAIRED: the location chains advance two outputs per instruction too (weights from the interleaved pairs the host's
 // launch wrote into the workspace just before this one: fused_pk_pair, linear_gaussian_fused.hpp) — the same bits.
-template <int D, bool GATHER, bool FOLDS, bool PAIRED>
+// PACKED: `anc` and `child_end` point at the resampling launches' packed words (uint32 per particle: the ancestor in the
+// low half of this step's word, the children's range in the high half of the next step's) — a third of the bytes, the
+// same values; everything behind the two loads is unchanged.
+template <int D, bool GATHER, bool FOLDS, bool PAIRED, bool PACKED = false>
 __global__ __launch_bounds__(kLgBlock, Sb<D>::kPerCu) void affine_step_backward_rows_kernel(SbArgs unused_by_name) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];
@@ -279,7 +282,12 @@ __global__ __launch_bounds__(kLgBlock, Sb<D>::kPerCu) void affine_step_backward_
   int64_t anc_n = 0;                                   // the tile after the next one's ancestors (raw)
   int32_t rb_c = 0, re_c = 0, rb_n = 0, re_n = 0;      // child_end entries (before the lane's particle, at it): this tile's, the next one's
   uint32_t blk_lo = 0, blk_hi = 0;                     // the staged block of THIS tile: flat rows [blk_lo, blk_hi)
-  auto anc_load = [&](uint32_t tile) -> int64_t { return SB_A()->anc[(uint64_t)tile * kLgBlock + tid]; };
+  auto anc_load = [&](uint32_t tile) -> int64_t {
+    // (PACKED: the word AS LOADED, zero-extended — its low half is taken in rows_prefetch, a tile later, where the load has
+    //  landed: a mask here would be a wait for everything just sent for, in the middle of the prefetch)
+    if constexpr (PACKED) return (int64_t)(uint64_t)reinterpret_cast<const uint32_t *>(SB_A()->anc)[(uint64_t)tile * kLgBlock + tid];
+    else return SB_A()->anc[(uint64_t)tile * kLgBlock + tid];
+  };
   auto raw_load = [&](uint32_t tile, int32_t &before, int32_t &end) {
     sb_cargs *A = SB_A();
     const uint32_t n = tile * kLgBlock + tid;
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(kLgBlock, Sb<D>::kPerCu) void affine_step_backward_
     const uint32_t n = tile * kLgBlock + tid, K = A->K;
     const float *src;
     if constexpr (GATHER) {
-      int64_t a = araw;
+      int64_t a = PACKED ? (araw & 0xffff) : araw;
       if (a < 0 || a >= (int64_t)K) {      // K2 writes K for a degenerate row (flagged there); never fault on it
         bad = 1;
         a = a < 0 ? 0 : (int64_t)K - 1;
@@ -310,6 +318,10 @@ __global__ __launch_bounds__(kLgBlock, Sb<D>::kPerCu) void affine_step_backward_
   };
   // flat rows [lo, hi) of the children of the lane's particle of `tile`, from its two entries (child_range of the first form)
   auto child_range = [&](uint32_t tile, int32_t before, int32_t end_, uint32_t &lo, uint32_t &hi) {
+    if constexpr (PACKED) {      // (the words as loaded: their high halves are the ranges — taken here, where the loads have landed)
+      before = (int32_t)((uint32_t)before >> 16);
+      end_ = (int32_t)((uint32_t)end_ >> 16);
+    }
     sb_cargs *A = SB_A();
     const uint32_t K = A->K;
     const uint32_t n0 = tile * kLgBlock;
@@ -733,12 +745,20 @@ unsigned affine_step_backward_rows_grid(int64_t B, int64_t K, int64_t d) {
   }
 }
 
-template <int D, bool PAIRED>
+template <int D, bool PAIRED, bool PACKED>
 static void sb_launch(bool gathers, bool folds, unsigned grid, hipStream_t stream, const SbArgs &a, bool &ok) {
   constexpr size_t lds = Sb<D>::kLds;
   static bool raised[4][64] = {};
   ok = true;
-  if (gathers && folds) {
+  if constexpr (PACKED) {      // (packed words are read through ancestors: always a gather)
+    if (folds) {
+      if (lds > 64 * 1024) ok = lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_step_backward_rows_kernel<D, true, true, PAIRED, true>), raised[0]);
+      hipLaunchKernelGGL((affine_step_backward_rows_kernel<D, true, true, PAIRED, true>), ok ? dim3(grid) : dim3(0), dim3(kLgBlock), lds, stream, a);
+    } else {
+      if (lds > 64 * 1024) ok = lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_step_backward_rows_kernel<D, true, false, PAIRED, true>), raised[1]);
+      hipLaunchKernelGGL((affine_step_backward_rows_kernel<D, true, false, PAIRED, true>), ok ? dim3(grid) : dim3(0), dim3(kLgBlock), lds, stream, a);
+    }
+  } else if (gathers && folds) {
     if (lds > 64 * 1024) ok = lg_raise_lds_limit(reinterpret_cast<const void *>(&affine_step_backward_rows_kernel<D, true, true, PAIRED>), raised[0]);
     hipLaunchKernelGGL((affine_step_backward_rows_kernel<D, true, true, PAIRED>), ok ? dim3(grid) : dim3(0), dim3(kLgBlock), lds, stream, a);
   } else if (gathers) {
@@ -753,9 +773,15 @@ static void sb_launch(bool gathers, bool folds, unsigned grid, hipStream_t strea
   }
 }
 template <int D>
-static void sb_launch_either(bool paired, bool gathers, bool folds, unsigned grid, hipStream_t stream, const SbArgs &a, bool &ok) {
-  if (paired) sb_launch<D, true>(gathers, folds, grid, stream, a, ok);
-  else sb_launch<D, false>(gathers, folds, grid, stream, a, ok);
+static void sb_launch_either(bool paired, bool packed, bool gathers, bool folds, unsigned grid, hipStream_t stream, const SbArgs &a,
+                             bool &ok) {
+  if (packed) {
+    if (paired) sb_launch<D, true, true>(gathers, folds, grid, stream, a, ok);
+    else sb_launch<D, false, true>(gathers, folds, grid, stream, a, ok);
+  } else {
+    if (paired) sb_launch<D, true, false>(gathers, folds, grid, stream, a, ok);
+    else sb_launch<D, false, false>(gathers, folds, grid, stream, a, ok);
+  }
 }
 
 // does the rows form take the maps' interleaved weight pairs (AESMC_K14_PAIRS=0 in the environment: a measurement knob)?
@@ -798,17 +824,19 @@ int launch_affine_step_backward_rows(const float *xprev, const float *x, const f
     }
     a.pairs = out.pairs;
   }
+  const bool packed = out.packed != 0;
+  if (packed && !gathers) return AESMC_ERR_UNSUPPORTED;
   bool ok = true;
   switch (mp.dout) {
 #ifndef AESMC_LG_FAST_BUILD
-    case 2: sb_launch_either<2>(paired, gathers, folds, grid, stream, a, ok); break;
-    case 4: sb_launch_either<4>(paired, gathers, folds, grid, stream, a, ok); break;
-    case 6: sb_launch_either<6>(paired, gathers, folds, grid, stream, a, ok); break;
-    case 8: sb_launch_either<8>(paired, gathers, folds, grid, stream, a, ok); break;
-    case 12: sb_launch_either<12>(paired, gathers, folds, grid, stream, a, ok); break;
-    case 14: sb_launch_either<14>(paired, gathers, folds, grid, stream, a, ok); break;
+    case 2: sb_launch_either<2>(paired, packed, gathers, folds, grid, stream, a, ok); break;
+    case 4: sb_launch_either<4>(paired, packed, gathers, folds, grid, stream, a, ok); break;
+    case 6: sb_launch_either<6>(paired, packed, gathers, folds, grid, stream, a, ok); break;
+    case 8: sb_launch_either<8>(paired, packed, gathers, folds, grid, stream, a, ok); break;
+    case 12: sb_launch_either<12>(paired, packed, gathers, folds, grid, stream, a, ok); break;
+    case 14: sb_launch_either<14>(paired, packed, gathers, folds, grid, stream, a, ok); break;
 #endif
-    case 10: sb_launch_either<10>(paired, gathers, folds, grid, stream, a, ok); break;
+    case 10: sb_launch_either<10>(paired, packed, gathers, folds, grid, stream, a, ok); break;
     default: return AESMC_ERR_UNSUPPORTED;
   }
   return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;

@@ -703,3 +703,32 @@ extern "C" int aesmc_resample_gather_backward(int dtype, const void *grad_out, c
                        (uint32_t)row_elems, re, (uint32_t)bpr);
   return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
 }
+
+// The packed words of aesmc_resample_step_packed back as the two arrays every other consumer reads: idx[n] = word & 0xffff
+// (int64), child_end[n] = word >> 16 (int32; NULL: not wanted).  One pass, a grid-stride loop.
+namespace aesmc {
+__global__ __launch_bounds__(256) void unpack_ancestors_kernel(const uint32_t *__restrict__ words, int64_t *__restrict__ idx,
+                                                               int32_t *__restrict__ child_end, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint32_t w = words[i];
+    idx[i] = (int64_t)(w & 0xffffu);
+    if (child_end != nullptr) child_end[i] = (int32_t)(w >> 16);
+  }
+}
+}  // namespace aesmc
+
+extern "C" int aesmc_unpack_ancestors(const uint32_t *words, int64_t *out_idx, int32_t *out_child_end, int64_t B, int64_t K,
+                                      void *stream) {
+  using namespace aesmc;
+  if (words == nullptr || out_idx == nullptr || B < 0 || K < 0 || (((uintptr_t)words) & 3u) != 0 ||
+      (((uintptr_t)out_idx) & 7u) != 0 || (((uintptr_t)out_child_end) & 3u) != 0)
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (B == 0 || K == 0) return AESMC_OK;
+  if (K > 65535 || B > 0x7fffffffLL) return AESMC_ERR_UNSUPPORTED;
+  const int64_t n = B * K;
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(unpack_ancestors_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+                     (hipStream_t)stream, words, out_idx, out_child_end, n);
+  return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+}

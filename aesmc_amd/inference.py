@@ -296,6 +296,7 @@ def get_resampled_latents(latents, ancestral_indices):
     len(latents) - 1, may be empty) and returns the latents re-indexed along it
     (aesmc/inference.py:196-231)."""
     assert len(ancestral_indices) == len(latents) - 1
+    ancestral_indices = [_kernels.as_index(index) for index in ancestral_indices]
     probe = _first_tensor(latents[0])
     batch_size, num_particles = probe.size()[:2]
     lineage = torch.arange(num_particles, dtype=torch.int64, device=probe.device) \
@@ -468,7 +469,8 @@ def _infer(inference_algorithm, observations, initial, transition, emission,
                 fold_gather = lazy_step and pending is not None and fold_children and torch.is_grad_enabled()
                 index, lse_previous, moved = _ops.resample_step(previous, uniforms, None if lazy_step else newest,
                                                                 want_lse=step_lse[-1] is None, pending=pending,
-                                                                want_child_end=fold_gather)
+                                                                want_child_end=fold_gather,
+                                                                packed=lazy_step and cfg.packed_ancestors)
                 if step_lse[-1] is None:
                     if pending is not None:
                         del deferred[time - 1]
@@ -578,6 +580,7 @@ def _infer(inference_algorithm, observations, initial, transition, emission,
             log_marginal_likelihood = torch.sum(
                 _ops.bind_rows(torch.stack(step_lse, dim=0), bound_rows) - log_num_particles, dim=0)
         if return_latents:
+            indices = [_kernels.as_index(index) for index in indices]
             latents = get_resampled_latents(originals, indices)
         if return_log_weight:
             log_weight = log_weights[-1]
@@ -599,6 +602,8 @@ def _infer(inference_algorithm, observations, initial, transition, emission,
         if not return_log_weight:
             log_weight = None
 
+    if use_smc and return_ancestral_indices:      # (what leaves `infer` is int64, whatever the steps handed one another)
+        indices = [_kernels.as_index(index) for index in indices]
     capturing = device is not None and device.type == "cuda" and torch.cuda.is_current_stream_capturing()
     if device is not None and not capturing:  # under hipGraph capture the replayer checks instead
         _raise_for_flags(_kernels.get().read_flags(device))

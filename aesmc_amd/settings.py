@@ -64,6 +64,14 @@ class Settings:
     # stands for (K6, K8, K5); off: those three  [AESMC_INITIAL_STEP]
     initial_step: bool = True
 
+    # on the lean route of `infer` (the newest latent left un-gathered: K2 without a payload, then K16) the resampling
+    # launch — where it is K2's lean kernel: whole rows of more than 512 particles — hands its ancestor indices and
+    # children ranges to K16 and K14 as ONE 32-bit word per particle
+    # (aesmc_resample_step_packed) instead of an int64 and an int32 array; anything else that wants them — a model that
+    # reads resampled values, the returned indices and latents, the wide step — gets the arrays from one unpack launch.
+    # The same numbers either way; off: the two arrays  [AESMC_PACKED_ANCESTORS]
+    packed_ancestors: bool = True
+
     # the resampling SCHEME of 'smc' inference — NOT a route switch: it changes the numbers.  'systematic' (the
     # reference's, aesmc/inference.py:234-269): positions (u + k) / K from ONE uniform per batch row, drawn from numpy's
     # global RandomState.  'stratified': positions (u_k + k) / K from one uniform per PARTICLE, drawn with torch.rand from
@@ -93,7 +101,7 @@ def knob(name, default=None):
 
 _DEFAULT = Settings(lazy_gather=_env_flag("AESMC_LAZY_GATHER"), fold_gather_backward=_env_flag("AESMC_FOLD_GATHER_BACKWARD"),
                     kernel_noise=_env_flag("AESMC_KERNEL_NOISE"), particle_linear=_env_flag("AESMC_PARTICLE_LINEAR"),
-                    initial_step=_env_flag("AESMC_INITIAL_STEP"))
+                    initial_step=_env_flag("AESMC_INITIAL_STEP"), packed_ancestors=_env_flag("AESMC_PACKED_ANCESTORS"))
 _SCOPED = contextvars.ContextVar("aesmc_amd_settings", default=None)      # the innermost `override`'s CHANGED fields only
 _FIELDS = tuple(field.name for field in dataclasses.fields(Settings))
 

@@ -455,6 +455,7 @@ def _wide_step(prior_dist, proposal_dist, latent, emission_dist, observation, de
     if type(x_prev) is LazyResampled:
         if x_prev.pending is not None:
             x_prev, ancestors = x_prev.pending        # (x_{t-1}, ancestors): fetched inside the launch
+            ancestors = _kernels.as_index(ancestors)  # (the wide launches read int64 indices)
         else:
             x_prev = x_prev.materialise()
     y_rows = observation[:, 0]
@@ -621,6 +622,7 @@ def resample(value, ancestral_index):
     (state.py:158-183); recurses through dicts; differentiable w.r.t. `value`."""
     if isinstance(value, dict):
         return {key: resample(item, ancestral_index) for key, item in value.items()}
+    ancestral_index = _kernels.as_index(ancestral_index)      # (a step's packed hand-off: unpacked once, here if nowhere before)
     if not torch.is_tensor(value):
         raise AttributeError("value must be a dict or a torch.Tensor. Got: {}".format(value))
     if isinstance(value, LazyParticles):

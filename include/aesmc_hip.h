@@ -65,7 +65,10 @@ extern "C" {
  *                aesmc_pairwise_lse (K22: the pairwise log-sum-exp of the marginal smoother, FFBSm);
  *                aesmc_pairwise_mean (K23: the pairwise softmax mean of the two-slice smoother);
  *                aesmc_pairwise_argmax (K24: the pairwise max and argmax of the MAP trajectory, particle Viterbi);
- *                aesmc_pairwise_pass (K25: the backward of K22, for the marginal particle filter's objective).
+ *                aesmc_pairwise_pass (K25: the backward of K22, for the marginal particle filter's objective);
+ *                aesmc_resample_step_packed, aesmc_affine_normal_propagate_drawn_packed,
+ *                aesmc_affine_step_backward_packed, aesmc_unpack_ancestors (a step's ancestry handed from K2 to K16 /
+ *                K14 as one 32-bit word per particle).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -262,6 +265,25 @@ int aesmc_resample_step(int dtype, const void *log_w, const double *u, int64_t *
  * The scan has the value in a register anyway: 4 more bytes per particle written. */
 int aesmc_resample_step_ranges(int dtype, const void *log_w, const double *u, int64_t *out_idx, void *out_lse,
                                int32_t *out_child_end, int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K2 handing its results to the launches of this library that consume them as ONE 32-bit word per particle:
+ *   out_words[b,k] = out_idx[b,k] | out_child_end[b,k] << 16      (uint32 [B,K], 16-byte aligned)
+ * — aesmc_resample_step_ranges' two arrays (12 bytes per particle) in 4: the index (K for a NaN / degenerate row, flagged
+ * as there) and the children's range (0 .. K) both fit 16 bits.  `want_child_end` == 0 leaves the high halves 0
+ * (aesmc_resample_step without a payload).  out_lse, flags: as aesmc_resample_step.  The words are read by
+ * aesmc_affine_normal_propagate_drawn_packed (low halves) and aesmc_affine_step_backward_packed; aesmc_unpack_ancestors
+ * turns them back into the two arrays for everything else.  AESMC_ERR_UNSUPPORTED (nothing launched; take
+ * aesmc_resample_step[_ranges]) unless a row is whole wavefronts of the kernel's particles per lane — K a multiple of 256
+ * from 768 to 4096, of 512 up to 8192, of 1024 up to 16384, of 2048 up to 32768, and log_w 16-byte aligned —: exactly the
+ * rows for which aesmc_resample_step[_ranges] without a payload runs the same kernel body, so the two give the same bits
+ * (rows of at most 512 particles run another kernel there, and are declined here). */
+int aesmc_resample_step_packed(int dtype, const void *log_w, const double *u, uint32_t *out_words, void *out_lse,
+                               int want_child_end, int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* out_idx[b,k] = words[b,k] & 0xffff (int64), out_child_end[b,k] = words[b,k] >> 16 (int32; NULL: not wanted): the packed
+ * words of aesmc_resample_step_packed as the arrays of aesmc_resample_step_ranges.  K <= 65535. */
+int aesmc_unpack_ancestors(const uint32_t *words, int64_t *out_idx, int32_t *out_child_end, int64_t B, int64_t K,
+                           void *stream);
 
 /* K2's stratified sibling — one independent uniform per particle instead of one per batch row:
  *   c[j]     as K2's                                             (float64; the same arithmetic, operation for operation)
@@ -649,6 +671,19 @@ int aesmc_affine_normal_propagate_drawn_paired(
     const void *scale_p, const void *scale_g, const void *scale_q, void *out_x, void *out_lw, int32_t *flags,
     int64_t B, int64_t K, uint64_t seed, uint64_t offset, int64_t threads, const uint64_t *rng_state,
     const void *weight_pairs, void *stream);
+
+/* aesmc_affine_normal_propagate_drawn_paired reading the ancestors out of the packed words of
+ * aesmc_resample_step_packed: x_prev[b,k,:] = x_src[b, ancestor_words[b,k] & 0xffff, :] — 4 bytes per particle in place
+ * of 8, every output bit the same.  `ancestor_words` uint32 [B,K], not NULL; a low half >= K is clamped and raises
+ * AESMC_FLAG_INDEX_OUT_OF_RANGE as there; `weight_pairs` may be NULL.  Only the launch with one work item per workgroup
+ * reads the words: AESMC_ERR_UNSUPPORTED (nothing launched; aesmc_unpack_ancestors, then the entry above) where that form
+ * does not cover the operands. */
+int aesmc_affine_normal_propagate_drawn_packed(
+    const void *x_src, const uint32_t *ancestor_words, const void *y, int64_t y_stride_b,
+    const aesmc_affine_map *transition, const aesmc_affine_map *emission, const aesmc_affine_map *proposal,
+    const void *scale_p, const void *scale_g, const void *scale_q, void *out_x, void *out_lw, int32_t *flags,
+    int64_t B, int64_t K, uint64_t seed, uint64_t offset, int64_t threads, const uint64_t *rng_state,
+    const void *weight_pairs, void *stream);
 /* pairs[map][jp][i] = (W[2 jp][i], W[2 jp + 1][i]), zero where a row or column does not exist, for the transition,
  * emission and proposal maps (float32, extents <= 16, any strides), into `out_pairs` (16-byte aligned device memory of
  * aesmc_affine_weight_pairs_floats() floats).  One small launch. */
@@ -889,6 +924,21 @@ int aesmc_affine_step_backward_resampled(
     const aesmc_affine_map *transition, const aesmc_affine_map *emission, const aesmc_affine_map *proposal,
     const void *scale_p, const void *scale_g, const void *scale_q, const void *lw, const void *lse,
     const void *grad_lse, const void *grad_lw, const void *grad_x, const void *child_grad, const int32_t *child_end,
+    const aesmc_affine_logweight_grads *out, void *ws, size_t ws_bytes, int32_t *flags, aesmc_affine_chain *chain,
+    int64_t B, int64_t K, void *stream);
+
+/* aesmc_affine_step_backward_resampled with the packed words of aesmc_resample_step_packed in place of the two arrays:
+ * `ancestor_words` (uint32 [B,K], not NULL) are the words of the resampling step in front of THIS step — their low
+ * halves are its ancestors —, `child_words` (NULL exactly when child_grad is) those of the NEXT step's — their high
+ * halves are where each particle's children end.  Every gradient and record equals, bit for bit, what the entry above
+ * forms from the unpacked arrays.  float32, rows of an even number (2 .. 14) of values on both sides, K a multiple of 256
+ * (the form of the kernel that keeps a wavefront's rows in registers); AESMC_ERR_UNSUPPORTED elsewhere, nothing
+ * launched: aesmc_unpack_ancestors, then the entry above. */
+int aesmc_affine_step_backward_packed(
+    int dtype, const void *x_src, const uint32_t *ancestor_words, const void *x, const void *y, int64_t y_stride_b,
+    const aesmc_affine_map *transition, const aesmc_affine_map *emission, const aesmc_affine_map *proposal,
+    const void *scale_p, const void *scale_g, const void *scale_q, const void *lw, const void *lse,
+    const void *grad_lse, const void *grad_lw, const void *grad_x, const void *child_grad, const uint32_t *child_words,
     const aesmc_affine_logweight_grads *out, void *ws, size_t ws_bytes, int32_t *flags, aesmc_affine_chain *chain,
     int64_t B, int64_t K, void *stream);
 
