@@ -52,6 +52,7 @@ from . import inference  # noqa: F401
 from . import losses  # noqa: F401
 from . import marginal_filter  # noqa: F401
 from . import math  # noqa: F401
+from . import particle_gibbs  # noqa: F401
 from . import settings  # noqa: F401
 from . import smoothing  # noqa: F401
 from . import state  # noqa: F401

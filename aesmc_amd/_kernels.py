@@ -2126,6 +2126,69 @@ class HipKernels:
                      tuple(keep) + (log_w, u, idx, moved) + tuple(views))
         return idx, moved
 
+    # ---- K26 -----------------------------------------------------------------------------------
+    CONDITIONAL_MAX_PARTICLES = 8192
+
+    @staticmethod
+    def conditional_ancestor_index_covers(log_w, u, loc=None, target=None, scale=None):
+        """Whether `conditional_ancestor_index` takes these operands: float32 / float64 throughout and all on one device,
+        1 to 8192 particles, one float64 uniform per slot, and either no transition term or loc [B,K,*], target [B,*] with
+        the same trailing dims of at most 256 values and a scale of one value or one per value."""
+        if not (torch.is_tensor(log_w) and log_w.dim() == 2 and log_w.dtype in _DTYPE_TAG and
+                0 < log_w.size(1) <= HipKernels.CONDITIONAL_MAX_PARTICLES):
+            return False
+        if not (torch.is_tensor(u) and u.dtype == torch.float64 and tuple(u.shape) == tuple(log_w.shape) and
+                u.device == log_w.device):
+            return False
+        if loc is None:
+            return target is None and scale is None
+        if not all(torch.is_tensor(t) and t.dtype == log_w.dtype and t.device == log_w.device
+                   for t in (loc, target, scale)):
+            return False
+        if loc.dim() < 2 or tuple(loc.shape[:2]) != tuple(log_w.shape) or target.dim() != loc.dim() - 1 or \
+                target.size(0) != log_w.size(0) or tuple(target.shape[1:]) != tuple(loc.shape[2:]):
+            return False
+        D = 1
+        for size in loc.shape[2:]:
+            D *= size
+        return 0 < D <= HipKernels.BACKWARD_SAMPLE_MAX_DIM and scale.dim() <= 1 and scale.numel() in (1, D)
+
+    def conditional_ancestor_index(self, log_w, u, loc=None, target=None, scale=None):
+        """The ancestors of one conditional-SMC step (aesmc_conditional_ancestor_index, K26): log_w [B,K], u float64
+        [B,K]; slots 0 .. K-2 draw multinomial ancestors from the weights, slot K-1 is pinned: it keeps ancestor K-1 (loc =
+        target = scale = None), or draws it as K21 draws one trajectory whose next state is target [B,*], with loc [B,K,*]
+        the transition's location per particle and scale one value or one per location value (ancestor sampling).
+        Returns idx int64 [B,K].  Views are taken as they are (element strides)."""
+        tag = self._rows_operand(log_w, "log_weight")
+        _require_hip(u, "uniforms")
+        B, K = log_w.shape
+        if tuple(u.shape) != (B, K) or u.dtype != torch.float64 or u.device != log_w.device:
+            raise ValueError("aesmc_amd: uniforms must be [{}, {}] float64 on {}".format(B, K, log_w.device))
+        if not self.conditional_ancestor_index_covers(log_w, u, loc, target, scale):
+            raise ValueError("aesmc_amd: conditional_ancestor_index does not take these operands (see "
+                             "conditional_ancestor_index_covers)")
+        log_w, u = log_w.contiguous(), u.contiguous()
+        views, keep, D, scale_stride = [None, None], [], 0, 0
+        if loc is not None:
+            for t in (loc, target, scale):
+                _require_hip(t, "transition term")
+            (loc, sl, D), (target, st, _) = self._view3(loc), self._view3(target.unsqueeze(1))
+            scale = scale.reshape(-1).contiguous()
+            scale_stride = 0 if scale.numel() == 1 else 1
+            views[0], views[1] = _lib.View3(_ptr(loc), *sl), _lib.View3(_ptr(target), *st)
+            keep += [loc, target, scale]
+        idx = torch.empty((B, K), dtype=torch.int64, device=log_w.device)
+        if idx.numel() == 0:
+            return idx
+        esz = log_w.element_size()
+        refs = [ctypes.byref(v) if v is not None else None for v in views]
+        self._launch(log_w.device, self._lib.aesmc_conditional_ancestor_index,
+                     (tag, _ptr(log_w), _ptr(u), refs[0], refs[1], _ptr(scale) if D else 0, scale_stride, _ptr(idx),
+                      _ptr(self.flags(log_w.device)), B, K, D, self._stream(log_w)),
+                     lambda: B * K * (esz * (1 + D) + 16) + B * D * esz,
+                     tuple(keep) + (log_w, u, idx) + tuple(views))
+        return idx
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 

@@ -10,7 +10,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libaesmc_hip.so")
-SOURCES = ["abi.hip", "logweight_lse.hip", "ancestor_index.hip", "ancestor_index_stratified.hip", "backward_sample.hip", "pairwise_lse.hip",
+SOURCES = ["abi.hip", "logweight_lse.hip", "ancestor_index.hip", "ancestor_index_stratified.hip", "backward_sample.hip", "conditional_ancestor_index.hip",
+           "pairwise_lse.hip",
            "pairwise_mean.hip", "pairwise_argmax.hip", "pairwise_lse_backward.hip",
            "resample_gather.hip",
            "normal_logprob.hip", "normal_rsample.hip", "particle_summary.hip", "linear_gaussian.hip",

@@ -26,6 +26,11 @@ p(x_t | y_0..y_t).  Four smoothers, all over `infer(..., return_original_latents
     backward-simulated paths searches K or M of the K^T.  It needs the particles only, NO `log_weights`: the filter's
     weights answer "how much mass", this asks "which path", from the model's densities alone.  O(K^2) pairs per step,
     once, deterministic (profiles/map_pairwise_argmax.txt).
+`aesmc_amd.particle_gibbs` (another module) — when the particles of ONE filter run are not enough: all four above are only
+    as good as the run underneath them, and all but FFBS are quadratic in the particle count.  Particle Gibbs with ancestor
+    sampling is a Markov kernel on whole trajectories that leaves the joint smoothing distribution exactly invariant for
+    any number of particles; it mixes with K = 8 .. 64, costs O(K) per step and sweep, and is the sampling step of
+    parameter learning (particle Gibbs, stochastic-approximation or Monte-Carlo EM).
 
 The smoothed posterior `infer(..., return_latents=True)` gives is the genealogy (`inference.get_resampled_latents`): every
 final particle traced back through the ancestor indices.  Over a long sequence the genealogy collapses — after a hundred

@@ -68,7 +68,9 @@ extern "C" {
  *                aesmc_pairwise_pass (K25: the backward of K22, for the marginal particle filter's objective);
  *                aesmc_resample_step_packed, aesmc_affine_normal_propagate_drawn_packed,
  *                aesmc_affine_step_backward_packed, aesmc_unpack_ancestors (a step's ancestry handed from K2 to K16 /
- *                K14 as one 32-bit word per particle).
+ *                K14 as one 32-bit word per particle);
+ *                aesmc_conditional_ancestor_index (K26: conditional multinomial resampling with ancestor sampling,
+ *                the resampling step of particle Gibbs).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -498,6 +500,36 @@ int aesmc_pairwise_pass(int dtype, const aesmc_view3 *own, const aesmc_view3 *ot
                         int64_t scale_stride, const void *own_term, const void *other_term, const void *own_gain,
                         const void *other_gain, void *mass, void *pull, void *spread, int32_t *flags, int64_t B,
                         int64_t N, int64_t M, int64_t D, void *stream);
+
+/* K26 — conditional multinomial resampling with ancestor sampling: the ancestors of one step of conditional SMC
+ * (particle Gibbs; Andrieu, Doucet & Holenstein 2010) whose slot K-1 carries a reference path, that slot's ancestor being
+ * drawn anew given the reference's next state (PGAS; Lindsten, Jordan & Schoen 2014).  The reference has no such call
+ * site.  Systematic and stratified resampling (K2) have no simple exact conditional form (Chopin & Singh 2015);
+ * multinomial resampling has, and this is it.  Per batch row, in one launch:
+ *   log_w   T [B,K] dense                 the step's log-weights
+ *   u       float64 [B,K] dense           in [0, 1), one uniform per slot
+ *   loc     T [B,K,D] view                the transition's location for every particle
+ *   target  T [B,1,D] view                the reference path's next state (`stride_k` is not read)
+ *   scale   T, D values                   read with the element stride `scale_stride`: 0 (one value) or 1
+ * All arithmetic is in float64 whatever T is (float32 or float64, `dtype`):
+ *   w[j]       = exp(log_w[b,j] - max_j log_w[b,:])                      (K2's float64 exp of a non-positive number)
+ *   C[j]       = w[0] + ... + w[j]                                       (added front to back, one at a time)
+ *   idx[b,k]   = min( #{j : C[j] <= u[b,k] * C[K-1]},  max{j : w[j] > 0} )               k = 0 .. K-2
+ *   idx[b,K-1] = K - 1                                                                   D == 0: no transition term
+ *   idx[b,K-1] = the same formula over s[j] = log_w[b,j] - 1/2 sum_d ((target[b,d] - loc[b,j,d]) * inv[d])^2, inv[d] =
+ *                1 / (double)scale[d], at u[b,K-1]: K21's score and draw for ONE trajectory (d ascending, the scaled
+ *                difference squared into a fused multiply-add).
+ * The free slots are K21's draw without a transition term at u[:, :K-1], the pinned slot K21's with M = 1.  Unlike K21's,
+ * the sums C are formed strictly front to back, so the index does not depend on an association of the additions.
+ * Bad rows, by K2's conventions: a NaN among log_w[b,:] raises AESMC_FLAG_NAN_LOG_WEIGHT, a maximum that is not finite
+ * AESMC_FLAG_DEGENERATE_ROW, and every slot of the row is K; a NaN among s (from loc or target) or no finite maximum of s
+ * raises the same flags and only idx[b,K-1] = K.  K == 1 gives idx = 0.
+ * The CDFs live in LDS: K above 8192 or D above 256 return AESMC_ERR_UNSUPPORTED and launch nothing; B K == 0 is a no-op.
+ * No workspace.  Every check runs before any launch.
+ */
+int aesmc_conditional_ancestor_index(int dtype, const void *log_w, const double *u, const aesmc_view3 *loc,
+                                     const aesmc_view3 *target, const void *scale, int64_t scale_stride, int64_t *out_idx,
+                                     int32_t *flags, int64_t B, int64_t K, int64_t D, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
