@@ -48,6 +48,7 @@ else:
     _os.environ[HIPGRAPH_ENV] = "0"
     HIPGRAPH_MEMSET_WORKAROUND = "set"
 
+from . import adapted  # noqa: F401
 from . import inference  # noqa: F401
 from . import losses  # noqa: F401
 from . import marginal_filter  # noqa: F401

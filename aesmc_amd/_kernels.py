@@ -2189,6 +2189,85 @@ class HipKernels:
                      tuple(keep) + (log_w, u, idx) + tuple(views))
         return idx
 
+    # ---- K27 / K28 -----------------------------------------------------------------------------
+    ADAPTED_MAX_DIM = 16
+
+    @staticmethod
+    def adapted_covers(loc, latent_dim, observation_dim):
+        """Whether `affine_quadratic_logweight` / `adapted_draw` take a location like this: a float32 / float64 tensor
+        [B,K,D] on the HIP device with D = latent_dim, both extents in 1 .. 16, and B K D within 32-bit element
+        arithmetic."""
+        if not (torch.is_tensor(loc) and loc.is_cuda and loc.dtype in _DTYPE_TAG and loc.dim() == 3):
+            return False
+        limit = HipKernels.ADAPTED_MAX_DIM
+        return loc.size(2) == latent_dim and 1 <= latent_dim <= limit and 1 <= observation_dim <= limit and \
+            loc.size(0) * loc.size(1) <= 0x7fffffff // limit
+
+    def _adapted_operands(self, loc, what, **matrices):
+        """The dtype tag of a [B,K,D] location and its float64 companions checked: name -> (tensor, shape)."""
+        _require_hip(loc, what)
+        tag = _tag(loc, what)
+        if loc.dim() != 3:
+            raise ValueError("aesmc_amd: {} must be [batch_size, num_particles, dim], got {}".format(what, tuple(loc.shape)))
+        for name, (tensor, shape) in matrices.items():
+            _require_hip(tensor, name)
+            if tuple(tensor.shape) != tuple(shape) or tensor.dtype != torch.float64 or tensor.device != loc.device:
+                raise ValueError("aesmc_amd: {} must be {} float64 on {}, got {} {} on {}".format(
+                    name, tuple(shape), loc.device, tuple(tensor.shape), tensor.dtype, tensor.device))
+        return tag
+
+    def affine_quadratic_logweight(self, loc, P, offset, base):
+        """The first-stage log-weights of an adapted step (aesmc_affine_quadratic_logweight, K27): loc [B,K,D] (a view is
+        taken as it is), P float64 [Dy,D], offset float64 [B,Dy], base a Python float.  Returns [B,K] in loc's dtype:
+        base - 1/2 |P loc + offset|^2, evaluated in float64."""
+        B, K, D = loc.shape if torch.is_tensor(loc) and loc.dim() == 3 else (0, 0, 0)
+        Dy = P.size(0) if torch.is_tensor(P) and P.dim() == 2 else 0
+        tag = self._adapted_operands(loc, "location", P=(P, (Dy, D)), offset=(offset, (B, Dy)))
+        if not self.adapted_covers(loc, D, Dy):
+            raise ValueError("aesmc_amd: affine_quadratic_logweight does not take these operands (see adapted_covers)")
+        P, offset = P.contiguous(), offset.contiguous()
+        out = torch.empty((B, K), dtype=loc.dtype, device=loc.device)
+        if out.numel() == 0:
+            return out
+        view = _lib.View3(_ptr(loc), *loc.stride())
+        esz = loc.element_size()
+        self._launch(loc.device, self._lib.aesmc_affine_quadratic_logweight,
+                     (tag, ctypes.byref(view), _ptr(P), _ptr(offset), float(base), _ptr(out), B, K, D, Dy,
+                      self._stream(loc)),
+                     lambda: self._unique_bytes(loc) + B * K * esz + 8 * (Dy * D + B * Dy), (loc, P, offset, out, view))
+        return out
+
+    def adapted_draw(self, loc, index, M, offset, L, eps):
+        """The draw of an adapted step (aesmc_adapted_draw, K28): loc [B,K,D] the transition's location of the STORED
+        particles (a view is taken as it is), index int64 [B,K] or None (the identity), M and L float64 [D,D], offset
+        float64 [B,D], eps [B,K,D] standard-normal noise in loc's dtype.  Returns x [B,K,D]: offset + M loc[index] +
+        L eps, evaluated in float64.  An index outside [0, K) gives NaN there and FLAG_INDEX_OUT_OF_RANGE."""
+        B, K, D = loc.shape if torch.is_tensor(loc) and loc.dim() == 3 else (0, 0, 0)
+        tag = self._adapted_operands(loc, "location", M=(M, (D, D)), L=(L, (D, D)), offset=(offset, (B, D)))
+        _require_hip(eps, "noise")
+        self._expect(eps, loc.shape, loc, "noise")
+        if not self.adapted_covers(loc, D, D):
+            raise ValueError("aesmc_amd: adapted_draw does not take these operands (see adapted_covers)")
+        if index is not None:
+            index = as_index(index)
+            if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != loc.device:
+                raise ValueError("aesmc_amd: index must be [{}, {}] int64 on {}".format(B, K, loc.device))
+            index = index.contiguous()
+        M, L, offset, eps = M.contiguous(), L.contiguous(), offset.contiguous(), eps.contiguous()
+        if eps.data_ptr() % 16:      # (a slice of a larger block: the kernel stages the noise in 16-byte vectors)
+            eps = eps.clone()
+        out = torch.empty((B, K, D), dtype=loc.dtype, device=loc.device)
+        if out.numel() == 0:
+            return out
+        view = _lib.View3(_ptr(loc), *loc.stride())
+        esz = loc.element_size()
+        self._launch(loc.device, self._lib.aesmc_adapted_draw,
+                     (tag, ctypes.byref(view), _ptr(index), _ptr(M), _ptr(offset), _ptr(L), _ptr(eps), _ptr(out),
+                      _ptr(self.flags(loc.device)), B, K, D, self._stream(loc)),
+                     lambda: self._unique_bytes(loc) + B * K * (2 * D * esz + (8 if index is not None else 0)) +
+                     8 * (2 * D * D + B * D), (loc, index, M, offset, L, eps, out, view))
+        return out
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 

@@ -11,6 +11,7 @@ dtype / device behave) that hold no values:
   LazyResampled(source, index)       previous_latents[-1]: x_{t-1} re-indexed by the newest ancestors
   LazyDraw(location terms, noise)    latents[-1]: the proposal's reparameterised draw  loc_q + s_q * eps
   LazyInitialDraw(proposal, noise)   latents[-1] of the FIRST step: a BATCH_EXPANDED Normal's transposed draw
+  LazyGiven(values)                  latents[-1] the adapted filter hands its emission: a tensor that exists, handed out lazily
   LazyAffine(source, weight, offset) what `x @ W.t()`, `F.linear(x, W, b)`, `+ offset`, `scalar * x` of one of the
                                      above evaluate to: a location  offset + source @ weight.T
 
@@ -138,6 +139,30 @@ class LazyResampled(LazyParticles):
         return state.resample(self._lazy_source, self._lazy_index)
 
 
+class LazyGiven(LazyParticles):
+    """A [B,K,d] tensor that already has its values, handed out lazily all the same so that an affine expression a callable
+    writes on it (`x @ C.t() + d`) is RECORDED, not evaluated: `aesmc_amd.adapted` hands the emission the transition's
+    location in the newest latent's place and wants the emission's map of it, never its values.  Reading it costs
+    nothing."""
+
+    @staticmethod
+    def __new__(cls, values):
+        return LazyParticles._make(cls, values.shape, values)
+
+    def __init__(self, values):
+        self._lazy_grad_mode = torch.is_grad_enabled()
+        self._lazy_like = values
+        self.values = values
+        self._lazy_real = None
+        self._lazy_shape = values.shape
+
+    def _lazy_requires_grad(self):
+        return self.values.requires_grad
+
+    def _lazy_compute(self):
+        return self.values
+
+
 class LazyAffine(LazyParticles):
     """offset + source @ weight.T for a [B,K,din] particle tensor `source` (itself possibly lazy), weight [dout,din]
     (any 2-D view), offset None, [dout] or [B,dout]: a location nobody has evaluated."""
@@ -228,7 +253,7 @@ class LazyInitialDraw(LazyParticles):
 def _is_particles(value):
     """A pending lazy [B,K,d] particle tensor an affine map may be recorded on (not a location: maps of maps are
     evaluated)."""
-    return type(value) in (LazyResampled, LazyDraw, LazyInitialDraw) and value._lazy_real is None and \
+    return type(value) in (LazyResampled, LazyDraw, LazyInitialDraw, LazyGiven) and value._lazy_real is None and \
         len(value._lazy_shape) == 3
 
 

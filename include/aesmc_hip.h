@@ -70,7 +70,9 @@ extern "C" {
  *                aesmc_affine_step_backward_packed, aesmc_unpack_ancestors (a step's ancestry handed from K2 to K16 /
  *                K14 as one 32-bit word per particle);
  *                aesmc_conditional_ancestor_index (K26: conditional multinomial resampling with ancestor sampling,
- *                the resampling step of particle Gibbs).
+ *                the resampling step of particle Gibbs);
+ *                aesmc_affine_quadratic_logweight, aesmc_adapted_draw (K27, K28: the first-stage weights and the draw of
+ *                a fully adapted auxiliary particle filter step).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -530,6 +532,50 @@ int aesmc_pairwise_pass(int dtype, const aesmc_view3 *own, const aesmc_view3 *ot
 int aesmc_conditional_ancestor_index(int dtype, const void *log_w, const double *u, const aesmc_view3 *loc,
                                      const aesmc_view3 *target, const void *scale, int64_t scale_stride, int64_t *out_idx,
                                      int32_t *flags, int64_t B, int64_t K, int64_t D, void *stream);
+
+/* K27 — the first-stage log-weights of a fully adapted auxiliary particle filter (Pitt & Shephard 1999): for a Normal
+ * transition N(mu, S_f) with a constant diagonal S_f and an emission N(C x + d, S_g), the predictive likelihood
+ *   out[b,k] = base - 1/2 || P mu[b,k] + o_b ||^2  =  log p(y_t | x_{t-1}[b,k]),
+ * P = -W C, o_b = W (y_b - d_b), W the inverse Cholesky factor of S = C S_f C^T + S_g, base = -Dy/2 log 2 pi - log det
+ * chol(S): small float64 operands the host forms once.  The reference has no such call site.
+ *   loc     T [B,K,D] view by element strides (0 = broadcast)      the transition's location mu for every particle
+ *   P       float64 [Dy,D] dense
+ *   offset  float64 [B,Dy] dense
+ *   out     T [B,K] dense
+ * All arithmetic is in float64 whatever T is (float32 or float64, `dtype`):
+ *   r_j      = one chain of fused multiply-adds over i = 0 .. D-1 ascending, starting from offset[b,j], of
+ *              P[j,i] * (double)loc[b,k,i]
+ *   q        = one chain over j = 0 .. Dy-1 ascending, starting from 0, of r_j * r_j
+ *   out[b,k] = (T)(base - 0.5 q)
+ * A NaN location gives a NaN log-weight and nothing else: the resampling launch that follows raises
+ * AESMC_FLAG_NAN_LOG_WEIGHT by its own rules, so this entry takes no flags.
+ * D and Dy lie in 1 .. aesmc_affine_max_dim(); beyond that, or B K beyond 32-bit element arithmetic, the entry returns
+ * AESMC_ERR_UNSUPPORTED and launches nothing.  NULL pointers, negative sizes, D or Dy below 1 and a base not aligned to
+ * its element return AESMC_ERR_INVALID_ARGUMENT.  B K == 0 is a no-op.  Every check runs before any launch.
+ */
+int aesmc_affine_quadratic_logweight(int dtype, const aesmc_view3 *loc, const double *P, const double *offset, double base,
+                                     void *out, int64_t B, int64_t K, int64_t D, int64_t Dy, void *stream);
+
+/* K28 — the draw of a fully adapted auxiliary particle filter step: the optimal proposal p(x_t | x_{t-1}, y_t) =
+ * N(r_b + M mu, L L^T) with its full covariance, through the ancestors the resampling launch drew from K27's weights.
+ * M = I - G C, r_b = G (y_b - d_b), G = S_f C^T S^-1 the gain, L the Cholesky factor of S_f - G C S_f.
+ *   loc     T [B,K,D] view by element strides (0 = broadcast)      the transition's location for every STORED particle
+ *   idx     int64 [B,K] dense, or NULL for the identity; NOT assumed sorted
+ *   M, L    float64 [D,D] dense; of L only L[j,i] with i <= j is read
+ *   offset  float64 [B,D] dense
+ *   eps     T [B,K,D] dense, 16-byte aligned                       standard-normal noise
+ *   out     T [B,K,D] dense, 16-byte aligned; must not alias an input
+ * With a = idx ? idx[b,k] : k, out[b,k,j] is ONE chain of float64 fused multiply-adds rounded once to T, in this order:
+ *   start from offset[b,j];
+ *   add M[j,i] * (double)loc[b,a,i]   for i = 0 .. D-1;
+ *   add L[j,i] * (double)eps[b,k,i]   for i = 0 .. j.
+ * An `a` outside [0, K) reads nothing, writes NaN to that particle's D values and raises AESMC_FLAG_INDEX_OUT_OF_RANGE
+ * (K2 marks a flagged row with idx == K).
+ * D lies in 1 .. aesmc_affine_max_dim(); sizes, statuses and the no-op as K27's.
+ */
+int aesmc_adapted_draw(int dtype, const aesmc_view3 *loc, const int64_t *idx, const double *M, const double *offset,
+                       const double *L, const void *eps, void *out, int32_t *flags, int64_t B, int64_t K, int64_t D,
+                       void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
