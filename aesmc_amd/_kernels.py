@@ -2268,6 +2268,83 @@ class HipKernels:
                      8 * (2 * D * D + B * D), (loc, index, M, offset, L, eps, out, view))
         return out
 
+    # ---- K29 / K30 -----------------------------------------------------------------------------
+    def _adapted_workspace(self, device, B, K, D, Dy):
+        """The float64 partial sums of a K29 / K30 launch (aesmc_adapted_backward_workspace_bytes): allocated per call from
+        torch's caching allocator, which keeps the block per device like the other backward workspaces."""
+        ws_bytes = int(self._lib.aesmc_adapted_backward_workspace_bytes(B, K, D, Dy))
+        return torch.empty(ws_bytes, dtype=torch.uint8, device=device), ws_bytes
+
+    def affine_quadratic_logweight_backward(self, loc, P, offset, grad, need_loc=True, need_P=True, need_offset=True):
+        """The adjoint of `affine_quadratic_logweight` (aesmc_affine_quadratic_logweight_backward, K29) for the gradient
+        grad [B,K] (loc's dtype) arriving at its output: (grad_loc [B,K,D] in loc's dtype, dense; grad_P float64 [Dy,D];
+        grad_offset float64 [B,Dy]), None where `need_*` is false.  The gradient of `base` is grad.sum(): the caller's."""
+        B, K, D = loc.shape if torch.is_tensor(loc) and loc.dim() == 3 else (0, 0, 0)
+        Dy = P.size(0) if torch.is_tensor(P) and P.dim() == 2 else 0
+        tag = self._adapted_operands(loc, "location", P=(P, (Dy, D)), offset=(offset, (B, Dy)))
+        _require_hip(grad, "gradient")
+        self._expect(grad, loc.shape[:2], loc, "gradient")
+        if not self.adapted_covers(loc, D, Dy):
+            raise ValueError("aesmc_amd: affine_quadratic_logweight_backward does not take these operands (see "
+                             "adapted_covers)")
+        P, offset, grad = P.contiguous(), offset.contiguous(), grad.contiguous()
+        f64 = lambda shape, wanted: torch.empty(shape, dtype=torch.float64, device=loc.device) if wanted else None
+        grad_loc = torch.empty((B, K, D), dtype=loc.dtype, device=loc.device) if need_loc else None
+        grad_P, grad_offset = f64((Dy, D), need_P), f64((B, Dy), need_offset)
+        if B * K == 0 or not (need_loc or need_P or need_offset):
+            return (grad_loc,) + tuple(None if t is None else t.zero_() for t in (grad_P, grad_offset))
+        ws, ws_bytes = self._adapted_workspace(loc.device, B, K, D, Dy) if (need_P or need_offset) else (None, 0)
+        view = _lib.View3(_ptr(loc), *loc.stride())
+        esz = loc.element_size()
+        self._launch(loc.device, self._lib.aesmc_affine_quadratic_logweight_backward,
+                     (tag, ctypes.byref(view), _ptr(P), _ptr(offset), _ptr(grad), _ptr(grad_loc), _ptr(grad_P),
+                      _ptr(grad_offset), _ptr(ws), ws_bytes, B, K, D, Dy, self._stream(loc)),
+                     lambda: self._unique_bytes(loc) + B * K * esz * (1 + (D if need_loc else 0)) +
+                     8 * (2 * Dy * D + 2 * B * Dy), (loc, P, offset, grad, grad_loc, grad_P, grad_offset, ws, view))
+        return grad_loc, grad_P, grad_offset
+
+    def adapted_draw_backward(self, loc, index, M, L, eps, grad, need_h=True, need_M=True, need_L=True, need_r=True):
+        """The adjoint of `adapted_draw` (aesmc_adapted_draw_backward, K30) for the gradient grad [B,K,D] arriving at its
+        output: (h [B,K,D] in loc's dtype — the gradient of the GATHERED rows loc[b, index[b,k]]: `gather_backward` makes
+        the location's of it —, grad_M float64 [D,D], grad_L float64 [D,D] (exactly zero above the diagonal), grad_r
+        float64 [B,D]: the gradient of `offset`), None where `need_*` is false.  L is taken for its shape only.  An index
+        outside [0, K) contributes nothing, gives a NaN row of h and FLAG_INDEX_OUT_OF_RANGE."""
+        B, K, D = loc.shape if torch.is_tensor(loc) and loc.dim() == 3 else (0, 0, 0)
+        tag = self._adapted_operands(loc, "location", M=(M, (D, D)), L=(L, (D, D)))
+        for name, t in (("noise", eps), ("gradient", grad)):
+            _require_hip(t, name)
+            self._expect(t, loc.shape, loc, name)
+        if not self.adapted_covers(loc, D, D):
+            raise ValueError("aesmc_amd: adapted_draw_backward does not take these operands (see adapted_covers)")
+        if index is not None:
+            index = as_index(index)
+            if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != loc.device:
+                raise ValueError("aesmc_amd: index must be [{}, {}] int64 on {}".format(B, K, loc.device))
+            index = index.contiguous()
+        M, eps, grad = M.contiguous(), eps.contiguous(), grad.contiguous()
+        if eps.data_ptr() % 16:      # (slices of larger blocks: the kernel reads both in 16-byte vectors)
+            eps = eps.clone()
+        if grad.data_ptr() % 16:
+            grad = grad.clone()
+        f64 = lambda shape, wanted: torch.empty(shape, dtype=torch.float64, device=loc.device) if wanted else None
+        h = torch.empty((B, K, D), dtype=loc.dtype, device=loc.device) if need_h else None
+        grad_M, grad_L, grad_r = f64((D, D), need_M), f64((D, D), need_L), f64((B, D), need_r)
+        if B * K == 0 or not (need_h or need_M or need_L or need_r):
+            return (h,) + tuple(None if t is None else t.zero_() for t in (grad_M, grad_L, grad_r))
+        reduces = need_M or need_L or need_r
+        ws, ws_bytes = self._adapted_workspace(loc.device, B, K, D, D) if reduces else (None, 0)
+        view = _lib.View3(_ptr(loc), *loc.stride())
+        esz = loc.element_size()
+        self._launch(loc.device, self._lib.aesmc_adapted_draw_backward,
+                     (tag, ctypes.byref(view), _ptr(index), _ptr(M), _ptr(eps), _ptr(grad), _ptr(h), _ptr(grad_M),
+                      _ptr(grad_L), _ptr(grad_r), _ptr(self.flags(loc.device)), _ptr(ws), ws_bytes, B, K, D,
+                      self._stream(loc)),
+                     lambda: (self._unique_bytes(loc) if need_M else 0) +
+                     B * K * (D * esz * (1 + (1 if need_L else 0) + (1 if need_h else 0)) +
+                              (8 if index is not None else 0)) + 8 * (3 * D * D + B * D),
+                     (loc, index, M, eps, grad, h, grad_M, grad_L, grad_r, ws, view))
+        return h, grad_M, grad_L, grad_r
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 

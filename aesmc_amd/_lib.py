@@ -118,6 +118,11 @@ SIGNATURES = {
     "aesmc_affine_quadratic_logweight": (_i32, [_i32, ctypes.POINTER(View3), _vp, _vp, ctypes.c_double, _vp, _i64, _i64, _i64,
                                                 _i64, _vp]),
     "aesmc_adapted_draw": (_i32, [_i32, ctypes.POINTER(View3), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "aesmc_adapted_backward_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "aesmc_affine_quadratic_logweight_backward": (_i32, [_i32, ctypes.POINTER(View3), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                         _i64, _i64, _i64, _i64, _vp]),
+    "aesmc_adapted_draw_backward": (_i32, [_i32, ctypes.POINTER(View3), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _i64, _i64, _i64, _i64, _vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

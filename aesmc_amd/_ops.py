@@ -1011,3 +1011,76 @@ def affine_propagate(operands, eps):
     x_prev = (x_prev.materialise() if isinstance(x_prev, LazyParticles) else x_prev).detach()
     return k.affine_propagate(x_prev, eps, y_rows, (A, off_p), (C, off_g), (Q, off_q),
                               (s_p, s_g, s_q), out_x=x, checked=True)    # state._affine_step_operands did
+
+
+# ---- the fully adapted step (K27 / K28) and its backward (K29 / K30) ---------------------------------
+class _AffineQuadraticLogweight(torch.autograd.Function):
+    """out[b,k] = base - 1/2 |P loc[b,k] + offset[b]|^2 (kernel K27, unchanged); the backward is one launch of K29 —
+    grad_loc, grad_P and grad_offset, each only where asked for — and grad_base = the sum of the arriving gradient.
+    First order only."""
+
+    @staticmethod
+    def forward(ctx, loc, P, offset, base, base_value):
+        out = _kernels.get().affine_quadratic_logweight(loc, P, offset, float(base) if base_value is None else base_value)
+        ctx.save_for_backward(loc, P, offset)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        loc, P, offset = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grad_loc = grad_P = grad_offset = None
+        if need[0] or need[1] or need[2]:
+            grad_loc, grad_P, grad_offset = _kernels.get().affine_quadratic_logweight_backward(
+                loc, P, offset, grad, need_loc=need[0], need_P=need[1], need_offset=need[2])
+        grad_base = grad.to(torch.float64).sum() if need[3] else None
+        return grad_loc, grad_P, grad_offset, grad_base, None
+
+
+def affine_quadratic_logweight(loc, P, offset, base, base_value=None):
+    """The first-stage log-weights of an adapted step [B,K] (kernel K27; operands as `HipKernels.affine_quadratic_logweight`
+    takes them, `base` a 0-dim float64 tensor), differentiable in all four operands through K29.  `base_value`: base's value
+    as a Python float where the caller has it (the forward then reads nothing back from the device)."""
+    operands = (loc, P, offset, base)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
+        return _AffineQuadraticLogweight.apply(loc, P, offset, base, base_value)
+    return _kernels.get().affine_quadratic_logweight(loc.detach(), P.detach(), offset.detach(),
+                                                     float(base) if base_value is None else base_value)
+
+
+class _AdaptedDraw(torch.autograd.Function):
+    """x[b,k] = offset[b] + M loc[b, index[b,k]] + L eps[b,k] (kernel K28, unchanged).  The backward is one launch of K30
+    (h = grad M per particle, grad_M, grad_L with zeros above the diagonal, grad_offset) and, for the location, the sorted
+    segmented sum of h over equal ancestors (aesmc_resample_gather_backward).  The ancestors are held fixed and the noise
+    takes no gradient.  First order only."""
+
+    @staticmethod
+    def forward(ctx, loc, index, M, offset, L, eps):
+        out = _kernels.get().adapted_draw(loc, index, M, offset, L, eps)
+        ctx.save_for_backward(loc, M, L, eps)
+        ctx.index = index
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        loc, M, L, eps = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        k = _kernels.get()
+        grad_loc = grad_M = grad_offset = grad_L = None
+        if need[0] or need[2] or need[3] or need[4]:
+            h, grad_M, grad_L, grad_offset = k.adapted_draw_backward(
+                loc, ctx.index, M, L, eps, grad, need_h=need[0], need_M=need[2], need_L=need[4], need_r=need[3])
+            if need[0]:
+                grad_loc = h if ctx.index is None else k.gather_backward(h, ctx.index, sorted_index=True)
+        return grad_loc, None, grad_M, grad_offset, grad_L, None
+
+
+def adapted_draw(loc, index, M, offset, L, eps):
+    """The draw of an adapted step [B,K,D] (kernel K28; operands as `HipKernels.adapted_draw` takes them, `index` the
+    SORTED ancestors of a resampling launch or None), differentiable in loc, M, offset and L through K30."""
+    operands = (loc, M, offset, L)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
+        return _AdaptedDraw.apply(loc, None if index is None else _kernels.as_index(index), M, offset, L, eps.detach())
+    return _kernels.get().adapted_draw(loc.detach(), index, M.detach(), offset.detach(), L.detach(), eps.detach())

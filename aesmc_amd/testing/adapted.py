@@ -285,3 +285,145 @@ def kalman_filter(A, C, s_f, s_g, loc0, scale0, ys):
         means.append(mean.copy()), covs.append(cov.copy())
     means, covs = np.stack(means), np.stack(covs)
     return (means, covs, total) if batched else (means[:, 0], covs, total[0])
+
+
+# ---- K29 / K30: the adjoints of the two launches ------------------------------------------------------------------------
+def _unit_of(dtype):
+    """The unit roundoff of the particles' dtype (what one rounding to T costs, relative)."""
+    return 2.0 ** -24 if np.dtype(dtype) == np.float32 else UNIT
+
+
+def affine_quadratic_logweight_backward(loc, P, offset, grad):
+    """(grad_loc [B,K,D] in loc's dtype, grad_P float64 [Dy,D], grad_offset float64 [B,Dy]) of `affine_quadratic_logweight`
+    for the gradient grad [B,K] arriving at its output, from plain float64 matrix products: with rho = loc P^T + offset
+    and w = -grad rho,  grad_loc = w P,  grad_P = sum_{b,k} w (outer) loc,  grad_offset = sum_k w.  (The gradient of
+    `base` is grad.sum().)"""
+    loc = np.asarray(loc)
+    x = loc.astype(np.float64)
+    P, offset = np.asarray(P, dtype=np.float64), np.asarray(offset, dtype=np.float64)
+    g = np.asarray(grad).astype(np.float64)
+    w = -g[:, :, None] * (x @ P.T + offset[:, None, :])
+    return (w @ P).astype(loc.dtype), np.einsum("bkj,bki->ji", w, x), w.sum(axis=1)
+
+
+def affine_quadratic_logweight_backward_bound(loc, P, offset, grad):
+    """(bound of grad_loc [B,K,D], of grad_P [Dy,D], of grad_offset [B,Dy]), float64: how far the kernel's outputs may
+    lie from `affine_quadratic_logweight_backward`'s, derived and not measured.  u = 2^-53, u_T the unit roundoff of loc's
+    dtype, A_j = |offset_j| + sum_i |P_ji loc_i| (which bounds |rho_j|), |w_j| <= |grad| A_j, and w_j itself is a chain of
+    D additions and one product: off by at most (D + 2) u |grad| A_j from the exact value.
+
+        grad_loc_i     a chain of Dy multiply-adds over terms of total size T_i = sum_j |grad| A_j |P_ji|:
+                       2 * 1.01 * (Dy + 1 + D + 2) u T_i  +  2 u_T T_i          (two evaluations; each rounds once to T)
+        grad_P_ji      a sum of B K terms in any order, each a chain of D + 2 operations:
+                       2 * 1.01 * (B K + D + 2) u sum_{b,k} |grad| A_j |loc_i|
+        grad_offset_bj 2 * 1.01 * (K + D + 2) u sum_k |grad| A_j"""
+    loc = np.asarray(loc)
+    x = np.abs(loc.astype(np.float64))
+    P, offset = np.abs(np.asarray(P, dtype=np.float64)), np.abs(np.asarray(offset, dtype=np.float64))
+    g = np.abs(np.asarray(grad).astype(np.float64))
+    B, K, D = x.shape
+    Dy = P.shape[0]
+    size = g[:, :, None] * (offset[:, None, :] + x @ P.T)                     # |grad| A_j  [B,K,Dy]
+    chain = size @ P
+    bound_loc = 2 * 1.01 * (Dy + D + 3) * UNIT * chain + 2 * _unit_of(loc.dtype) * chain
+    bound_P = 2 * 1.01 * (B * K + D + 2) * UNIT * np.einsum("bkj,bki->ji", size, x)
+    bound_offset = 2 * 1.01 * (K + D + 2) * UNIT * size.sum(axis=1)
+    return bound_loc, bound_P, bound_offset
+
+
+def adapted_draw_backward(loc, idx, M, L, eps, grad):
+    """(h [B,K,D] in eps' dtype, grad_M [D,D], grad_L [D,D], grad_r [B,D] float64, flags) of `adapted_draw` for the
+    gradient grad [B,K,D] arriving at its output, from plain float64 matrix products: with a = idx[b,k] (None: k),
+    h = grad M (the gradient of the gathered row loc[b,a]),  grad_M = sum_{b,k} grad (outer) loc[b,a],  grad_L = the lower
+    triangle of sum_{b,k} grad (outer) eps (exactly zero above the diagonal),  grad_r = sum_k grad.  L is taken for its
+    shape only.  An `a` outside [0, K) contributes nothing to the three sums, gives a NaN row of h and
+    FLAG_INDEX_OUT_OF_RANGE."""
+    eps = np.asarray(eps)
+    B, K, D = eps.shape
+    x = np.broadcast_to(np.asarray(loc), (B, K, D)).astype(np.float64)
+    M = np.asarray(M, dtype=np.float64)
+    assert np.asarray(L).shape == (D, D)
+    G = np.asarray(grad).astype(np.float64)
+    flags = 0
+    bad = np.zeros((B, K), dtype=bool)
+    if idx is not None:
+        idx = np.asarray(idx)
+        bad = (idx < 0) | (idx >= K)
+        if bad.any():
+            flags |= FLAG_INDEX_OUT_OF_RANGE
+        x = np.take_along_axis(x, np.where(bad, 0, idx)[:, :, None], axis=1)
+    counted = np.where(bad[:, :, None], 0.0, G)
+    x = np.where(bad[:, :, None], 0.0, x)
+    h = G @ M
+    h[bad] = np.nan
+    grad_M = np.einsum("bkj,bki->ji", counted, x)
+    grad_L = np.tril(np.einsum("bkj,bki->ji", counted, eps.astype(np.float64)))
+    return h.astype(eps.dtype), grad_M, grad_L, counted.sum(axis=1), flags
+
+
+def adapted_draw_backward_bound(loc, idx, M, L, eps, grad):
+    """(bound of h [B,K,D], of grad_M [D,D], of grad_L [D,D], of grad_r [B,D]), float64: the counterpart of
+    `affine_quadratic_logweight_backward_bound`.  The operands enter exactly, so every term is one product:
+
+        h_i        a chain of D multiply-adds over terms of total size T_i = sum_j |grad_j M_ji|:
+                   2 * 1.01 * (D + 1) u T_i + 2 u_T T_i           (zero where the index is out of range: NaN there)
+        grad_M_ji  2 * 1.01 * (B K + 1) u sum_{b,k} |grad_j loc[b,a]_i|      grad_L_ji likewise with eps, zero above the
+        grad_r_bj  2 * 1.01 * (K + 1) u sum_k |grad_j|                       diagonal."""
+    eps = np.asarray(eps)
+    B, K, D = eps.shape
+    sized = adapted_draw_backward(np.abs(np.asarray(loc)).astype(np.float64), idx, np.abs(np.asarray(M, dtype=np.float64)), L,
+                                  np.abs(eps).astype(np.float64), np.abs(np.asarray(grad)).astype(np.float64))
+    chain = np.where(np.isnan(sized[0]), 0.0, sized[0])
+    bound_h = 2 * 1.01 * (D + 1) * UNIT * chain + 2 * _unit_of(eps.dtype) * chain
+    factor = 2 * 1.01 * (B * K + 1) * UNIT
+    return bound_h, factor * sized[1], factor * sized[2], 2 * 1.01 * (K + 1) * UNIT * sized[3]
+
+
+# ---- the whole differentiable filter, restated in PyTorch ------------------------------------------------------------------
+def adapted_elbo_restated(observations, loc0, scale0, location, transition_scale, weight, emission_offset, emission_scale,
+                          noise, ancestors, dtype=None):
+    """What `aesmc_amd.adapted.adapted_elbo` computes and differentiates, restated with torch.distributions, torch.linalg
+    and torch.gather — no kernel, no `_ops` function, no provider — for GIVEN noise (T x [B,K,D]) and GIVEN ancestors
+    ((T-1) x int64 [B,K], held fixed: they carry no gradient).  observations: T x [B,Dy]; loc0 [D] or [B,D]; scale0,
+    transition_scale, emission_scale: tensors of one value or one per dimension; location(x [B,K,D], t) -> the transition's
+    location of the stored particles x of time t-1 (a differentiable torch function); weight: C [Dy,D]; emission_offset:
+    None, [Dy] or [B,Dy].  `dtype` (default torch.float64): what everything is computed in.  Any of the tensors may
+    require grad.  Returns a dict: log_marginal_likelihood [B] (on the tape), latents (T x [B,K,D]).
+
+        log p(y_t | x_{t-1}) = MultivariateNormal(C mu + d, C S_f C^T + S_g).log_prob(y_t)
+        x_t = mu[a] + (y_t - d - C mu[a]) G^T + eps chol(S_f - G C S_f)^T,   G = S_f C^T S^-1   (torch.linalg.solve)"""
+    import torch
+    dtype = torch.float64 if dtype is None else dtype
+    cast = lambda t: None if t is None else t.to(dtype)
+    C, d = cast(weight), cast(emission_offset)
+    Dy, D = C.shape
+    B, K = noise[0].shape[:2]
+    variances = lambda scale, size: (cast(scale).reshape(-1) ** 2).expand(size)
+    var_g = variances(emission_scale, Dy)
+
+    def step(mu, var_f, y, eps, index):
+        """(log p(y | x_{t-1}) [B,K], x_t [B,K,D]) for the locations mu [B,K,D] of the stored particles."""
+        S = (C * var_f) @ C.t() + torch.diag(var_g)
+        predicted = mu @ C.t() + (0.0 if d is None else (d.unsqueeze(1) if d.dim() == 2 else d))
+        log_lambda = torch.distributions.MultivariateNormal(predicted, covariance_matrix=S, validate_args=False).log_prob(
+            y.unsqueeze(1))
+        G = torch.linalg.solve(S, C * var_f).t()                           # S_f C^T S^-1  [D,Dy]
+        sigma = torch.diag(var_f) - G @ (C * var_f)
+        chol = torch.linalg.cholesky(0.5 * (sigma + sigma.t()))
+        if index is not None:
+            expanded = index.unsqueeze(-1).expand(-1, -1, D)
+            mu, predicted = torch.gather(mu, 1, expanded), torch.gather(predicted, 1, index.unsqueeze(-1).expand(-1, -1, Dy))
+        x = mu + (y.unsqueeze(1) - predicted) @ G.t() + cast(eps) @ chol.t()
+        return log_lambda, x
+
+    ys = [cast(y) for y in observations]
+    start = cast(loc0).expand(B, D).unsqueeze(1).expand(B, K, D)
+    log_lambda, x = step(start, variances(scale0, D), ys[0], noise[0], None)
+    log_z = log_lambda[:, 0]                                               # log p(y_0), exact
+    latents = [x]
+    var_f = variances(transition_scale, D)
+    for t in range(1, len(ys)):
+        log_lambda, x = step(location(latents[-1], t), var_f, ys[t], noise[t], ancestors[t - 1])
+        log_z = log_z + torch.logsumexp(log_lambda, dim=1) - np.log(K)
+        latents.append(x)
+    return {"log_marginal_likelihood": log_z, "latents": latents}

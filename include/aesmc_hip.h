@@ -72,7 +72,9 @@ extern "C" {
  *                aesmc_conditional_ancestor_index (K26: conditional multinomial resampling with ancestor sampling,
  *                the resampling step of particle Gibbs);
  *                aesmc_affine_quadratic_logweight, aesmc_adapted_draw (K27, K28: the first-stage weights and the draw of
- *                a fully adapted auxiliary particle filter step).
+ *                a fully adapted auxiliary particle filter step);
+ *                aesmc_affine_quadratic_logweight_backward, aesmc_adapted_draw_backward,
+ *                aesmc_adapted_backward_workspace_bytes (K29, K30: their adjoints, for training through the adapted filter).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -576,6 +578,47 @@ int aesmc_affine_quadratic_logweight(int dtype, const aesmc_view3 *loc, const do
 int aesmc_adapted_draw(int dtype, const aesmc_view3 *loc, const int64_t *idx, const double *M, const double *offset,
                        const double *L, const void *eps, void *out, int32_t *flags, int64_t B, int64_t K, int64_t D,
                        void *stream);
+
+/* Bytes of workspace K29 / K30 need for these extents (float64 partial sums: a fixed block for the matrices, 256 bytes
+ * per 64 particles for the batch rows' sums); 0 for extents the entries do not launch for. */
+int64_t aesmc_adapted_backward_workspace_bytes(int64_t B, int64_t K, int64_t D, int64_t Dy);
+
+/* K29 — the adjoint of K27.  With rho[b,k,j] = offset[b,j] + sum_i P[j,i] loc[b,k,i] evaluated by K27's own chain and
+ * w[b,k,j] = -(grad[b,k] * rho[b,k,j]) (one rounding, float64):
+ *   grad_loc[b,k,i]   = sum_j w[b,k,j] P[j,i]        T [B,K,D] dense, 16-byte aligned: ONE chain of float64 fused
+ *                                                    multiply-adds over j = 0 .. Dy-1 ascending from zero, rounded once
+ *   grad_P[j,i]       = sum_{b,k} w[b,k,j] loc[b,k,i]  float64 [Dy,D]
+ *   grad_offset[b,j]  = sum_k w[b,k,j]                 float64 [B,Dy]
+ * (the gradient of `base` is the sum of grad: the caller's).  loc, P, offset as K27 takes them; grad T [B,K] dense.
+ * Each of the three outputs may be NULL (not wanted, not computed); all three NULL is an invalid argument.
+ * The two reductions use no floating-point atomics and one fixed order of additions for given extents — the float64
+ * matrix cores over each wavefront's 64 particles, the wavefronts of a workgroup in order, the workgroups (batch rows:
+ * the 64-particle chunks) in order in a second launch: the same operands give the same bits.
+ * workspace: aesmc_adapted_backward_workspace_bytes(B, K, D, Dy) bytes, 8-byte aligned; needed unless grad_P and
+ * grad_offset are both NULL.  Sizes, statuses and the no-op as K27's; an output that aliases its input is an invalid
+ * argument.  Every check runs before any launch.
+ */
+int aesmc_affine_quadratic_logweight_backward(int dtype, const aesmc_view3 *loc, const double *P, const double *offset,
+                                              const void *grad, void *grad_loc, double *grad_P, double *grad_offset,
+                                              void *workspace, int64_t workspace_bytes, int64_t B, int64_t K, int64_t D,
+                                              int64_t Dy, void *stream);
+
+/* K30 — the adjoint of K28 for the gradient `grad` T [B,K,D] (dense, 16-byte aligned) arriving at its output.  With
+ * a = idx ? idx[b,k] : k:
+ *   h[b,k,i]      = sum_j grad[b,k,j] M[j,i]             T [B,K,D] dense, 16-byte aligned: ONE chain over j = 0 .. D-1
+ *                                                        ascending from zero, rounded once — the gradient of the
+ *                                                        GATHERED row loc[b,a,:]; summing it over equal ancestors
+ *                                                        (aesmc_resample_gather_backward) is the caller's
+ *   grad_M[j,i]   = sum_{b,k} grad[b,k,j] loc[b,a,i]     float64 [D,D]
+ *   grad_L[j,i]   = sum_{b,k} grad[b,k,j] eps[b,k,i]     float64 [D,D] for i <= j; exactly 0 above the diagonal
+ *   grad_r[b,j]   = sum_k grad[b,k,j]                    float64 [B,D]  (the gradient of K28's `offset`)
+ * Each of the four outputs may be NULL; all four NULL is an invalid argument.  L's values are not needed.  An `a` outside
+ * [0, K) reads nothing and contributes nothing to the three sums; that particle's h row is NaN and
+ * AESMC_FLAG_INDEX_OUT_OF_RANGE is raised.  Reductions, workspace, sizes and statuses as K29's.
+ */
+int aesmc_adapted_draw_backward(int dtype, const aesmc_view3 *loc, const int64_t *idx, const double *M, const void *eps,
+                                const void *grad, void *h, double *grad_M, double *grad_L, double *grad_r, int32_t *flags,
+                                void *workspace, int64_t workspace_bytes, int64_t B, int64_t K, int64_t D, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
