@@ -49,6 +49,7 @@ else:
     HIPGRAPH_MEMSET_WORKAROUND = "set"
 
 from . import adapted  # noqa: F401
+from . import rao_blackwell  # noqa: F401
 from . import inference  # noqa: F401
 from . import losses  # noqa: F401
 from . import marginal_filter  # noqa: F401

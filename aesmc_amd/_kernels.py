@@ -2345,6 +2345,91 @@ class HipKernels:
                      (loc, index, M, eps, grad, h, grad_M, grad_L, grad_r, ws, view))
         return h, grad_M, grad_L, grad_r
 
+    # ---- K31 -----------------------------------------------------------------------------------
+    SWITCHING_MODEL_KEYS = ("cdf0", "cdf", "m0", "s0", "A", "b", "q", "C", "d", "r")
+
+    def switching_limits(self):
+        """(largest D, largest Dy, largest M) of `switching_kalman_step`, as the library exports them."""
+        return (int(self._lib.aesmc_switching_max_latent_dim()), int(self._lib.aesmc_switching_max_observation_dim()),
+                int(self._lib.aesmc_switching_max_regimes()))
+
+    def switching_covers(self, observation, num_regimes, latent_dim, observation_dim, num_particles):
+        """Whether `switching_kalman_step` takes a step like this: a float32 / float64 observation [B,Dy] on the HIP device
+        with Dy = observation_dim, 1 <= D <= 8, 1 <= Dy <= 8, 1 <= M <= 16, and B K D(D+1)/2 within 32-bit element
+        arithmetic."""
+        if not (torch.is_tensor(observation) and observation.is_cuda and observation.dtype in _DTYPE_TAG and
+                observation.dim() == 2 and observation.size(1) == observation_dim):
+            return False
+        max_d, max_dy, max_m = self.switching_limits()
+        return 1 <= latent_dim <= max_d and 1 <= observation_dim <= max_dy and 1 <= num_regimes <= max_m and \
+            observation.size(0) * num_particles <= 0x7fffffff // (max_d * (max_d + 1) // 2)
+
+    def switching_kalman_step(self, model, state, index, uniforms, observation):
+        """One step of the Rao-Blackwellised filter of a switching linear-Gaussian model (aesmc_switching_kalman_step, K31).
+        model: a dict of dense float64 tensors cdf0 [M], cdf [M,M], m0 [D], s0 [D], A [M,D,D], b [M,D], q [M,D], C [M,Dy,D],
+        d [M,Dy], r [M,Dy]; state: None (step 0) or (regime int32 [B,K], mean float64 [B,K,D], cov float64 [B,K,D(D+1)/2])
+        — the STORED particles of the step before; index: int64 [B,K] or None (the identity); uniforms float64 [B,K];
+        observation float32 / float64 [B,Dy].  Returns (regime, mean, cov, log_weight [B,K] float64), new tensors.  An index
+        outside [0, K) or a stored regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        _require_hip(uniforms, "regime uniforms")
+        device = observation.device
+        if uniforms.dim() != 2 or uniforms.dtype != torch.float64 or uniforms.device != device:
+            raise ValueError("aesmc_amd: regime uniforms must be [batch_size, num_particles] float64 on {}".format(device))
+        B, K = uniforms.shape
+        A, C = model["A"], model["C"]
+        M, D, Dy = (A.size(0), A.size(2), C.size(1)) if torch.is_tensor(A) and A.dim() == 3 and torch.is_tensor(C) and \
+            C.dim() == 3 else (0, 0, 0)
+        TD = D * (D + 1) // 2
+        shapes = {"cdf0": (M,), "cdf": (M, M), "m0": (D,), "s0": (D,), "A": (M, D, D), "b": (M, D), "q": (M, D),
+                  "C": (M, Dy, D), "d": (M, Dy), "r": (M, Dy)}
+        for name in self.SWITCHING_MODEL_KEYS:
+            tensor = model[name]
+            _require_hip(tensor, name)
+            if tuple(tensor.shape) != shapes[name] or tensor.dtype != torch.float64 or tensor.device != device or \
+                    not tensor.is_contiguous():
+                raise ValueError("aesmc_amd: {} must be dense {} float64 on {}, got {} {} on {}".format(
+                    name, shapes[name], device, tuple(tensor.shape), tensor.dtype, tensor.device))
+        if tuple(observation.shape) != (B, Dy):
+            raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
+        if not self.switching_covers(observation, M, D, Dy, K):
+            raise ValueError("aesmc_amd: switching_kalman_step does not take these operands (see switching_covers)")
+        if state is not None:
+            regime, mean, cov = state
+            for tensor, shape, dtype, what in ((regime, (B, K), torch.int32, "regime"), (mean, (B, K, D), torch.float64, "mean"),
+                                               (cov, (B, K, TD), torch.float64, "cov")):
+                _require_hip(tensor, what)
+                if tuple(tensor.shape) != shape or tensor.dtype != dtype or tensor.device != device:
+                    raise ValueError("aesmc_amd: {} must be {} {} on {}".format(what, shape, dtype, device))
+            regime, mean, cov = regime.contiguous(), mean.contiguous(), cov.contiguous()
+            if index is not None:
+                index = as_index(index)
+                if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != device:
+                    raise ValueError("aesmc_amd: index must be [{}, {}] int64 on {}".format(B, K, device))
+                index = index.contiguous()
+        else:
+            regime = mean = cov = index = None
+        uniforms, observation = uniforms.contiguous(), observation.contiguous()
+        out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
+        out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
+        out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
+        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
+        if log_weight.numel() == 0:
+            return out_regime, out_mean, out_cov, log_weight
+        block = _lib.SwitchingModel(*([_ptr(model[name]) for name in self.SWITCHING_MODEL_KEYS] + [M, D, Dy]))
+        per_particle = 8 + 2 * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) if state is not None else \
+            8 + (4 + 8 * D + 8 * TD) + 8
+        self._launch(device, self._lib.aesmc_switching_kalman_step,
+                     (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
+                      _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_weight),
+                      _ptr(self.flags(device)), B, K, self._stream(observation)),
+                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
+                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                     (model, regime, mean, cov, index, uniforms, observation, out_regime, out_mean, out_cov, log_weight,
+                      block), name="switching_kalman_step")
+        return out_regime, out_mean, out_cov, log_weight
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 

@@ -55,6 +55,12 @@ class AffineChain(ctypes.Structure):
                 ("records", ctypes.c_int32), ("pairs_in", ctypes.c_void_p), ("pairs_out", ctypes.c_void_p)]
 
 
+class SwitchingModel(ctypes.Structure):
+    """`aesmc_switching_model` of include/aesmc_hip.h: the float64 operands of a switching linear-Gaussian model."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("cdf0", "cdf", "m0", "s0", "A", "b", "q", "C", "d", "r")] + \
+        [(name, ctypes.c_int64) for name in ("M", "D", "Dy")]
+
+
 # name -> (restype, argtypes); mirrors include/aesmc_hip.h one to one.
 SIGNATURES = {
     "aesmc_version": (_i32, []),
@@ -123,6 +129,10 @@ SIGNATURES = {
                                                          _i64, _i64, _i64, _i64, _vp]),
     "aesmc_adapted_draw_backward": (_i32, [_i32, ctypes.POINTER(View3), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _i64, _i64, _i64, _i64, _vp]),
+    "aesmc_switching_max_latent_dim": (_i64, []),
+    "aesmc_switching_max_observation_dim": (_i64, []),
+    "aesmc_switching_max_regimes": (_i64, []),
+    "aesmc_switching_kalman_step": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 11 + [_i64, _i64, _vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

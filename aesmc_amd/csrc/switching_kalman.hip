@@ -1,0 +1,386 @@
+// One step of the Rao-Blackwellised particle filter (mixture Kalman filter; Doucet, de Freitas, Murphy & Russell 2000; Chen &
+// Liu 2000) for a switching linear-Gaussian state-space model — aesmc_switching_kalman_step (K31) of include/aesmc_hip.h.
+//
+// Only the regimes are sampled.  Particle k of batch row b carries (s, m, P): its regime and the exact Kalman mean and
+// covariance of the continuous state given its regime history.  One launch, per particle: the gather through the ancestors,
+// the inverse-CDF regime draw, the Kalman predict, the Dy x Dy Cholesky factor of the innovation covariance, two triangular
+// solves, the rank-Dy downdate and the predictive log-likelihood, which is the particle's weight.
+//
+//   workgroup = 256 consecutive particles of the flattened [B K] range, one lane per particle;
+//   model     every regime's A, b, q^2, C, d, r^2 and the cumulative rows of the chain staged once per workgroup into LDS
+//             as float64, zero-padded to the instantiation's extents (r^2 padded with ONE: the padded pivots are 1, their
+//             logarithms 0) — 20 KB + 2 KB at M = 16, D = Dy = 8; a lane reads the block of ITS regime (a broadcast where
+//             the lanes of a wavefront agree, a bank conflict per distinct regime where they do not);
+//   state     the lane's m, P (packed lower triangle), the innovation covariance S and V = Lam^-1 C P- live in registers;
+//             the kernel is templated on the padded extents DP of D and DYP of Dy (2, 4, 8 each), all loops fully unrolled;
+//             the predict forms W = A P and then P-_ij = A_i . W_j, the innovation U = C P- and S_ij = C_i . U_j: each row
+//             of A and C serves one block of the code and is read from LDS again in the next (SK_REREAD_LDS);
+//   chains    every value is ONE chain of float64 __builtin_fma in the header's order.  A padded term multiplies a zero by a
+//             zero: the chain's bits do not change.  One reciprocal per pivot; no atomics but the flag's.
+//
+// Compiler's resource report (-Rpass-analysis=kernel-resource-usage, gfx950, 256 lanes per workgroup):
+//   <DP,DYP>  VGPRs  AGPRs  scratch B/lane  waves/SIMD
+//   <2,2>        63      0        0             7
+//   <2,4>        95      0        0             5
+//   <2,8>       208      0        0             2
+//   <4,2>        89      0        0             5
+//   <4,4>       147      0        0             3
+//   <4,8>       256     92        0             1
+//   <8,2>       256      0        0             2       P- in LDS
+//   <8,4>       256      0        0             2       P- in LDS
+//   <8,8>       256    256      132             1       P- in LDS
+// With P- in registers <8,8> took 328 bytes of scratch per lane (its live set — V 128, S 72, P- 72 registers and the vectors —
+// exceeds the 256 architectural VGPRs; the accumulation registers are a spill space with a move per use), so the 8-wide
+// instantiations keep the packed P- in LDS in an [element][lane] layout (72 KB per workgroup).  <8,8> still spills 33
+// dwords per lane and moves through the accumulation registers (about 880 moves beside 755 multiply-adds): slower than
+// it could be, correct, and measured as it is (profiles/switching_kalman.txt).
+//
+// Traffic per particle at D = Dy = 4: 8 (ancestor) + 8 (uniform) + 2 (4 + 32 + 80) (state in and out) + 8 (log-weight) =
+// 256 bytes; at D = 8: 736 bytes.
+#include "common.hpp"
+
+namespace aesmc {
+
+constexpr int kSkBlock = 256;
+constexpr int kSkMaxDim = 8;        // D and Dy
+constexpr int kSkMaxRegimes = 16;
+constexpr double kHalfLog2Pi = 0.9189385332046727;
+
+struct SwitchingArgs {
+  const double *cdf;                // [M,M] (later steps) or [M] (step 0)
+  const double *m0, *s0;            // [D]
+  const double *A, *b, *q, *C, *d, *r;
+  const int32_t *regime_in;         // NULL: step 0
+  const double *mean_in, *cov_in;
+  const int64_t *idx;
+  const double *uniforms;
+  const void *y;
+  int32_t *regime_out;
+  double *mean_out, *cov_out, *log_weight;
+  int32_t *flags;
+  int64_t N;
+  uint32_t K;
+  int M, D, Dy, y_is_float;
+};
+
+// whether an instantiation keeps the predicted covariance in LDS (see SkCov)
+__host__ __device__ constexpr bool sk_cov_in_lds(int dp) { return dp == 8; }
+// The compiler otherwise keeps every model value it has read once in a register for its later uses (128 VGPRs per 8 x 8
+// matrix): after this it reads LDS again
+#define SK_REREAD_LDS() asm volatile("" ::: "memory")
+
+__host__ __device__ constexpr int sk_tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+
+// A lane's packed predicted covariance P-: in registers, or (the 8-wide instantiations, which would spill) in LDS in an
+// [element][lane] layout — consecutive lanes on consecutive banks, no conflicts
+template <int TP, bool InLds> struct SkCov {
+  double reg[InLds ? 1 : TP];
+  double *lds;
+  __device__ __forceinline__ double get(int e) const {
+    if constexpr (InLds) return lds[e * kSkBlock];
+    else return reg[e];
+  }
+  __device__ __forceinline__ void set(int e, double v) {
+    if constexpr (InLds) lds[e * kSkBlock] = v;
+    else reg[e] = v;
+  }
+};
+
+// LDS: [M * M] (or [M]) cumulative rows, then per regime kPer values: A [DP,DP], b [DP], q^2 [DP], C [DYP,DP], d [DYP],
+// r^2 [DYP]; then, for DP == 8, [TP][256] predicted covariances
+template <int DP, int DYP>
+__global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const SwitchingArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sk_smem[];
+  constexpr int kPer = DP * DP + 2 * DP + DYP * DP + 2 * DYP;
+  constexpr int TP = DP * (DP + 1) / 2, TY = DYP * (DYP + 1) / 2;
+  const int M = a.M, D = a.D, Dy = a.Dy;
+  const bool later = a.regime_in != nullptr;
+  const int ncdf = later ? M * M : M;
+  double *cdf = sk_smem;
+  double *mdl = sk_smem + ncdf;
+  for (int e = threadIdx.x; e < ncdf; e += kSkBlock) cdf[e] = a.cdf[e];
+  for (int e = threadIdx.x; e < M * kPer; e += kSkBlock) {
+    const int s = e / kPer;
+    int o = e - s * kPer;
+    double v;
+    if (o < DP * DP) {
+      const int i = o / DP, l = o - i * DP;
+      v = (i < D && l < D) ? a.A[(s * D + i) * D + l] : 0.0;
+    } else if ((o -= DP * DP) < DP) {
+      v = o < D ? a.b[s * D + o] : 0.0;
+    } else if ((o -= DP) < DP) {
+      const double q = o < D ? a.q[s * D + o] : 0.0;
+      v = q * q;
+    } else if ((o -= DP) < DYP * DP) {
+      const int i = o / DP, l = o - i * DP;
+      v = (i < Dy && l < D) ? a.C[(s * Dy + i) * D + l] : 0.0;
+    } else if ((o -= DYP * DP) < DYP) {
+      v = o < Dy ? a.d[s * Dy + o] : 0.0;
+    } else {
+      o -= DYP;
+      const double r = o < Dy ? a.r[s * Dy + o] : 1.0;
+      v = r * r;
+    }
+    mdl[e] = v;
+  }
+  __syncthreads();
+  const int64_t n = (int64_t)blockIdx.x * kSkBlock + threadIdx.x;
+  if (n >= a.N) return;
+  const int64_t b = n / a.K;
+  const int64_t k = n - b * a.K;
+  const int TD = D * (D + 1) / 2;
+
+  // ---- the ancestor and the regime ------------------------------------------------------------------------------------
+  const int64_t anc = (later && a.idx != nullptr) ? a.idx[n] : k;
+  bool good = anc >= 0 && anc < (int64_t)a.K;
+  const int64_t src = b * a.K + (good ? anc : 0);
+  int s_prev = 0;
+  if (later) {
+    s_prev = a.regime_in[src];
+    if (s_prev < 0 || s_prev >= M) good = false, s_prev = 0;
+  }
+  if (!good) {
+    raise_flag(a.flags, AESMC_FLAG_INDEX_OUT_OF_RANGE);
+    const double nan = Num<double>::nan();
+    a.regime_out[n] = 0;
+    a.log_weight[n] = nan;
+    for (int i = 0; i < D; ++i) a.mean_out[n * D + i] = nan;
+    for (int e = 0; e < TD; ++e) a.cov_out[n * TD + e] = nan;
+    return;
+  }
+  const double u = a.uniforms[n];
+  const double *row = cdf + (later ? s_prev * M : 0);
+  int s = 0;
+  for (int i = 0; i < M - 1; ++i) s += row[i] <= u ? 1 : 0;
+
+  const double *Am = mdl + s * kPer, *bv = Am + DP * DP, *q2 = bv + DP, *Cm = q2 + DP, *dv = Cm + DYP * DP, *r2 = dv + DYP;
+
+  // ---- predict -----------------------------------------------------------------------------------------------------------
+  double mp[DP];
+  SkCov<TP, sk_cov_in_lds(DP)> Pm;
+  Pm.lds = mdl + M * kPer + threadIdx.x;
+  if (later) {
+    double mi[DP], Pi[TP];
+    const double *mrow = a.mean_in + src * D, *prow = a.cov_in + src * TD;
+#pragma unroll
+    for (int i = 0; i < DP; ++i) mi[i] = i < D ? mrow[i] : 0.0;
+#pragma unroll
+    for (int e = 0; e < TP; ++e) Pi[e] = e < TD ? prow[e] : 0.0;
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      double acc = bv[i];
+#pragma unroll
+      for (int l = 0; l < DP; ++l) acc = __builtin_fma(Am[i * DP + l], mi[l], acc);
+      mp[i] = acc;
+    }
+    double W[DP][DP];      // A P: row i from row i of A alone
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+#pragma unroll
+      for (int l = 0; l < DP; ++l) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < DP; ++c) acc = __builtin_fma(Am[i * DP + c], Pi[sk_tri(c, l)], acc);
+        W[i][l] = acc;
+      }
+    }
+    SK_REREAD_LDS();
+    // P-_ij = A_i . W_j (P is symmetric): row i of A alone again, and the rows of W already there
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double acc = i == j ? q2[i] : 0.0;
+#pragma unroll
+        for (int l = 0; l < DP; ++l) acc = __builtin_fma(Am[i * DP + l], W[j][l], acc);
+        Pm.set(sk_tri(i, j), acc);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      mp[i] = i < D ? a.m0[i] : 0.0;
+      const double s0 = i < D ? a.s0[i] : 0.0;
+#pragma unroll
+      for (int j = 0; j <= i; ++j) Pm.set(sk_tri(i, j), i == j ? s0 * s0 : 0.0);
+    }
+  }
+
+  // ---- innovation, U = C P-, S_ij = C_i . U_j + diag(r^2): row i of C alone serves e_i, U_i and S_i ---------------------------
+  SK_REREAD_LDS();
+  double e[DYP], U[DYP][DP], S[TY], yv[DYP];
+  if (a.y_is_float) {
+    const float *yrow = (const float *)a.y + b * Dy;
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) yv[i] = i < Dy ? (double)yrow[i] : 0.0;
+  } else {
+    const double *yrow = (const double *)a.y + b * Dy;
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) yv[i] = i < Dy ? yrow[i] : 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < DYP; ++i) {
+    if (i) SK_REREAD_LDS();
+    double acc = yv[i] - dv[i];
+#pragma unroll
+    for (int l = 0; l < DP; ++l) acc = __builtin_fma(-Cm[i * DP + l], mp[l], acc);
+    e[i] = acc;
+#pragma unroll
+    for (int l = 0; l < DP; ++l) {
+      double w = 0.0;
+#pragma unroll
+      for (int c = 0; c < DP; ++c) w = __builtin_fma(Cm[i * DP + c], Pm.get(sk_tri(c, l)), w);
+      U[i][l] = w;
+    }
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      double w = i == j ? r2[i] : 0.0;
+#pragma unroll
+      for (int l = 0; l < DP; ++l) w = __builtin_fma(Cm[i * DP + l], U[j][l], w);
+      S[sk_tri(i, j)] = w;
+    }
+  }
+
+  // ---- Lam = chol(S) in place, column by column; inv[j] = 1 / Lam_jj -------------------------------------------------------
+  double inv[DYP], log_det = 0.0;
+  bool positive = true;
+#pragma unroll
+  for (int j = 0; j < DYP; ++j) {
+    double pivot = S[sk_tri(j, j)];
+#pragma unroll
+    for (int c = 0; c < j; ++c) pivot = __builtin_fma(-S[sk_tri(j, c)], S[sk_tri(j, c)], pivot);
+    positive = positive && pivot > 0.0;
+    const double ljj = __builtin_sqrt(pivot);
+    S[sk_tri(j, j)] = ljj;
+    inv[j] = 1.0 / ljj;
+    log_det += ::log(ljj);
+#pragma unroll
+    for (int i = j + 1; i < DYP; ++i) {
+      double acc = S[sk_tri(i, j)];
+#pragma unroll
+      for (int c = 0; c < j; ++c) acc = __builtin_fma(-S[sk_tri(i, c)], S[sk_tri(j, c)], acc);
+      S[sk_tri(i, j)] = acc * inv[j];
+    }
+  }
+
+  // ---- v = Lam^-1 e, V = Lam^-1 U (in place) -------------------------------------------------------------------------------
+  double quad = 0.0;
+#pragma unroll
+  for (int i = 0; i < DYP; ++i) {
+    double acc = e[i];
+#pragma unroll
+    for (int c = 0; c < i; ++c) acc = __builtin_fma(-S[sk_tri(i, c)], e[c], acc);
+    e[i] = acc * inv[i];
+    quad = __builtin_fma(e[i], e[i], quad);
+#pragma unroll
+    for (int l = 0; l < DP; ++l) {
+      double w = U[i][l];
+#pragma unroll
+      for (int c = 0; c < i; ++c) w = __builtin_fma(-S[sk_tri(i, c)], U[c][l], w);
+      U[i][l] = w * inv[i];
+    }
+  }
+
+  // ---- outputs -----------------------------------------------------------------------------------------------------------
+  a.regime_out[n] = s;
+  double *mout = a.mean_out + n * D, *pout = a.cov_out + n * TD;
+  if (!positive) {
+    const double nan = Num<double>::nan();
+    a.log_weight[n] = nan;
+    for (int i = 0; i < D; ++i) mout[i] = nan;
+    for (int c = 0; c < TD; ++c) pout[c] = nan;
+    return;
+  }
+  a.log_weight[n] = (-0.5 * quad - log_det) - (double)Dy * kHalfLog2Pi;
+#pragma unroll
+  for (int l = 0; l < DP; ++l) {
+    SK_REREAD_LDS();      // (row by row: neither the reads of P- nor the stores move across)
+    double acc = mp[l];
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) acc = __builtin_fma(U[i][l], e[i], acc);
+    if (l < D) mout[l] = acc;
+#pragma unroll
+    for (int j = 0; j <= l; ++j) {
+      double w = Pm.get(sk_tri(l, j));
+#pragma unroll
+      for (int i = 0; i < DYP; ++i) w = __builtin_fma(-U[i][l], U[i][j], w);
+      if (l < D) pout[sk_tri(l, j)] = w;
+    }
+  }
+}
+
+static inline bool sk_aligned(const void *p, size_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
+static inline int sk_pad(int64_t d) { return d <= 2 ? 2 : d <= 4 ? 4 : 8; }
+
+template <int DP, int DYP>
+static bool sk_launch(dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
+  // the 8-wide instantiations (72 KB of covariances beside the model) need the limit raised; on every launch — no state to
+  // share between threads or devices, and the call is cheap beside the kernel
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_kalman_kernel<DP, DYP>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    return false;
+  hipLaunchKernelGGL((switching_kalman_kernel<DP, DYP>), grid, dim3(kSkBlock), lds, s, a);
+  return true;
+}
+
+template <int DP>
+static bool sk_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
+  if (dyp == 2) return sk_launch<DP, 2>(grid, lds, s, a);
+  if (dyp == 4) return sk_launch<DP, 4>(grid, lds, s, a);
+  return sk_launch<DP, 8>(grid, lds, s, a);
+}
+
+}  // namespace aesmc
+
+extern "C" int64_t aesmc_switching_max_latent_dim(void) { return aesmc::kSkMaxDim; }
+extern "C" int64_t aesmc_switching_max_observation_dim(void) { return aesmc::kSkMaxDim; }
+extern "C" int64_t aesmc_switching_max_regimes(void) { return aesmc::kSkMaxRegimes; }
+
+extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                           const double *mean_in, const double *cov_in, const int64_t *idx,
+                                           const double *uniforms, const void *y, int32_t *regime_out, double *mean_out,
+                                           double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
+                                           void *stream) {
+  using namespace aesmc;
+  if (model == nullptr || uniforms == nullptr || y == nullptr || regime_out == nullptr || mean_out == nullptr ||
+      cov_out == nullptr || log_weight == nullptr || B < 0 || K < 0)
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (y_dtype != AESMC_F32 && y_dtype != AESMC_F64) return AESMC_ERR_INVALID_ARGUMENT;
+  const bool later = regime_in != nullptr;
+  if (later != (mean_in != nullptr) || later != (cov_in != nullptr)) return AESMC_ERR_INVALID_ARGUMENT;
+  if (model->M < 1 || model->D < 1 || model->Dy < 1) return AESMC_ERR_INVALID_ARGUMENT;
+  const double *operands[] = {later ? model->cdf : model->cdf0, model->m0, model->s0, model->A, model->b, model->q,
+                              model->C, model->d, model->r};
+  for (const double *p : operands)
+    if (p == nullptr || !sk_aligned(p, 8)) return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_aligned(regime_in, 4) || !sk_aligned(mean_in, 8) || !sk_aligned(cov_in, 8) || !sk_aligned(idx, 8) ||
+      !sk_aligned(uniforms, 8) || !sk_aligned(y, y_dtype == AESMC_F32 ? 4 : 8) || !sk_aligned(regime_out, 4) ||
+      !sk_aligned(mean_out, 8) || !sk_aligned(cov_out, 8) || !sk_aligned(log_weight, 8) || !sk_aligned(flags, 4))
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (later && (regime_out == regime_in || mean_out == mean_in || cov_out == cov_in)) return AESMC_ERR_INVALID_ARGUMENT;
+  if (B == 0 || K == 0) return AESMC_OK;
+  if (model->D > kSkMaxDim || model->Dy > kSkMaxDim || model->M > kSkMaxRegimes) return AESMC_ERR_UNSUPPORTED;
+  if (B > 0x7fffffffLL || K > 0x7fffffffLL || B * K > 0x7fffffffLL / (kSkMaxDim * (kSkMaxDim + 1) / 2))
+    return AESMC_ERR_UNSUPPORTED;
+  SwitchingArgs a;
+  a.cdf = later ? model->cdf : model->cdf0;
+  a.m0 = model->m0, a.s0 = model->s0;
+  a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
+  a.regime_in = regime_in, a.mean_in = mean_in, a.cov_in = cov_in;
+  a.idx = idx, a.uniforms = uniforms, a.y = y;
+  a.regime_out = regime_out, a.mean_out = mean_out, a.cov_out = cov_out, a.log_weight = log_weight;
+  a.flags = flags;
+  a.N = B * K, a.K = (uint32_t)K;
+  a.M = (int)model->M, a.D = (int)model->D, a.Dy = (int)model->Dy;
+  a.y_is_float = y_dtype == AESMC_F32;
+  const int dp = sk_pad(model->D), dyp = sk_pad(model->Dy);
+  const size_t per = (size_t)dp * dp + 2 * dp + (size_t)dyp * dp + 2 * dyp;
+  const size_t lds = ((later ? (size_t)a.M * a.M : (size_t)a.M) + (size_t)a.M * per + (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0)) *
+                     sizeof(double);
+  const dim3 grid((unsigned)((a.N + kSkBlock - 1) / kSkBlock));
+  hipStream_t s = (hipStream_t)stream;
+  const bool launched = dp == 2 ? sk_launch_dy<2>(dyp, grid, lds, s, a)
+                        : dp == 4 ? sk_launch_dy<4>(dyp, grid, lds, s, a) : sk_launch_dy<8>(dyp, grid, lds, s, a);
+  return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+}

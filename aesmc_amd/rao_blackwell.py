@@ -1,0 +1,301 @@
+"""The Rao-Blackwellised particle filter (mixture Kalman filter; Doucet, de Freitas, Murphy & Russell 2000; Chen & Liu
+2000) for switching linear-Gaussian state-space models (SLDS, jump-Markov linear systems):
+
+    s_0 ~ Cat(pi0)                      s_t | s_{t-1} ~ Cat(Pi[s_{t-1}, :])
+    z_0 ~ N(m0, diag(s0^2))             z_t = A[s_t] z_{t-1} + b[s_t] + N(0, diag(q[s_t]^2))
+    y_t = C[s_t] z_t + d[s_t] + N(0, diag(r[s_t]^2))        (also at t = 0, under s_0)
+
+Every other filter of this package represents the whole latent by samples.  Here only the discrete regime s_t is sampled
+(a bootstrap on the regimes); each particle carries the EXACT Kalman mean and covariance of the continuous state z_t given
+its regime history, and its weight is the Kalman predictive likelihood p(y_t | s_{0:t}, y_{0:t-1}).  With one regime
+(M = 1) the filter is the Kalman filter, exact for any number of particles: `kalman_log_likelihood` is the log p(y) that
+`adapted`'s docstring cites as the ceiling ELBO(adapted) <= log p(y), computed on the device.
+
+A step is two launches: the existing resampling launch K2 on the log-weights (its row log-sum-exp is the step's evidence
+increment) and K31 (`aesmc_switching_kalman_step`): the gather through the ancestors, the inverse-CDF regime draw, the
+Kalman predict, the Dy x Dy Cholesky factor, two triangular solves and the rank-Dy downdate, one lane per particle in
+float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
+
+The reference has no counterpart; this module adds to its interface and changes none of it.
+"""
+import math
+
+import torch
+
+from . import _kernels
+from . import _ops
+from . import _syncfree
+from . import inference
+from . import statistics
+
+MAX_LATENT_DIM, MAX_OBSERVATION_DIM, MAX_REGIMES = 8, 8, 16      # aesmc_switching_max_*() of the library
+_COVERED = ("covered: switching linear-Gaussian models with at most {} regimes, a latent of at most {} values and an "
+            "observation of at most {} values, constant in time; observations [batch_size, Dy] of float32 or float64 on "
+            "the HIP device".format(MAX_REGIMES, MAX_LATENT_DIM, MAX_OBSERVATION_DIM))
+
+
+def _refuse(what):
+    raise NotImplementedError("aesmc_amd.rao_blackwell: {} is not implemented; {}".format(what, _COVERED))
+
+
+class SwitchingLinearGaussian(torch.nn.Module):
+    """A switching linear-Gaussian state-space model with M regimes, latent z in R^D and observation y in R^Dy.
+
+    pi0 [M], Pi [M,M] (rows: from-regime); m0 [D], s0 (one value or D); A [M,D,D], b [M,D], q [M,D]; C [M,Dy,D], d [M,Dy],
+    r [M,Dy].  A leading extent of 1 in place of M means shared across regimes.  Everything is held as a float64 buffer
+    (`.to(device)` moves the model); nothing here is learned: the filter is not differentiable."""
+
+    def __init__(self, pi0, Pi, m0, s0, A, b, q, C, d, r):
+        super().__init__()
+        for name, value in (("pi0", pi0), ("Pi", Pi), ("m0", m0), ("s0", s0), ("A", A), ("b", b), ("q", q), ("C", C),
+                            ("d", d), ("r", r)):
+            self.register_buffer(name, torch.as_tensor(value).detach().to(torch.float64).clone())
+
+    @property
+    def num_regimes(self):
+        return self.pi0.numel()
+
+    @property
+    def latent_dim(self):
+        return self.A.size(-1) if self.A.dim() == 3 else 0
+
+    @property
+    def observation_dim(self):
+        return self.C.size(-2) if self.C.dim() == 3 else 0
+
+    def operands(self):
+        """The model as a step takes it: a dict of dense float64 tensors on the buffers' device — pi0 [M], Pi [M,M], their
+        cumulative rows cdf0 [M] and cdf [M,M] (torch.cumsum on the host, the last entry set to 1), m0 [D], s0 [D], and A,
+        b, q, C, d, r expanded to M regimes.  Validates: ValueError for shapes that disagree, for probabilities that are
+        negative or do not sum to 1 within 1e-12 and for scales that are not finite; NotImplementedError naming the
+        covered class for anything past the limits.  One copy to the host (the probabilities and the scales together); the
+        cumulative rows are copied back."""
+        M, D, Dy = self.num_regimes, self.latent_dim, self.observation_dim
+        if self.pi0.dim() != 1 or M < 1 or tuple(self.Pi.shape) != (M, M):
+            raise ValueError("SwitchingLinearGaussian: pi0 must be [M] and Pi [M, M], got {} and {}".format(
+                tuple(self.pi0.shape), tuple(self.Pi.shape)))
+        if self.A.dim() != 3 or self.C.dim() != 3 or D < 1 or Dy < 1 or self.A.size(1) != D or self.C.size(2) != D:
+            raise ValueError("SwitchingLinearGaussian: A must be [M, D, D] and C [M, Dy, D], got {} and {}".format(
+                tuple(self.A.shape), tuple(self.C.shape)))
+        if M > MAX_REGIMES:
+            _refuse("a model of {} regimes (M > {})".format(M, MAX_REGIMES))
+        if D > MAX_LATENT_DIM:
+            _refuse("a latent of {} values (D > {})".format(D, MAX_LATENT_DIM))
+        if Dy > MAX_OBSERVATION_DIM:
+            _refuse("an observation of {} values (Dy > {})".format(Dy, MAX_OBSERVATION_DIM))
+        shapes = {"A": (M, D, D), "b": (M, D), "q": (M, D), "C": (M, Dy, D), "d": (M, Dy), "r": (M, Dy)}
+        out = {}
+        for name, shape in shapes.items():
+            value = getattr(self, name)
+            if value.dim() != len(shape) or value.size(0) not in (1, M) or tuple(value.shape[1:]) != shape[1:]:
+                raise ValueError("SwitchingLinearGaussian: {} must be {} (or a leading 1: shared across regimes), got {}"
+                                 .format(name, shape, tuple(value.shape)))
+            out[name] = value.expand(shape).contiguous()
+        if tuple(self.m0.shape) != (D,):
+            raise ValueError("SwitchingLinearGaussian: m0 must be [{}], got {}".format(D, tuple(self.m0.shape)))
+        if self.s0.numel() not in (1, D):
+            raise ValueError("SwitchingLinearGaussian: s0 must hold one value or {}, got {}".format(D, self.s0.numel()))
+        out["m0"] = self.m0.contiguous()
+        out["s0"] = self.s0.reshape(-1).expand(D).contiguous()
+        device = self.pi0.device
+        # ONE copy to the host: the probabilities (validated and accumulated there) with the scales behind them
+        host = torch.cat([self.pi0.reshape(-1), self.Pi.reshape(-1)] +
+                         [out[name].reshape(-1) for name in ("s0", "q", "r")]).cpu()
+        pi0, Pi, scales = host[:M].clone(), host[M:M + M * M].reshape(M, M).clone(), host[M + M * M:]
+        for name, p in (("pi0", pi0), ("Pi", Pi)):
+            if not bool(torch.isfinite(p).all()) or bool((p < 0).any()):
+                raise ValueError("SwitchingLinearGaussian: {} holds a negative or non-finite probability".format(name))
+            if bool(((p.sum(dim=-1) - 1.0).abs() > 1e-12).any()):
+                raise ValueError("SwitchingLinearGaussian: {} must sum to 1 within 1e-12 along its last dimension".format(
+                    name))
+        if not bool(torch.isfinite(scales).all()):
+            raise ValueError("SwitchingLinearGaussian: a scale is not finite")
+        cdf0, cdf = torch.cumsum(pi0, dim=-1), torch.cumsum(Pi, dim=-1)
+        cdf0[-1] = 1.0
+        cdf[:, -1] = 1.0
+        out.update(pi0=self.pi0.contiguous(), Pi=self.Pi.contiguous(), cdf0=cdf0.to(device), cdf=cdf.to(device))
+        return out
+
+    def simulate(self, num_timesteps, batch_size, seed=None, return_latents=False):
+        """Draws `batch_size` series of `num_timesteps` observations from the model (torch's CPU generator; `seed` fixes
+        it): a list of [batch_size, Dy] float64 tensors on the model's device — with `return_latents`, (observations,
+        regimes: T x int64 [batch_size], states: T x [batch_size, D]) instead."""
+        ops = {name: value.cpu() for name, value in self.operands().items()}
+        generator = torch.Generator()
+        if seed is not None:
+            generator.manual_seed(int(seed))
+        D, Dy = self.latent_dim, self.observation_dim
+        device = self.pi0.device
+        normal = lambda *shape: torch.randn(*shape, dtype=torch.float64, generator=generator)
+        observations, regimes, states = [], [], []
+        for time in range(num_timesteps):
+            if time == 0:
+                s = torch.multinomial(ops["pi0"].expand(batch_size, -1), 1, generator=generator).squeeze(1)
+                z = ops["m0"] + ops["s0"] * normal(batch_size, D)
+            else:
+                s = torch.multinomial(ops["Pi"][s], 1, generator=generator).squeeze(1)
+                z = torch.einsum("bij,bj->bi", ops["A"][s], z) + ops["b"][s] + ops["q"][s] * normal(batch_size, D)
+            y = torch.einsum("bij,bj->bi", ops["C"][s], z) + ops["d"][s] + ops["r"][s] * normal(batch_size, Dy)
+            observations.append(y.to(device)), regimes.append(s.to(device)), states.append(z.to(device))
+        return (observations, regimes, states) if return_latents else observations
+
+
+def unpack_covariance(packed, dim):
+    """[..., D(D+1)/2] packed lower triangles (element (i,j), i >= j, at i(i+1)/2 + j) -> [..., D, D] symmetric."""
+    rows, cols = torch.tril_indices(dim, dim, device=packed.device)
+    full = packed.new_zeros(packed.shape[:-1] + (dim, dim))
+    full[..., rows, cols] = packed
+    full[..., cols, rows] = packed
+    return full
+
+
+def _moments(regimes, means, covariances, log_weights, num_regimes):
+    """(filtered_mean [T,B,D], filtered_covariance [T,B,D,D], regime_probabilities [T,B,M]) of the stored systems: the
+    weighted summaries are `statistics.empirical_mean`'s (kernel K7 on the device), the rest plain torch."""
+    filtered_mean, filtered_cov, probabilities = [], [], []
+    for regime, mean, cov, log_w in zip(regimes, means, covariances, log_weights):
+        D = mean.size(-1)
+        average = statistics.empirical_mean(mean, log_w)
+        second = unpack_covariance(cov, D) + mean.unsqueeze(-1) * mean.unsqueeze(-2)
+        second = statistics.empirical_mean(second.reshape(second.shape[:2] + (D * D,)), log_w).reshape(-1, D, D)
+        one_hot = torch.nn.functional.one_hot(regime.to(torch.int64), num_regimes).to(torch.float64)
+        filtered_mean.append(average)
+        filtered_cov.append(second - average.unsqueeze(-1) * average.unsqueeze(-2))
+        probabilities.append(statistics.empirical_mean(one_hot, log_w))
+    return torch.stack(filtered_mean), torch.stack(filtered_cov), torch.stack(probabilities)
+
+
+def switching_filter(observations, model, num_particles, resampling=None, regime_uniforms=None, return_moments=False,
+                     return_latents=False):
+    """Runs the Rao-Blackwellised particle filter of a `SwitchingLinearGaussian`.
+
+    observations: length-T sequence of [batch_size, Dy] tensors (float32 or float64) on the model's device.
+    num_particles: K.
+    resampling: 'systematic', 'stratified' or None (`settings.current().resampling`), as `infer` — the uniforms come from
+        the same feeds (`inference.uniform_feed(...)` overrides them), and 'stratified' inside `distributed.shard_scope`
+        raises.  Every step resamples.
+    regime_uniforms: None — torch.rand((batch_size, num_particles), float64) per step on the device (seed with
+        torch.manual_seed); or a length-T sequence of such tensors (replay).  None inside `distributed.shard_scope` raises
+        NotImplementedError for the reason stratified resampling does: a per-particle device draw has no global block
+        that every rank could cut its rows from.
+    return_moments: also filtered_mean [T,batch_size,D], filtered_covariance [T,batch_size,D,D] (the mixture's: sum_k w_k
+        (P_k + m_k m_k^T) - mean mean^T) and regime_probabilities [T,batch_size,M].
+    return_latents: also `latents`: the regime genealogy (`inference.get_resampled_latents` of the stored regimes).
+
+    Returns a dict: log_marginal_likelihood [batch_size] float64 (unbiased for p(y_0..y_{T-1}); exact for M = 1); regimes (T
+    int32 [batch_size, K]), means (T float64 [batch_size, K, D]), covariances (T float64 [batch_size, K, D(D+1)/2]: packed
+    lower triangles, `unpack_covariance`), log_weights (T float64 [batch_size, K]) — the stored, un-resampled particle
+    systems; ancestral_indices (T-1 int64 [batch_size, K], `infer`'s convention); log_weight (the last of log_weights).
+
+    ValueError for an invalid model (`SwitchingLinearGaussian.operands`), T == 0, K < 1 and feeds of the wrong shape;
+    NotImplementedError naming the covered class for anything past the limits.  An innovation covariance that is not
+    positive definite gives NaN log-weights and FloatingPointError, a row without a finite maximum RuntimeError — read
+    once, at the end; an exception on the way discards whatever was flagged.  No host synchronisation inside the step
+    loop.  Runs under torch.no_grad(): NOT differentiable."""
+    from . import distributed
+    num_timesteps, num_particles = len(observations), int(num_particles)
+    if num_timesteps == 0:
+        raise ValueError("switching_filter: observations must hold at least one timestep")
+    if num_particles < 1:
+        raise ValueError("switching_filter: num_particles must be at least 1")
+    if regime_uniforms is not None and len(regime_uniforms) != num_timesteps:
+        raise ValueError("switching_filter: regime_uniforms must hold one tensor per timestep ({}), got {}".format(
+            num_timesteps, len(regime_uniforms)))
+    stratified = inference._resolve_resampling(resampling) == "stratified"
+    if regime_uniforms is None and distributed.active_shard() is not None:
+        raise NotImplementedError(
+            "aesmc_amd.rao_blackwell: drawing the regime uniforms inside distributed.shard_scope is not implemented: a "
+            "sharded run reproduces the unsharded one through the global block of host uniforms every rank draws, which "
+            "per-particle device draws do not have. Pass regime_uniforms when sharding.")
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops = model.operands()      # validation, expansion and the cumulative rows: once, before the loop
+            M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
+            for y in observations:
+                if not torch.is_tensor(y) or y.dim() != 2 or y.size(1) != Dy or y.size(0) != observations[0].size(0):
+                    raise ValueError("switching_filter: observations must be [batch_size, {}] tensors".format(Dy))
+            batch_size, device = observations[0].size(0), observations[0].device
+            if provider.name == "hip":
+                _kernels._require_hip(observations[0], "observations")      # (no CPU fallback)
+            if not provider.switching_covers(observations[0], M, D, Dy, num_particles):
+                _refuse("these observations ({} {} on {})".format(tuple(observations[0].shape), observations[0].dtype,
+                                                                   device))
+            shape = (batch_size, num_particles)
+
+            def draw(time):
+                if regime_uniforms is None:
+                    return torch.rand(shape, dtype=torch.float64, device=device)
+                u = regime_uniforms[time]
+                if not torch.is_tensor(u) or tuple(u.shape) != shape or u.dtype != torch.float64 or u.device != device:
+                    raise ValueError("switching_filter: regime_uniforms[{}] must be {} float64 on {}".format(
+                        time, shape, device))
+                return u
+
+            log_z = torch.zeros(batch_size, dtype=torch.float64, device=device)
+            regimes, means, covariances, log_weights, ancestral = [], [], [], [], []
+            state, index, feed = None, None, None
+            for time in range(num_timesteps):
+                if time > 0:
+                    if feed is None:
+                        feed = inference._FEED_OVERRIDE.get() or (
+                            inference._StratifiedFeed(batch_size, num_particles, device) if stratified else
+                            inference._UniformFeed(batch_size, num_timesteps - 1, device))
+                    uniforms = feed.next()
+                    per_particle = uniforms.dim() == 2 and tuple(uniforms.shape) == shape
+                    if per_particle != stratified and num_particles != 1:
+                        raise ValueError("aesmc_amd: {} resampling takes {} uniforms per step, the feed returned {}".format(
+                            "stratified" if stratified else "systematic",
+                            "[batch_size, num_particles]" if stratified else "[batch_size]", tuple(uniforms.shape)))
+                    index, lse, _ = _ops.resample_step(log_weights[-1], uniforms, None, want_lse=True)
+                    index = _kernels.as_index(index)
+                    log_z = log_z + (lse.to(torch.float64) - math.log(num_particles))
+                    ancestral.append(index)
+                regime, mean, cov, log_w = provider.switching_kalman_step(ops, state, index, draw(time),
+                                                                          observations[time])
+                state = (regime, mean, cov)
+                regimes.append(regime), means.append(mean), covariances.append(cov), log_weights.append(log_w)
+            log_z = log_z + (_ops.row_logsumexp(log_weights[-1]).to(torch.float64) - math.log(num_particles))
+            out = {"log_marginal_likelihood": log_z, "regimes": regimes, "means": means, "covariances": covariances,
+                   "log_weights": log_weights, "ancestral_indices": ancestral, "log_weight": log_weights[-1]}
+            if return_moments:
+                out["filtered_mean"], out["filtered_covariance"], out["regime_probabilities"] = _moments(
+                    regimes, means, covariances, log_weights, M)
+            if return_latents:
+                out["latents"] = inference.get_resampled_latents(regimes, ancestral)
+            inference._raise_for_flags(provider.read_flags(device))
+            # (the last step's log-weights meet no resampling launch: a NaN among them is reported here, after the one read)
+            if bool(torch.isnan(log_z).any()):
+                raise FloatingPointError("log_weight contains nan element(s)")
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
+
+
+class _ZeroFeed:
+    """A resampling feed that consumes no random numbers (`kalman_log_likelihood`: nothing is sampled)."""
+
+    def __init__(self, block):
+        self.block = block
+
+    def next(self):
+        return self.block
+
+
+def kalman_log_likelihood(observations, model):
+    """The exact Kalman filter of a one-regime model on the device: `switching_filter` with M = 1 and one particle, where
+    nothing is sampled.  Returns (log p(y_0..y_{T-1}) [batch_size] float64, filtered means [T,batch_size,D], filtered
+    covariances [T,batch_size,D,D]).  ValueError if the model has more than one regime."""
+    if model.num_regimes != 1:
+        raise ValueError("kalman_log_likelihood: the model has {} regimes; the Kalman filter is the one-regime case".format(
+            model.num_regimes))
+    if len(observations) == 0:
+        raise ValueError("kalman_log_likelihood: observations must hold at least one timestep")
+    shape = (observations[0].size(0), 1)
+    zeros = [torch.zeros(shape, dtype=torch.float64, device=observations[0].device)] * len(observations)
+    with inference.uniform_feed(_ZeroFeed(zeros[0][:, 0])):      # one particle: its own ancestor whatever the uniform
+        out = switching_filter(observations, model, 1, resampling="systematic", regime_uniforms=zeros)
+    D = model.latent_dim
+    return (out["log_marginal_likelihood"], torch.stack([m[:, 0] for m in out["means"]]),
+            torch.stack([unpack_covariance(c[:, 0], D) for c in out["covariances"]]))

@@ -1,0 +1,68 @@
+"""Filter a switching linear-Gaussian state-space model with the Rao-Blackwellised particle filter
+(`aesmc_amd.rao_blackwell.switching_filter`): only the regime is sampled, every particle carries the exact Kalman mean and
+covariance of the continuous state given its regime history (kernel K31).
+
+    python examples/slds_filter.py [--regimes 2] [--dim 2] [--particles 256] [--batch 8] [--timesteps 200] [--short 6]
+
+Simulates a series whose regimes differ in their dynamics, filters it, and prints how often the most probable filtered
+regime is the true one and the error of the filtered mean; then, for a short series, log Z-hat beside the exact log p(y)
+from the enumeration of all M^T regime sequences.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import aesmc_amd as aesmc  # noqa: F401
+from aesmc_amd import rao_blackwell
+from aesmc_amd.testing import rao_blackwell as contract
+
+
+def make_model(M, D, seed):
+    """Sticky regimes that rotate the state at different speeds and shrink it differently; the state is seen whole."""
+    rng = np.random.default_rng(seed)
+    Pi = np.full((M, M), 0.05 / max(M - 1, 1)) + (0.95 - 0.05 / max(M - 1, 1)) * np.eye(M) if M > 1 else np.ones((1, 1))
+    A = np.stack([np.linalg.qr(rng.standard_normal((D, D)))[0] * (0.5 + 0.45 * i / max(M - 1, 1)) for i in range(M)])
+    b = np.stack([np.full(D, 0.5 * i) for i in range(M)])
+    return rao_blackwell.SwitchingLinearGaussian(np.full(M, 1.0 / M), Pi / Pi.sum(axis=1, keepdims=True), np.zeros(D), 1.0, A,
+                                                 b, np.full((1, D), 0.3), np.eye(D)[None], np.zeros((1, D)),
+                                                 np.full((1, D), 0.3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--regimes", type=int, default=2)
+    ap.add_argument("--dim", type=int, default=2)
+    ap.add_argument("--particles", type=int, default=256)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--timesteps", type=int, default=200)
+    ap.add_argument("--short", type=int, default=6)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+
+    device = torch.device("cuda", 0)
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    model = make_model(args.regimes, args.dim, args.seed).to(device)
+    observations, regimes, states = model.simulate(args.timesteps, args.batch, seed=args.seed + 1, return_latents=True)
+    out = rao_blackwell.switching_filter(observations, model, args.particles, return_moments=True)
+    guess = out["regime_probabilities"].argmax(dim=-1)
+    accuracy = (guess == torch.stack(regimes)).double().mean().item()
+    error = (out["filtered_mean"] - torch.stack(states)).pow(2).mean().sqrt().item()
+    print("T = {}, {} series, K = {}: filtered regime = true regime {:.1%} of the time; RMSE of the filtered mean {:.3f}; "
+          "log Z-hat per step {:.4f}".format(args.timesteps, args.batch, args.particles, accuracy, error,
+                                             out["log_marginal_likelihood"].mean().item() / args.timesteps))
+    short = [y[:1] for y in observations[:args.short]]
+    ops = {name: value.cpu().numpy() for name, value in model.operands().items()}
+    exact = contract.exact_log_likelihood(ops, [y.cpu().numpy() for y in short])[0]
+    repeats = [rao_blackwell.switching_filter(short, model, args.particles)["log_marginal_likelihood"].item()
+               for _ in range(5)]
+    print("T = {}: exact log p(y) = {:.6f} ({} regime sequences); log Z-hat over 5 runs: {}".format(
+        args.short, exact, args.regimes ** args.short, ", ".join("{:.6f}".format(v) for v in repeats)))
+
+
+if __name__ == "__main__":
+    main()

@@ -74,7 +74,10 @@ extern "C" {
  *                aesmc_affine_quadratic_logweight, aesmc_adapted_draw (K27, K28: the first-stage weights and the draw of
  *                a fully adapted auxiliary particle filter step);
  *                aesmc_affine_quadratic_logweight_backward, aesmc_adapted_draw_backward,
- *                aesmc_adapted_backward_workspace_bytes (K29, K30: their adjoints, for training through the adapted filter).
+ *                aesmc_adapted_backward_workspace_bytes (K29, K30: their adjoints, for training through the adapted filter);
+ *                aesmc_switching_kalman_step with aesmc_switching_max_latent_dim, aesmc_switching_max_observation_dim,
+ *                aesmc_switching_max_regimes (K31: one step of the Rao-Blackwellised filter of a switching
+ *                linear-Gaussian model).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -619,6 +622,59 @@ int aesmc_affine_quadratic_logweight_backward(int dtype, const aesmc_view3 *loc,
 int aesmc_adapted_draw_backward(int dtype, const aesmc_view3 *loc, const int64_t *idx, const double *M, const void *eps,
                                 const void *grad, void *h, double *grad_M, double *grad_L, double *grad_r, int32_t *flags,
                                 void *workspace, int64_t workspace_bytes, int64_t B, int64_t K, int64_t D, void *stream);
+
+/* K31 — one step of the Rao-Blackwellised particle filter (mixture Kalman filter; Doucet, de Freitas, Murphy & Russell
+ * 2000; Chen & Liu 2000) for a switching linear-Gaussian state-space model with M regimes, latent z in R^D, observation
+ * y in R^Dy:
+ *   s_0 ~ Cat(pi0)              s_t | s_{t-1} ~ Cat(Pi[s_{t-1},:])
+ *   z_0 ~ N(m0, diag(s0^2))     z_t = A[s_t] z_{t-1} + b[s_t] + N(0, diag(q[s_t]^2))
+ *   y_t = C[s_t] z_t + d[s_t] + N(0, diag(r[s_t]^2))                      (also at t = 0, under s_0)
+ * Only the regimes are sampled: particle (b,k) carries its regime s, and the exact Kalman mean m and covariance P of z
+ * given its regime history; its weight is the Kalman predictive likelihood.  The reference has no such call site.
+ * The model, all float64, dense, 8-byte aligned (the host expands anything shared across regimes): */
+typedef struct {
+  const double *cdf0;      /* [M]    cumulative pi0, last entry 1: read by the step-0 form only                     */
+  const double *cdf;       /* [M,M]  cumulative rows of Pi, last entry of each 1: read by the later form only       */
+  const double *m0, *s0;   /* [D]    the initial mean and scale: read by the step-0 form only                       */
+  const double *A, *b, *q; /* [M,D,D], [M,D], [M,D]                                                                 */
+  const double *C, *d, *r; /* [M,Dy,D], [M,Dy], [M,Dy]                                                              */
+  int64_t M, D, Dy;
+} aesmc_switching_model;
+/*   regime_in   int32 [B,K], mean_in float64 [B,K,D], cov_in float64 [B,K,D(D+1)/2]: the STORED particles of the step
+ *               before — all three NULL: the step-0 form, which reads no state and no idx; cov is the packed lower
+ *               triangle, element (i,j) with i >= j at i(i+1)/2 + j
+ *   idx         int64 [B,K] dense, or NULL for the identity; NOT assumed sorted
+ *   uniforms    float64 [B,K]                       y   T [B,Dy] dense, T float32 or float64 (`y_dtype`), widened on read
+ *   regime_out, mean_out, cov_out as the inputs, log_weight float64 [B,K]: written out of place (the gather forbids in
+ *               place: an output that is its own input is an invalid argument)
+ * Per particle, with j = idx ? idx[b,k] : k (step 0: k), everything in float64, every sum ONE chain of fused multiply-adds
+ * in ascending index order starting from the value named first:
+ *   s        = #{ i < M-1 : cdf[regime_in[b,j], i] <= uniforms[b,k] }                 (step 0: the row cdf0)
+ *   m-_i     = b_s[i] + sum_l A_s[i,l] m[b,j,l]                                          (step 0: m0)
+ *   W_il     = 0 + sum_c A_s[i,c] P[b,j][c,l];   P-_ij = (i == j ? q_s[i]^2 : 0) + sum_l A_s[i,l] W_jl,  i >= j
+ *                                                                                        (step 0: diag(s0^2))
+ *   e_i      = (y[b,i] - d_s[i]) - sum_l C_s[i,l] m-_l
+ *   U_il     = 0 + sum_c C_s[i,c] P-[c,l];       S_ij = (i == j ? r_s[i]^2 : 0) + sum_l C_s[i,l] U_jl,    i >= j
+ *   Lam      = chol(S) column by column: Lam_jj = sqrt(S_jj - sum_{c<j} Lam_jc^2), rho_j = 1 / Lam_jj,
+ *              Lam_ij = (S_ij - sum_{c<j} Lam_ic Lam_jc) rho_j
+ *   v_i      = (e_i - sum_{c<i} Lam_ic v_c) rho_i;   V_il = (U_il - sum_{c<i} Lam_ic V_cl) rho_i
+ *   log_weight[b,k] = (-1/2 sum_i v_i^2 - sum_j log Lam_jj) - Dy * (1/2 log 2 pi)
+ *   mean_out_l = m-_l + sum_i V_il v_i;          cov_out_lj = P-_lj - sum_i V_il V_ij,  l >= j (the lower triangle only)
+ * An idx outside [0, K) or a stored regime outside [0, M) reads nothing further, writes regime 0 and NaN to the particle's
+ * mean, covariance and log-weight and raises AESMC_FLAG_INDEX_OUT_OF_RANGE.  A pivot S_jj - sum that is not positive
+ * writes the drawn regime and NaN to the particle's mean, covariance and log-weight; the resampling launch that follows
+ * raises AESMC_FLAG_NAN_LOG_WEIGHT by its own rules.
+ * NULL or misaligned pointers, negative sizes, M, D or Dy below 1, an unknown dtype, a state given in part and an output
+ * that aliases its input return AESMC_ERR_INVALID_ARGUMENT; B K == 0 is a no-op; D above aesmc_switching_max_latent_dim(),
+ * Dy above aesmc_switching_max_observation_dim(), M above aesmc_switching_max_regimes() or B K beyond 32-bit element
+ * arithmetic return AESMC_ERR_UNSUPPORTED.  Every check runs before any launch.  `flags` may be NULL. */
+int64_t aesmc_switching_max_latent_dim(void);      /* 8 */
+int64_t aesmc_switching_max_observation_dim(void); /* 8 */
+int64_t aesmc_switching_max_regimes(void);         /* 16 */
+int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                const double *mean_in, const double *cov_in, const int64_t *idx, const double *uniforms,
+                                const void *y, int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
+                                int32_t *flags, int64_t B, int64_t K, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
