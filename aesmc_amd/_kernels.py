@@ -2364,6 +2364,35 @@ class HipKernels:
         return 1 <= latent_dim <= max_d and 1 <= observation_dim <= max_dy and 1 <= num_regimes <= max_m and \
             observation.size(0) * num_particles <= 0x7fffffff // (max_d * (max_d + 1) // 2)
 
+    def _switching_block(self, model, device):
+        """(block, M, D, Dy) of a switching model: every tensor of SWITCHING_MODEL_KEYS validated (dense float64 of its
+        shape on `device`), and the C structure that points at them."""
+        A, C = model["A"], model["C"]
+        M, D, Dy = (A.size(0), A.size(2), C.size(1)) if torch.is_tensor(A) and A.dim() == 3 and torch.is_tensor(C) and \
+            C.dim() == 3 else (0, 0, 0)
+        shapes = {"cdf0": (M,), "cdf": (M, M), "m0": (D,), "s0": (D,), "A": (M, D, D), "b": (M, D), "q": (M, D),
+                  "C": (M, Dy, D), "d": (M, Dy), "r": (M, Dy)}
+        for name in self.SWITCHING_MODEL_KEYS:
+            tensor = model[name]
+            _require_hip(tensor, name)
+            if tuple(tensor.shape) != shapes[name] or tensor.dtype != torch.float64 or tensor.device != device or \
+                    not tensor.is_contiguous():
+                raise ValueError("aesmc_amd: {} must be dense {} float64 on {}, got {} {} on {}".format(
+                    name, shapes[name], device, tuple(tensor.shape), tensor.dtype, tensor.device))
+        return _lib.SwitchingModel(*([_ptr(model[name]) for name in self.SWITCHING_MODEL_KEYS] + [M, D, Dy])), M, D, Dy
+
+    @staticmethod
+    def _switching_state(state, B, K, D, device):
+        """The stored (regime, mean, cov) of a step, validated and dense."""
+        regime, mean, cov = state
+        TD = D * (D + 1) // 2
+        for tensor, shape, dtype, what in ((regime, (B, K), torch.int32, "regime"), (mean, (B, K, D), torch.float64, "mean"),
+                                           (cov, (B, K, TD), torch.float64, "cov")):
+            _require_hip(tensor, what)
+            if tuple(tensor.shape) != shape or tensor.dtype != dtype or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} {} on {}".format(what, shape, dtype, device))
+        return regime.contiguous(), mean.contiguous(), cov.contiguous()
+
     def switching_kalman_step(self, model, state, index, uniforms, observation):
         """One step of the Rao-Blackwellised filter of a switching linear-Gaussian model (aesmc_switching_kalman_step, K31).
         model: a dict of dense float64 tensors cdf0 [M], cdf [M,M], m0 [D], s0 [D], A [M,D,D], b [M,D], q [M,D], C [M,Dy,D],
@@ -2378,31 +2407,14 @@ class HipKernels:
         if uniforms.dim() != 2 or uniforms.dtype != torch.float64 or uniforms.device != device:
             raise ValueError("aesmc_amd: regime uniforms must be [batch_size, num_particles] float64 on {}".format(device))
         B, K = uniforms.shape
-        A, C = model["A"], model["C"]
-        M, D, Dy = (A.size(0), A.size(2), C.size(1)) if torch.is_tensor(A) and A.dim() == 3 and torch.is_tensor(C) and \
-            C.dim() == 3 else (0, 0, 0)
+        block, M, D, Dy = self._switching_block(model, device)
         TD = D * (D + 1) // 2
-        shapes = {"cdf0": (M,), "cdf": (M, M), "m0": (D,), "s0": (D,), "A": (M, D, D), "b": (M, D), "q": (M, D),
-                  "C": (M, Dy, D), "d": (M, Dy), "r": (M, Dy)}
-        for name in self.SWITCHING_MODEL_KEYS:
-            tensor = model[name]
-            _require_hip(tensor, name)
-            if tuple(tensor.shape) != shapes[name] or tensor.dtype != torch.float64 or tensor.device != device or \
-                    not tensor.is_contiguous():
-                raise ValueError("aesmc_amd: {} must be dense {} float64 on {}, got {} {} on {}".format(
-                    name, shapes[name], device, tuple(tensor.shape), tensor.dtype, tensor.device))
         if tuple(observation.shape) != (B, Dy):
             raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
         if not self.switching_covers(observation, M, D, Dy, K):
             raise ValueError("aesmc_amd: switching_kalman_step does not take these operands (see switching_covers)")
         if state is not None:
-            regime, mean, cov = state
-            for tensor, shape, dtype, what in ((regime, (B, K), torch.int32, "regime"), (mean, (B, K, D), torch.float64, "mean"),
-                                               (cov, (B, K, TD), torch.float64, "cov")):
-                _require_hip(tensor, what)
-                if tuple(tensor.shape) != shape or tensor.dtype != dtype or tensor.device != device:
-                    raise ValueError("aesmc_amd: {} must be {} {} on {}".format(what, shape, dtype, device))
-            regime, mean, cov = regime.contiguous(), mean.contiguous(), cov.contiguous()
+            regime, mean, cov = self._switching_state(state, B, K, D, device)
             if index is not None:
                 index = as_index(index)
                 if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != device:
@@ -2417,7 +2429,6 @@ class HipKernels:
         log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
         if log_weight.numel() == 0:
             return out_regime, out_mean, out_cov, log_weight
-        block = _lib.SwitchingModel(*([_ptr(model[name]) for name in self.SWITCHING_MODEL_KEYS] + [M, D, Dy]))
         per_particle = 8 + 2 * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) if state is not None else \
             8 + (4 + 8 * D + 8 * TD) + 8
         self._launch(device, self._lib.aesmc_switching_kalman_step,
@@ -2429,6 +2440,102 @@ class HipKernels:
                      (model, regime, mean, cov, index, uniforms, observation, out_regime, out_mean, out_cov, log_weight,
                       block), name="switching_kalman_step")
         return out_regime, out_mean, out_cov, log_weight
+
+    # ---- K32, K33 ------------------------------------------------------------------------------
+    def switching_lookahead(self, model, log_prior, state, observation, num_particles=None):
+        """The look-ahead of the fully adapted filter of a switching linear-Gaussian model (aesmc_switching_lookahead, K32):
+        per stored particle one Kalman prediction per regime, the exact first-stage log-weight log p(y | history) and the
+        cumulative row of the exact regime posterior.  model, state, observation as `switching_kalman_step`'s; log_prior:
+        float64 [M,M] with a state (log Pi), [M] without one (log pi0; `num_particles` then gives K).  Returns (log_weight
+        [B,K], cdf [B,K,M]) float64, new tensors.  A stored regime outside [0, M) gives NaN there and
+        FLAG_INDEX_OUT_OF_RANGE."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        device = observation.device
+        block, M, D, Dy = self._switching_block(model, device)
+        if observation.dim() != 2 or observation.size(1) != Dy:
+            raise ValueError("aesmc_amd: observation must be [batch_size, {}], got {}".format(Dy, tuple(observation.shape)))
+        B = observation.size(0)
+        if state is None:
+            if num_particles is None or int(num_particles) < 0:
+                raise ValueError("aesmc_amd: switching_lookahead without a state needs num_particles")
+            K = int(num_particles)
+        else:
+            K = state[0].size(1) if torch.is_tensor(state[0]) and state[0].dim() == 2 else -1
+            if num_particles is not None and int(num_particles) != K:
+                raise ValueError("aesmc_amd: num_particles ({}) disagrees with the state ({})".format(num_particles, K))
+        if not self.switching_covers(observation, M, D, Dy, K):
+            raise ValueError("aesmc_amd: switching_lookahead does not take these operands (see switching_covers)")
+        _require_hip(log_prior, "log_prior")
+        want = (M,) if state is None else (M, M)
+        if tuple(log_prior.shape) != want or log_prior.dtype != torch.float64 or log_prior.device != device:
+            raise ValueError("aesmc_amd: log_prior must be {} float64 on {}, got {} {} on {}".format(
+                want, device, tuple(log_prior.shape), log_prior.dtype, log_prior.device))
+        log_prior = log_prior.contiguous()
+        regime, mean, cov = (None, None, None) if state is None else self._switching_state(state, B, K, D, device)
+        observation = observation.contiguous()
+        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
+        cdf = torch.empty((B, K, M), dtype=torch.float64, device=device)
+        if log_weight.numel() == 0:
+            return log_weight, cdf
+        TD = D * (D + 1) // 2
+        per_particle = (4 + 8 * D + 8 * TD if state is not None else 0) + 8 + 8 * M
+        self._launch(device, self._lib.aesmc_switching_lookahead,
+                     (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
+                      _ptr(log_weight), _ptr(cdf), _ptr(self.flags(device)), B, K, self._stream(observation)),
+                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
+                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                     (model, log_prior, regime, mean, cov, observation, log_weight, cdf, block), name="switching_lookahead")
+        return log_weight, cdf
+
+    def switching_kalman_draw(self, model, state, index, uniforms, cdf, observation):
+        """`switching_kalman_step` with the regime drawn from a cumulative row per particle (aesmc_switching_kalman_draw,
+        K33): cdf float64 [B,K,M], read at the ancestor's position (`switching_lookahead`'s).  Returns (regime, mean, cov,
+        log_likelihood [B,K] float64), new tensors; regimes, flags and NaNs as `switching_kalman_step`'s."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        _require_hip(uniforms, "regime uniforms")
+        device = observation.device
+        if uniforms.dim() != 2 or uniforms.dtype != torch.float64 or uniforms.device != device:
+            raise ValueError("aesmc_amd: regime uniforms must be [batch_size, num_particles] float64 on {}".format(device))
+        B, K = uniforms.shape
+        block, M, D, Dy = self._switching_block(model, device)
+        TD = D * (D + 1) // 2
+        if tuple(observation.shape) != (B, Dy):
+            raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
+        if not self.switching_covers(observation, M, D, Dy, K):
+            raise ValueError("aesmc_amd: switching_kalman_draw does not take these operands (see switching_covers)")
+        _require_hip(cdf, "cdf")
+        if tuple(cdf.shape) != (B, K, M) or cdf.dtype != torch.float64 or cdf.device != device:
+            raise ValueError("aesmc_amd: cdf must be {} float64 on {}".format((B, K, M), device))
+        cdf = cdf.contiguous()
+        if state is not None:
+            regime, mean, cov = self._switching_state(state, B, K, D, device)
+            if index is not None:
+                index = as_index(index)
+                if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != device:
+                    raise ValueError("aesmc_amd: index must be [{}, {}] int64 on {}".format(B, K, device))
+                index = index.contiguous()
+        else:
+            regime = mean = cov = index = None
+        uniforms, observation = uniforms.contiguous(), observation.contiguous()
+        out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
+        out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
+        out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
+        log_likelihood = torch.empty((B, K), dtype=torch.float64, device=device)
+        if log_likelihood.numel() == 0:
+            return out_regime, out_mean, out_cov, log_likelihood
+        per_particle = 8 + 8 * M + (2 if state is not None else 1) * (4 + 8 * D + 8 * TD) + 8 + \
+            (8 if index is not None else 0)
+        self._launch(device, self._lib.aesmc_switching_kalman_draw,
+                     (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms), _ptr(cdf),
+                      _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_likelihood),
+                      _ptr(self.flags(device)), B, K, self._stream(observation)),
+                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
+                     8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
+                     (model, regime, mean, cov, index, uniforms, cdf, observation, out_regime, out_mean, out_cov,
+                      log_likelihood, block), name="switching_kalman_draw")
+        return out_regime, out_mean, out_cov, log_likelihood
 
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256

@@ -133,6 +133,8 @@ SIGNATURES = {
     "aesmc_switching_max_observation_dim": (_i64, []),
     "aesmc_switching_max_regimes": (_i64, []),
     "aesmc_switching_kalman_step": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 11 + [_i64, _i64, _vp]),
+    "aesmc_switching_lookahead": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 8 + [_i64, _i64, _vp]),
+    "aesmc_switching_kalman_draw": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 12 + [_i64, _i64, _vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

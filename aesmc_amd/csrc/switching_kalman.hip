@@ -1,6 +1,10 @@
 // One step of the Rao-Blackwellised particle filter (mixture Kalman filter; Doucet, de Freitas, Murphy & Russell 2000; Chen &
 // Liu 2000) for a switching linear-Gaussian state-space model — aesmc_switching_kalman_step (K31) of include/aesmc_hip.h.
 //
+// The same kernel is aesmc_switching_kalman_draw (K33): one more pointer, `particle_cdf`, from whose row at the ancestor's
+// position the regime is drawn instead of from the chain's rows (the fully adapted filter: switching_lookahead.hip writes
+// those rows).  NULL for K31, whose arithmetic and order it does not touch.
+//
 // Only the regimes are sampled.  Particle k of batch row b carries (s, m, P): its regime and the exact Kalman mean and
 // covariance of the continuous state given its regime history.  One launch, per particle: the gather through the ancestors,
 // the inverse-CDF regime draw, the Kalman predict, the Dy x Dy Cholesky factor of the innovation covariance, two triangular
@@ -20,7 +24,7 @@
 //
 // Compiler's resource report (-Rpass-analysis=kernel-resource-usage, gfx950, 256 lanes per workgroup):
 //   <DP,DYP>  VGPRs  AGPRs  scratch B/lane  waves/SIMD
-//   <2,2>        63      0        0             7
+//   <2,2>        64      0        0             7
 //   <2,4>        95      0        0             5
 //   <2,8>       208      0        0             2
 //   <4,2>        89      0        0             5
@@ -37,17 +41,13 @@
 //
 // Traffic per particle at D = Dy = 4: 8 (ancestor) + 8 (uniform) + 2 (4 + 32 + 80) (state in and out) + 8 (log-weight) =
 // 256 bytes; at D = 8: 736 bytes.
-#include "common.hpp"
+#include "switching_kalman.hpp"
 
 namespace aesmc {
 
-constexpr int kSkBlock = 256;
-constexpr int kSkMaxDim = 8;        // D and Dy
-constexpr int kSkMaxRegimes = 16;
-constexpr double kHalfLog2Pi = 0.9189385332046727;
-
 struct SwitchingArgs {
-  const double *cdf;                // [M,M] (later steps) or [M] (step 0)
+  const double *cdf;                // [M,M] (later steps) or [M] (step 0); not read when particle_cdf is given
+  const double *particle_cdf;       // K33: [B,K,M], the row of the ancestor's position; NULL: K31
   const double *m0, *s0;            // [D]
   const double *A, *b, *q, *C, *d, *r;
   const int32_t *regime_in;         // NULL: step 0
@@ -63,29 +63,6 @@ struct SwitchingArgs {
   int M, D, Dy, y_is_float;
 };
 
-// whether an instantiation keeps the predicted covariance in LDS (see SkCov)
-__host__ __device__ constexpr bool sk_cov_in_lds(int dp) { return dp == 8; }
-// The compiler otherwise keeps every model value it has read once in a register for its later uses (128 VGPRs per 8 x 8
-// matrix): after this it reads LDS again
-#define SK_REREAD_LDS() asm volatile("" ::: "memory")
-
-__host__ __device__ constexpr int sk_tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
-
-// A lane's packed predicted covariance P-: in registers, or (the 8-wide instantiations, which would spill) in LDS in an
-// [element][lane] layout — consecutive lanes on consecutive banks, no conflicts
-template <int TP, bool InLds> struct SkCov {
-  double reg[InLds ? 1 : TP];
-  double *lds;
-  __device__ __forceinline__ double get(int e) const {
-    if constexpr (InLds) return lds[e * kSkBlock];
-    else return reg[e];
-  }
-  __device__ __forceinline__ void set(int e, double v) {
-    if constexpr (InLds) lds[e * kSkBlock] = v;
-    else reg[e] = v;
-  }
-};
-
 // LDS: [M * M] (or [M]) cumulative rows, then per regime kPer values: A [DP,DP], b [DP], q^2 [DP], C [DYP,DP], d [DYP],
 // r^2 [DYP]; then, for DP == 8, [TP][256] predicted covariances
 template <int DP, int DYP>
@@ -95,34 +72,11 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
   constexpr int TP = DP * (DP + 1) / 2, TY = DYP * (DYP + 1) / 2;
   const int M = a.M, D = a.D, Dy = a.Dy;
   const bool later = a.regime_in != nullptr;
-  const int ncdf = later ? M * M : M;
+  const int ncdf = a.particle_cdf != nullptr ? 0 : later ? M * M : M;
   double *cdf = sk_smem;
   double *mdl = sk_smem + ncdf;
   for (int e = threadIdx.x; e < ncdf; e += kSkBlock) cdf[e] = a.cdf[e];
-  for (int e = threadIdx.x; e < M * kPer; e += kSkBlock) {
-    const int s = e / kPer;
-    int o = e - s * kPer;
-    double v;
-    if (o < DP * DP) {
-      const int i = o / DP, l = o - i * DP;
-      v = (i < D && l < D) ? a.A[(s * D + i) * D + l] : 0.0;
-    } else if ((o -= DP * DP) < DP) {
-      v = o < D ? a.b[s * D + o] : 0.0;
-    } else if ((o -= DP) < DP) {
-      const double q = o < D ? a.q[s * D + o] : 0.0;
-      v = q * q;
-    } else if ((o -= DP) < DYP * DP) {
-      const int i = o / DP, l = o - i * DP;
-      v = (i < Dy && l < D) ? a.C[(s * Dy + i) * D + l] : 0.0;
-    } else if ((o -= DYP * DP) < DYP) {
-      v = o < Dy ? a.d[s * Dy + o] : 0.0;
-    } else {
-      o -= DYP;
-      const double r = o < Dy ? a.r[s * Dy + o] : 1.0;
-      v = r * r;
-    }
-    mdl[e] = v;
-  }
+  sk_stage_model<DP, DYP>(mdl, M, D, Dy, a.A, a.b, a.q, a.C, a.d, a.r);
   __syncthreads();
   const int64_t n = (int64_t)blockIdx.x * kSkBlock + threadIdx.x;
   if (n >= a.N) return;
@@ -149,7 +103,7 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
     return;
   }
   const double u = a.uniforms[n];
-  const double *row = cdf + (later ? s_prev * M : 0);
+  const double *row = a.particle_cdf != nullptr ? a.particle_cdf + src * M : cdf + (later ? s_prev * M : 0);
   int s = 0;
   for (int i = 0; i < M - 1; ++i) s += row[i] <= u ? 1 : 0;
 
@@ -309,9 +263,6 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
   }
 }
 
-static inline bool sk_aligned(const void *p, size_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-static inline int sk_pad(int64_t d) { return d <= 2 ? 2 : d <= 4 ? 4 : 8; }
-
 template <int DP, int DYP>
 static bool sk_launch(dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
   // the 8-wide instantiations (72 KB of covariances beside the model) need the limit raised; on every launch — no state to
@@ -337,12 +288,15 @@ extern "C" int64_t aesmc_switching_max_latent_dim(void) { return aesmc::kSkMaxDi
 extern "C" int64_t aesmc_switching_max_observation_dim(void) { return aesmc::kSkMaxDim; }
 extern "C" int64_t aesmc_switching_max_regimes(void) { return aesmc::kSkMaxRegimes; }
 
-extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
-                                           const double *mean_in, const double *cov_in, const int64_t *idx,
-                                           const double *uniforms, const void *y, int32_t *regime_out, double *mean_out,
-                                           double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
-                                           void *stream) {
-  using namespace aesmc;
+namespace aesmc {
+
+// K31 (particle_cdf NULL, `draw` false) and K33 (`draw`: the regime from particle_cdf [B,K,M], the model's own cumulative
+// rows not read): one set of checks, one launch
+static int sk_step(bool draw, int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                   const double *mean_in, const double *cov_in, const int64_t *idx, const double *uniforms,
+                   const double *particle_cdf, const void *y, int32_t *regime_out, double *mean_out, double *cov_out,
+                   double *log_weight, int32_t *flags, int64_t B, int64_t K, void *stream) {
+  if (draw && (particle_cdf == nullptr || !sk_aligned(particle_cdf, 8))) return AESMC_ERR_INVALID_ARGUMENT;
   if (model == nullptr || uniforms == nullptr || y == nullptr || regime_out == nullptr || mean_out == nullptr ||
       cov_out == nullptr || log_weight == nullptr || B < 0 || K < 0)
     return AESMC_ERR_INVALID_ARGUMENT;
@@ -350,8 +304,9 @@ extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_mo
   const bool later = regime_in != nullptr;
   if (later != (mean_in != nullptr) || later != (cov_in != nullptr)) return AESMC_ERR_INVALID_ARGUMENT;
   if (model->M < 1 || model->D < 1 || model->Dy < 1) return AESMC_ERR_INVALID_ARGUMENT;
-  const double *operands[] = {later ? model->cdf : model->cdf0, model->m0, model->s0, model->A, model->b, model->q,
-                              model->C, model->d, model->r};
+  const double *rows = later ? model->cdf : model->cdf0;
+  if (!draw && (rows == nullptr || !sk_aligned(rows, 8))) return AESMC_ERR_INVALID_ARGUMENT;
+  const double *operands[] = {model->m0, model->s0, model->A, model->b, model->q, model->C, model->d, model->r};
   for (const double *p : operands)
     if (p == nullptr || !sk_aligned(p, 8)) return AESMC_ERR_INVALID_ARGUMENT;
   if (!sk_aligned(regime_in, 4) || !sk_aligned(mean_in, 8) || !sk_aligned(cov_in, 8) || !sk_aligned(idx, 8) ||
@@ -359,12 +314,15 @@ extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_mo
       !sk_aligned(mean_out, 8) || !sk_aligned(cov_out, 8) || !sk_aligned(log_weight, 8) || !sk_aligned(flags, 4))
     return AESMC_ERR_INVALID_ARGUMENT;
   if (later && (regime_out == regime_in || mean_out == mean_in || cov_out == cov_in)) return AESMC_ERR_INVALID_ARGUMENT;
+  if (draw && (particle_cdf == mean_out || particle_cdf == cov_out || particle_cdf == log_weight))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (B == 0 || K == 0) return AESMC_OK;
   if (model->D > kSkMaxDim || model->Dy > kSkMaxDim || model->M > kSkMaxRegimes) return AESMC_ERR_UNSUPPORTED;
   if (B > 0x7fffffffLL || K > 0x7fffffffLL || B * K > 0x7fffffffLL / (kSkMaxDim * (kSkMaxDim + 1) / 2))
     return AESMC_ERR_UNSUPPORTED;
   SwitchingArgs a;
-  a.cdf = later ? model->cdf : model->cdf0;
+  a.cdf = draw ? nullptr : later ? model->cdf : model->cdf0;
+  a.particle_cdf = draw ? particle_cdf : nullptr;
   a.m0 = model->m0, a.s0 = model->s0;
   a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
   a.regime_in = regime_in, a.mean_in = mean_in, a.cov_in = cov_in;
@@ -376,11 +334,31 @@ extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_mo
   a.y_is_float = y_dtype == AESMC_F32;
   const int dp = sk_pad(model->D), dyp = sk_pad(model->Dy);
   const size_t per = (size_t)dp * dp + 2 * dp + (size_t)dyp * dp + 2 * dyp;
-  const size_t lds = ((later ? (size_t)a.M * a.M : (size_t)a.M) + (size_t)a.M * per + (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0)) *
+  const size_t lds = ((draw ? 0 : later ? (size_t)a.M * a.M : (size_t)a.M) + (size_t)a.M * per + (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0)) *
                      sizeof(double);
   const dim3 grid((unsigned)((a.N + kSkBlock - 1) / kSkBlock));
   hipStream_t s = (hipStream_t)stream;
   const bool launched = dp == 2 ? sk_launch_dy<2>(dyp, grid, lds, s, a)
                         : dp == 4 ? sk_launch_dy<4>(dyp, grid, lds, s, a) : sk_launch_dy<8>(dyp, grid, lds, s, a);
   return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+}
+
+}  // namespace aesmc
+
+extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                           const double *mean_in, const double *cov_in, const int64_t *idx,
+                                           const double *uniforms, const void *y, int32_t *regime_out, double *mean_out,
+                                           double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
+                                           void *stream) {
+  return aesmc::sk_step(false, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, y, regime_out, mean_out,
+                        cov_out, log_weight, flags, B, K, stream);
+}
+
+extern "C" int aesmc_switching_kalman_draw(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                           const double *mean_in, const double *cov_in, const int64_t *idx,
+                                           const double *uniforms, const double *particle_cdf, const void *y,
+                                           int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
+                                           int32_t *flags, int64_t B, int64_t K, void *stream) {
+  return aesmc::sk_step(true, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, particle_cdf, y, regime_out,
+                        mean_out, cov_out, log_weight, flags, B, K, stream);
 }

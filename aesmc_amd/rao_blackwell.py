@@ -16,6 +16,18 @@ increment) and K31 (`aesmc_switching_kalman_step`): the gather through the ances
 Kalman predict, the Dy x Dy Cholesky factor, two triangular solves and the rank-Dy downdate, one lane per particle in
 float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
 
+    SwitchingLinearGaussian    the model
+    switching_filter           the bootstrap on the regimes described above
+    adapted_switching_filter   the look-ahead form: with M <= 16 regimes one Kalman prediction per regime gives every particle
+                               p(y_t | s_t = j, history) for all j, hence the exact first-stage weight p(y_t | history) and the
+                               exact regime posterior.  A step is the look-ahead K32 (`aesmc_switching_lookahead`) on the stored
+                               system, K2 on its log-weights, and K33 (`aesmc_switching_kalman_draw`: K31 with the regime drawn
+                               from the ancestor's posterior row).  The weights after the draw are all equal; at T = 1 the
+                               evidence is exact for any K, and a regime change is met in the step where it happens (Chen &
+                               Liu 2000; Doucet, Gordon & Krishnamurthy 2001; Pitt & Shephard 1999)
+    kalman_log_likelihood      one regime: the exact log p(y)
+    unpack_covariance          packed lower triangles -> symmetric matrices
+
 The reference has no counterpart; this module adds to its interface and changes none of it.
 """
 import math
@@ -165,6 +177,68 @@ def _moments(regimes, means, covariances, log_weights, num_regimes):
     return torch.stack(filtered_mean), torch.stack(filtered_cov), torch.stack(probabilities)
 
 
+def _check_arguments(name, observations, num_particles, regime_uniforms, resampling):
+    """(T, K, stratified) of a filter's arguments: what is checked before the provider is asked for anything."""
+    from . import distributed
+    num_timesteps, num_particles = len(observations), int(num_particles)
+    if num_timesteps == 0:
+        raise ValueError("{}: observations must hold at least one timestep".format(name))
+    if num_particles < 1:
+        raise ValueError("{}: num_particles must be at least 1".format(name))
+    if regime_uniforms is not None and len(regime_uniforms) != num_timesteps:
+        raise ValueError("{}: regime_uniforms must hold one tensor per timestep ({}), got {}".format(
+            name, num_timesteps, len(regime_uniforms)))
+    stratified = inference._resolve_resampling(resampling) == "stratified"
+    if regime_uniforms is None and distributed.active_shard() is not None:
+        raise NotImplementedError(
+            "aesmc_amd.rao_blackwell: drawing the regime uniforms inside distributed.shard_scope is not implemented: a "
+            "sharded run reproduces the unsharded one through the global block of host uniforms every rank draws, which "
+            "per-particle device draws do not have. Pass regime_uniforms when sharding.")
+    return num_timesteps, num_particles, stratified
+
+
+def _check_observations(name, provider, observations, model, num_particles):
+    """(batch_size, device) of the observations, or the refusal: [batch_size, Dy] tensors the provider's step covers."""
+    M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
+    for y in observations:
+        if not torch.is_tensor(y) or y.dim() != 2 or y.size(1) != Dy or y.size(0) != observations[0].size(0):
+            raise ValueError("{}: observations must be [batch_size, {}] tensors".format(name, Dy))
+    batch_size, device = observations[0].size(0), observations[0].device
+    if provider.name == "hip":
+        _kernels._require_hip(observations[0], "observations")      # (no CPU fallback)
+    if not provider.switching_covers(observations[0], M, D, Dy, num_particles):
+        _refuse("these observations ({} {} on {})".format(tuple(observations[0].shape), observations[0].dtype, device))
+    return batch_size, device
+
+
+def _regime_draws(name, regime_uniforms, shape, device):
+    """time -> the step's regime uniforms: fresh from torch's device generator, or the replayed tensor, validated."""
+    def draw(time):
+        if regime_uniforms is None:
+            return torch.rand(shape, dtype=torch.float64, device=device)
+        u = regime_uniforms[time]
+        if not torch.is_tensor(u) or tuple(u.shape) != shape or u.dtype != torch.float64 or u.device != device:
+            raise ValueError("{}: regime_uniforms[{}] must be {} float64 on {}".format(name, time, shape, device))
+        return u
+    return draw
+
+
+def _resampling_uniforms(feed, stratified, batch_size, num_particles, num_timesteps, device):
+    """(feed, the next step's resampling uniforms): the feed is `infer`'s (an override, or the scheme's own, made at the
+    first resampling step), and what it returns must have the scheme's shape."""
+    if feed is None:
+        feed = inference._FEED_OVERRIDE.get() or (
+            inference._StratifiedFeed(batch_size, num_particles, device) if stratified else
+            inference._UniformFeed(batch_size, num_timesteps - 1, device))
+    uniforms = feed.next()
+    per_particle = uniforms.dim() == 2 and tuple(uniforms.shape) == (batch_size, num_particles)
+    if per_particle != stratified and num_particles != 1:
+        raise ValueError("aesmc_amd: {} resampling takes {} uniforms per step, the feed returned {}".format(
+            "stratified" if stratified else "systematic",
+            "[batch_size, num_particles]" if stratified else "[batch_size]", tuple(uniforms.shape)))
+    return feed, uniforms
+
+
 def switching_filter(observations, model, num_particles, resampling=None, regime_uniforms=None, return_moments=False,
                      return_latents=False):
     """Runs the Rao-Blackwellised particle filter of a `SwitchingLinearGaussian`.
@@ -192,61 +266,21 @@ def switching_filter(observations, model, num_particles, resampling=None, regime
     positive definite gives NaN log-weights and FloatingPointError, a row without a finite maximum RuntimeError — read
     once, at the end; an exception on the way discards whatever was flagged.  No host synchronisation inside the step
     loop.  Runs under torch.no_grad(): NOT differentiable."""
-    from . import distributed
-    num_timesteps, num_particles = len(observations), int(num_particles)
-    if num_timesteps == 0:
-        raise ValueError("switching_filter: observations must hold at least one timestep")
-    if num_particles < 1:
-        raise ValueError("switching_filter: num_particles must be at least 1")
-    if regime_uniforms is not None and len(regime_uniforms) != num_timesteps:
-        raise ValueError("switching_filter: regime_uniforms must hold one tensor per timestep ({}), got {}".format(
-            num_timesteps, len(regime_uniforms)))
-    stratified = inference._resolve_resampling(resampling) == "stratified"
-    if regime_uniforms is None and distributed.active_shard() is not None:
-        raise NotImplementedError(
-            "aesmc_amd.rao_blackwell: drawing the regime uniforms inside distributed.shard_scope is not implemented: a "
-            "sharded run reproduces the unsharded one through the global block of host uniforms every rank draws, which "
-            "per-particle device draws do not have. Pass regime_uniforms when sharding.")
+    num_timesteps, num_particles, stratified = _check_arguments("switching_filter", observations, num_particles,
+                                                                regime_uniforms, resampling)
     provider = _kernels.get()
     try:
         with torch.no_grad(), _syncfree.scope():
             ops = model.operands()      # validation, expansion and the cumulative rows: once, before the loop
-            M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
-            for y in observations:
-                if not torch.is_tensor(y) or y.dim() != 2 or y.size(1) != Dy or y.size(0) != observations[0].size(0):
-                    raise ValueError("switching_filter: observations must be [batch_size, {}] tensors".format(Dy))
-            batch_size, device = observations[0].size(0), observations[0].device
-            if provider.name == "hip":
-                _kernels._require_hip(observations[0], "observations")      # (no CPU fallback)
-            if not provider.switching_covers(observations[0], M, D, Dy, num_particles):
-                _refuse("these observations ({} {} on {})".format(tuple(observations[0].shape), observations[0].dtype,
-                                                                   device))
-            shape = (batch_size, num_particles)
-
-            def draw(time):
-                if regime_uniforms is None:
-                    return torch.rand(shape, dtype=torch.float64, device=device)
-                u = regime_uniforms[time]
-                if not torch.is_tensor(u) or tuple(u.shape) != shape or u.dtype != torch.float64 or u.device != device:
-                    raise ValueError("switching_filter: regime_uniforms[{}] must be {} float64 on {}".format(
-                        time, shape, device))
-                return u
-
+            M = model.num_regimes
+            batch_size, device = _check_observations("switching_filter", provider, observations, model, num_particles)
+            draw = _regime_draws("switching_filter", regime_uniforms, (batch_size, num_particles), device)
             log_z = torch.zeros(batch_size, dtype=torch.float64, device=device)
             regimes, means, covariances, log_weights, ancestral = [], [], [], [], []
             state, index, feed = None, None, None
             for time in range(num_timesteps):
                 if time > 0:
-                    if feed is None:
-                        feed = inference._FEED_OVERRIDE.get() or (
-                            inference._StratifiedFeed(batch_size, num_particles, device) if stratified else
-                            inference._UniformFeed(batch_size, num_timesteps - 1, device))
-                    uniforms = feed.next()
-                    per_particle = uniforms.dim() == 2 and tuple(uniforms.shape) == shape
-                    if per_particle != stratified and num_particles != 1:
-                        raise ValueError("aesmc_amd: {} resampling takes {} uniforms per step, the feed returned {}".format(
-                            "stratified" if stratified else "systematic",
-                            "[batch_size, num_particles]" if stratified else "[batch_size]", tuple(uniforms.shape)))
+                    feed, uniforms = _resampling_uniforms(feed, stratified, batch_size, num_particles, num_timesteps, device)
                     index, lse, _ = _ops.resample_step(log_weights[-1], uniforms, None, want_lse=True)
                     index = _kernels.as_index(index)
                     log_z = log_z + (lse.to(torch.float64) - math.log(num_particles))
@@ -265,6 +299,71 @@ def switching_filter(observations, model, num_particles, resampling=None, regime
                 out["latents"] = inference.get_resampled_latents(regimes, ancestral)
             inference._raise_for_flags(provider.read_flags(device))
             # (the last step's log-weights meet no resampling launch: a NaN among them is reported here, after the one read)
+            if bool(torch.isnan(log_z).any()):
+                raise FloatingPointError("log_weight contains nan element(s)")
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
+
+
+def adapted_switching_filter(observations, model, num_particles, resampling=None, regime_uniforms=None,
+                             return_moments=False, return_latents=False):
+    """Runs the fully adapted (look-ahead) Rao-Blackwellised filter of a `SwitchingLinearGaussian`: every step resamples on
+    the exact first-stage weights p(y_t | history) and draws the regime from its exact posterior p(s_t | history, y_t).
+
+    Arguments, validation, refusals and feeds as `switching_filter` (T - 1 blocks of resampling uniforms, T of regime
+    uniforms).
+
+    Returns a dict: log_marginal_likelihood [batch_size] float64 (unbiased for p(y_0..y_{T-1}); exact for M = 1 and, for any
+    K, at T = 1); regimes (T int32 [batch_size, K]), means, covariances (packed, as `switching_filter`'s) — the T stored,
+    EQUALLY WEIGHTED systems after the draw; first_stage_log_weights (T float64 [batch_size, K]: the look-ahead of step t on
+    system t-1, of step 0 on the prior, where all K are equal); ancestral_indices (T-1 int64 [batch_size, K]).  With
+    return_moments, `switching_filter`'s three moments under equal weights; with return_latents, the regime genealogy.
+
+    An innovation covariance that is not positive definite under a regime of positive prior probability gives a NaN
+    first-stage weight and FloatingPointError (under a regime of probability zero it is ignored); flags are read once, at the
+    end; an exception on the way discards whatever was flagged.  No host synchronisation inside the step loop.  Runs under
+    torch.no_grad(): NOT differentiable."""
+    num_timesteps, num_particles, stratified = _check_arguments("adapted_switching_filter", observations, num_particles,
+                                                                regime_uniforms, resampling)
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops = model.operands()
+            M = model.num_regimes
+            batch_size, device = _check_observations("adapted_switching_filter", provider, observations, model,
+                                                     num_particles)
+            draw = _regime_draws("adapted_switching_filter", regime_uniforms, (batch_size, num_particles), device)
+            log_pi0, log_Pi = torch.log(ops["pi0"]), torch.log(ops["Pi"])      # (-inf where a probability is 0) once
+            log_z = torch.zeros(batch_size, dtype=torch.float64, device=device)
+            regimes, means, covariances, first_stage, ancestral = [], [], [], [], []
+            state, feed = None, None
+            for time in range(num_timesteps):
+                regime_u = draw(time)      # (a replayed tensor of the wrong shape is refused before the step's launches)
+                log_w, cdf = provider.switching_lookahead(ops, log_pi0 if time == 0 else log_Pi, state, observations[time],
+                                                          num_particles=num_particles)
+                if time == 0:
+                    index, lse = None, _ops.row_logsumexp(log_w)
+                else:
+                    feed, uniforms = _resampling_uniforms(feed, stratified, batch_size, num_particles, num_timesteps, device)
+                    index, lse, _ = _ops.resample_step(log_w, uniforms, None, want_lse=True)
+                    index = _kernels.as_index(index)
+                    ancestral.append(index)
+                log_z = log_z + (lse.to(torch.float64) - math.log(num_particles))
+                regime, mean, cov, _ = provider.switching_kalman_draw(ops, state, index, regime_u, cdf, observations[time])
+                state = (regime, mean, cov)
+                regimes.append(regime), means.append(mean), covariances.append(cov), first_stage.append(log_w)
+            out = {"log_marginal_likelihood": log_z, "regimes": regimes, "means": means, "covariances": covariances,
+                   "first_stage_log_weights": first_stage, "ancestral_indices": ancestral}
+            if return_moments:
+                equal = torch.zeros((batch_size, num_particles), dtype=torch.float64, device=device)
+                out["filtered_mean"], out["filtered_covariance"], out["regime_probabilities"] = _moments(
+                    regimes, means, covariances, [equal] * num_timesteps, M)
+            if return_latents:
+                out["latents"] = inference.get_resampled_latents(regimes, ancestral)
+            inference._raise_for_flags(provider.read_flags(device))
+            # (step 0's first-stage weights meet no resampling launch: a NaN among them is reported here, after the one read)
             if bool(torch.isnan(log_z).any()):
                 raise FloatingPointError("log_weight contains nan element(s)")
     except BaseException:

@@ -465,3 +465,277 @@ def example_step(B, K, M, D, Dy, index="none", later=True, observation_dtype=np.
         if index == "sorted":
             idx = np.sort(idx, axis=1)
     return model, state, idx, uniforms, y
+
+
+# ---- the fully adapted filter: the look-ahead (K32), the draw (K33) and the pass they make -----------------------------------------
+# The regimes are drawn from their exact posterior (Chen & Liu 2000; Doucet, Gordon & Krishnamurthy 2001; the fully adapted
+# auxiliary particle filter of Pitt & Shephard 1999).  For the STORED particle (s, m, P) and every regime j, with l_j the
+# step's log-likelihood under s_t = j (everything above up to `log w`, the draw replaced by j, no ancestors):
+#
+#     g_j     = log_prior[s, j] + l_j (step 0: log_prior[j]); -inf where the log-prior is -inf WHATEVER l_j is (a pivot that
+#               is not positive there is ignored); NaN where the log-prior is finite and a pivot is not positive
+#     log w   = top + log(0 + sum_j exp(g_j - top)),  top = max_j g_j
+#     cdf_j   = 0 + sum_{i <= j} exp(g_i - log w); exactly 1 from the last i with exp(g_i - log w) > 0 onwards
+#
+# and the draw is the step with s = #{ i < M-1 : cdf[b,a,i] <= uniforms[b,k] } for the ancestor a.
+def _forced(model, regime):
+    """(model, uniforms) under which `_step` draws exactly `regime` [B,K] for every particle whatever its ancestor: every
+    cumulative row replaced by (1/M, 2/M, .., 1) and the uniform by (regime + 1/2) / M.  Nothing else of the step changes."""
+    M = model["A"].shape[0]
+    edges = (np.arange(M) + 1.0) / M
+    shim = dict(model, cdf0=edges, cdf=np.ascontiguousarray(np.broadcast_to(edges, (M, M))))
+    return shim, (np.asarray(regime, dtype=np.float64) + 0.5) / M
+
+
+def _exp(x):
+    """exp to within two units in the last place (a device's library exponential); an argument off by e moves it by at most
+    exp(x) (exp(e) - 1)."""
+    xv, xe = x
+    value = np.exp(xv)
+    if xe is None:
+        return value, None
+    return value, value * np.expm1(xe) + 2 * UNIT * value
+
+
+def _minus(x, y):
+    """x - y, one rounding; exact (and -inf) where x is -inf."""
+    (xv, xe), (yv, ye) = x, y
+    value = xv - yv
+    if xe is None:
+        return value, None
+    return value, np.where(np.isneginf(value), 0.0, xe + ye + UNIT * np.abs(value))
+
+
+def _lookahead(model, log_prior, state, y, num_particles, dtype, track):
+    y = np.asarray(y)
+    B, M = y.shape[0], model["A"].shape[0]
+    K = int(num_particles) if state is None else np.asarray(state[0]).shape[1]
+    log_prior = np.asarray(log_prior, dtype=np.float64)
+    zero = np.zeros((B, K), dtype=dtype)
+    given = lambda array: (np.asarray(array).astype(dtype), zero if track else None)
+    one = given(zero + 1.0)
+    bad = np.zeros((B, K), dtype=bool)
+    if state is None:
+        prior = np.broadcast_to(log_prior, (B, K, M))
+    else:
+        previous = np.asarray(state[0])
+        bad = (previous < 0) | (previous >= M)
+        prior = log_prior[np.where(bad, 0, previous)]
+    flags, scores = 0, []
+    for j in range(M):
+        shim, forced = _forced(model, np.full((B, K), j))
+        (_, _, _, ell, bits), (_, _, ell_e) = _step(shim, state, None, forced, y, dtype, track)
+        flags |= bits
+        excluded = np.isneginf(prior[:, :, j])
+        value, error = _chain(given(np.where(excluded, 0.0, prior[:, :, j])), [((ell, ell_e), one)])
+        value = np.where(excluded & ~bad, -np.inf, value)
+        scores.append((value, np.where(excluded, 0.0, error) if track else None))
+    top = scores[0][0]
+    for value, _ in scores[1:]:
+        top = np.maximum(top, value)      # (a NaN stays)
+    top = (top, np.maximum.reduce([error for _, error in scores]) if track else None)
+    total = _chain(given(zero), [(_exp(_minus(score, top)), one) for score in scores])
+    log_w = _chain(top, [(_log(total), one)])
+    terms = [_exp(_minus(score, log_w)) for score in scores]
+    running, rows = given(zero), []
+    for term in terms:
+        running = _chain(running, [(term, one)])
+        rows.append(running)
+    positive = np.stack([term[0] > 0 for term in terms], axis=-1)
+    last = M - 1 - np.argmax(positive[:, :, ::-1], axis=-1)
+    forced_one = np.arange(M)[None, None, :] >= last[:, :, None]
+    invalid = np.isnan(log_w[0])
+    cdf = np.stack([row[0] for row in rows], axis=-1)
+    cdf_e = None
+    if track:      # (where both sides set the entry to 1 the distance is 0; where they disagree on `last`, this)
+        cdf_e = np.stack([row[1] for row in rows], axis=-1).astype(np.float64)
+        cdf_e = np.where(forced_one, cdf_e + np.abs(1.0 - cdf).astype(np.float64), cdf_e)
+        cdf_e[invalid] = 0.0
+    cdf = np.where(forced_one, 1.0, cdf).astype(dtype)
+    cdf[invalid] = np.nan
+    return (log_w[0], cdf, flags), (np.where(invalid, 0.0, log_w[1]).astype(np.float64) if track else None, cdf_e)
+
+
+def switching_lookahead(model, log_prior, state, y, num_particles=None, dtype=np.float64):
+    """(log_weight [B,K], cdf [B,K,M], flags) of one look-ahead (include/aesmc_hip.h: aesmc_switching_lookahead, K32).
+
+    model: `operands`' dict (cdf0 and cdf are not read); log_prior: float64 [M,M] with a state (rows: from-regime), [M]
+    without one — the logarithms of Pi or pi0, -inf where a probability is 0; state: None (step 0: every regime predicted by
+    m0 and diag(s0^2); `num_particles` gives K) or the stored (regime, mean, cov); y [B,Dy]; dtype: the arithmetic.
+    A stored regime outside [0, M): NaN log-weight and NaN CDF row, FLAG_INDEX_OUT_OF_RANGE.  A pivot that is not positive
+    under a regime of finite log-prior, or no regime of finite log-prior: NaN log-weight and NaN CDF row."""
+    with np.errstate(all="ignore"):
+        return _lookahead(model, log_prior, state, y, num_particles, dtype, False)[0]
+
+
+def switching_lookahead_bound(model, log_prior, state, y, num_particles=None):
+    """(bound of log_weight [B,K], of cdf [B,K,M]), float64: `switching_kalman_step_bound`'s running analysis carried on
+    through the scores (one addition), the log-sum-exp, the exponentials and the cumulative sum, with
+
+        exp(x):   exp(x) (exp(dx) - 1) + 2 u exp(x)                (a library exponential)
+        x - y:    dx + dy + u |x - y|                               (exact where x is -inf)
+        max_j:    the largest of the scores' bounds
+
+    and 2 * 1.01 times the running bound returned, as there.  Zero where the output is NaN."""
+    with np.errstate(all="ignore"):
+        _, (lw_e, cdf_e) = _lookahead(model, log_prior, state, y, num_particles, np.float64, True)
+    clean = lambda e: np.where(np.isfinite(e), 2 * 1.01 * e, np.inf)
+    return clean(lw_e), clean(cdf_e)
+
+
+def _draw(model, state, idx, uniforms, cdf, y, dtype, track):
+    uniforms = np.asarray(uniforms, dtype=np.float64)
+    B, K = uniforms.shape
+    M = model["A"].shape[0]
+    rows = np.asarray(cdf, dtype=np.float64)
+    if state is not None and idx is not None:
+        idx = np.asarray(idx)
+        rows = rows[np.arange(B)[:, None], np.where((idx < 0) | (idx >= K), 0, idx)]
+    s = (rows[:, :, :M - 1] <= uniforms[:, :, None]).sum(axis=2)      # (a NaN row: regime 0)
+    shim, forced = _forced(model, s)
+    return _step(shim, state, idx, forced, y, dtype, track), rows
+
+
+def switching_kalman_draw(model, state, idx, uniforms, cdf, y, dtype=np.float64):
+    """(regime int32 [B,K], mean, cov, log_likelihood [B,K], flags): `switching_kalman_step` with the regime drawn from the
+    ancestor's row of `cdf` [B,K,M] (include/aesmc_hip.h: aesmc_switching_kalman_draw, K33) — `_step` itself under
+    `_forced`.  Everything else, the conventions included, as `switching_kalman_step`."""
+    with np.errstate(all="ignore"):
+        return _draw(model, state, idx, uniforms, cdf, y, dtype, False)[0][0]
+
+
+def switching_kalman_draw_bound(model, state, idx, uniforms, cdf, y):
+    """`switching_kalman_step_bound` of the draw: (bound of mean, of cov, of log_likelihood)."""
+    with np.errstate(all="ignore"):
+        (_, (mean_e, cov_e, ll_e)), _ = _draw(model, state, idx, uniforms, cdf, y, np.float64, True)
+    clean = lambda e: np.where(np.isfinite(e), 2 * 1.01 * e, np.inf)
+    return clean(mean_e), clean(cov_e), clean(ll_e)
+
+
+def score_from_cdf(log_weight, cdf, regime, bound_w=None, bound_c=None):
+    """(g_s [B,K], its bound or None): the score of regime `regime[b,k]` recovered from a look-ahead's outputs,
+    g_s = log(cdf_s - cdf_{s-1}) + log_weight (cdf_{-1} = 0).  With the look-ahead's bounds, how far the value recovered from
+    outputs within them may lie from the one recovered here: the difference d carries both entries' bounds, the logarithm
+    divides by d less that — infinite where nothing of d is left."""
+    B, K, _ = cdf.shape
+    rows, cols = np.arange(B)[:, None], np.arange(K)[None, :]
+    regime = np.asarray(regime).astype(np.int64)
+    below = np.where(regime > 0, cdf[rows, cols, np.maximum(regime - 1, 0)], 0.0)
+    d = cdf[rows, cols, regime] - below
+    with np.errstate(all="ignore"):
+        value = np.log(d) + log_weight
+        if bound_w is None:
+            return value, None
+        error = bound_c[rows, cols, regime] + np.where(regime > 0, bound_c[rows, cols, np.maximum(regime - 1, 0)], 0.0) + UNIT * d
+        bound = np.where(d > 2 * error, error / (d - error), np.inf) + 2 * UNIT * np.abs(np.log(d)) + UNIT + bound_w + \
+            UNIT * np.abs(value)
+    return value, 2 * 1.01 * bound
+
+
+def _regime_margin(rows, uniforms):
+    """The smallest |cdf[b,a,i] - u[b,k]| over i < M-1: only a regime whose uniform lies this close to an entry of its row
+    can differ on the device.  An entry that is exactly 1 (set, not summed, on both sides) is above every uniform."""
+    edges = rows[:, :, :rows.shape[-1] - 1]
+    with np.errstate(invalid="ignore"):
+        distance = np.where(edges < 1.0, np.abs(edges - np.asarray(uniforms)[:, :, None]), np.inf)
+    return float(distance.min()) if distance.size else float("inf")
+
+
+def adapted_switching_pass(observations, model, num_particles, regime_uniforms, resampling_uniforms):
+    """The fully adapted filter on replayed uniforms: at every step the look-ahead on the stored system of the step before
+    (step 0: on the prior), the resampling on ITS log-weights (step 0: none), and the draw through the ancestors.  Arguments
+    as `switching_pass`.
+
+    Returns a dict: log_marginal_likelihood [B] float64 (the sum of the row log-sum-exps of the first-stage log-weights minus
+    log K each); regimes, means, covariances (T arrays each: the stored, equally weighted systems after the draw);
+    log_likelihoods (T x [B,K]: l_s of the draw, which the filter does not use); first_stage_log_weights (T x [B,K]);
+    ancestral_indices ((T-1) x int64 [B,K]); flags; margins: {"resampling": (T-1) floats, `ancestor_index`'s;
+    "regimes": T floats, the smallest distance of a regime uniform from an entry (below 1) of its posterior row}; and
+    tolerances, propagated as `switching_pass` propagates its own, with the factors of `_sensitivities`:
+
+        tol_P[t], tol_m[t]   as there, from the draw's bound
+        tol_g[t]  = 1.01 max_j (wm_j tol_m[t-1] + wp_j tol_P[t-1])       (what the input state's error does to a score; over
+                                                                         the regimes of positive prior probability)
+        tol_lw[t] = tol_g[t] + max log-weight bound       (`first_stage_log_weights`: a log-sum-exp moves by at most its terms)
+        tol_c[t]  = tol_g[t] + max cdf bound              (`cdf`: sum_l |d cdf_j / d g_l| = 2 cdf_j (1 - cdf_j) <= 1/2)
+        tol_Z    += tol_lw[t] + (K + 4) u (1 + max |lse| + log K)."""
+    T, K = len(observations), int(num_particles)
+    M = model["A"].shape[0]
+    with np.errstate(divide="ignore"):
+        log_pi0, log_Pi = np.log(model["pi0"]), np.log(model["Pi"])
+    out = {name: [] for name in ("regimes", "means", "covariances", "log_likelihoods", "first_stage_log_weights",
+                                 "ancestral_indices")}
+    margins = {"resampling": [], "regimes": []}
+    tolerances = {name: [] for name in ("means", "covariances", "log_likelihoods", "first_stage_log_weights", "cdf")}
+    state, flags = None, 0
+    log_z, tol_z = 0.0, 0.0
+    for t in range(T):
+        y = observations[t]
+        B = np.asarray(y).shape[0]
+        prior = log_pi0 if t == 0 else log_Pi
+        log_w, cdf, bits = switching_lookahead(model, prior, state, y, K)
+        bound_w, bound_c = switching_lookahead_bound(model, prior, state, y, K)
+        flags |= bits
+        carried = 0.0
+        if t > 0:
+            before_m, before_p = tolerances["means"][-1], tolerances["covariances"][-1]
+            rows = log_Pi[np.clip(state[0], 0, M - 1)]
+            for j in range(M):      # (a particle for which regime j is excluded stands in with its likeliest successor)
+                considered = np.where(np.isneginf(rows[:, :, j]), np.argmax(rows, axis=-1), j)
+                _, _, _, wm, wp = _sensitivities(model, state, None, considered, y)
+                carried = max(carried, 1.01 * (wm * before_m + wp * before_p))
+        tolerances["first_stage_log_weights"].append(carried + float(bound_w.max()))
+        tolerances["cdf"].append(carried + float(bound_c.max()))
+        if t == 0:
+            idx = None
+            with np.errstate(invalid="ignore"):
+                top = log_w.max(axis=1)
+                lse = top + np.log(np.exp(log_w - top[:, None]).sum(axis=1))
+        else:
+            idx, lse, bits, margin = _adapted.ancestor_index(log_w, resampling_uniforms[t - 1])
+            flags |= bits
+            out["ancestral_indices"].append(idx), margins["resampling"].append(margin)
+        log_z = log_z + lse - np.log(K)
+        tol_z += tolerances["first_stage_log_weights"][-1] + (K + 4) * UNIT * (1.0 + float(np.abs(lse).max()) + np.log(K))
+        with np.errstate(all="ignore"):
+            ((regime, mean, cov, ell, bits), _), rows = _draw(model, state, idx, regime_uniforms[t], cdf, y, np.float64, False)
+        bound_m, bound_p, bound_l = switching_kalman_draw_bound(model, state, idx, regime_uniforms[t], cdf, y)
+        flags |= bits
+        margins["regimes"].append(_regime_margin(rows, regime_uniforms[t]))
+        D = mean.shape[-1]
+        fresh_m = float(np.sqrt((bound_m ** 2).sum(axis=-1)).max())
+        fresh_p = float(np.sqrt((unpack(bound_p, D) ** 2).sum(axis=(-2, -1))).max())
+        fresh_l = float(bound_l.max())
+        if t == 0:
+            tol_m, tol_p, tol_l = fresh_m, fresh_p, fresh_l
+        else:
+            pp, mm, mp, wm, wp = _sensitivities(model, state, idx, regime, y)
+            tol_p = 1.01 * pp * before_p + fresh_p
+            tol_m = 1.01 * (mm * before_m + mp * before_p) + fresh_m
+            tol_l = 1.01 * (wm * before_m + wp * before_p) + fresh_l
+        state = (regime, mean, cov)
+        tolerances["means"].append(tol_m), tolerances["covariances"].append(tol_p), tolerances["log_likelihoods"].append(tol_l)
+        out["regimes"].append(regime), out["means"].append(mean), out["covariances"].append(cov)
+        out["log_likelihoods"].append(ell), out["first_stage_log_weights"].append(log_w)
+    tolerances["log_marginal_likelihood"] = float(tol_z)
+    out.update(log_marginal_likelihood=log_z, flags=flags, tolerances=tolerances, margins=margins)
+    return out
+
+
+def sticky_example(T=12, seed=0):
+    """(model, one series: T x [Dy]) where a look-ahead pays: three sticky regimes (0.96 on the diagonal) with
+    well-separated emission offsets (-4, 0, 4 against r = 0.5) over a slowly moving scalar state — a regime change shows in
+    the observation at once, and a bootstrap on the regimes finds it only with the particles that guessed it.  The series
+    is simulated from the model (a fixed generator)."""
+    M, D, Dy = 3, 1, 1
+    Pi = np.full((M, M), 0.02) + 0.94 * np.eye(M)
+    model = operands(np.full(M, 1.0 / M), Pi, np.zeros(D), np.ones(D), np.full((1, D, D), 0.9), np.zeros((1, D)),
+                     np.full((1, D), 0.3), np.ones((1, Dy, D)), np.array([[-4.0], [0.0], [4.0]]), np.full((1, Dy), 0.5))
+    rng = np.random.default_rng([seed, 1999])
+    series, s, z = [], None, None
+    for t in range(T):
+        s = rng.choice(M, p=model["pi0"] if t == 0 else model["Pi"][s])
+        z = model["m0"] + model["s0"] * rng.standard_normal(D) if t == 0 else \
+            model["A"][s] @ z + model["b"][s] + model["q"][s] * rng.standard_normal(D)
+        series.append(model["C"][s] @ z + model["d"][s] + model["r"][s] * rng.standard_normal(Dy))
+    return model, series

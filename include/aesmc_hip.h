@@ -77,7 +77,9 @@ extern "C" {
  *                aesmc_adapted_backward_workspace_bytes (K29, K30: their adjoints, for training through the adapted filter);
  *                aesmc_switching_kalman_step with aesmc_switching_max_latent_dim, aesmc_switching_max_observation_dim,
  *                aesmc_switching_max_regimes (K31: one step of the Rao-Blackwellised filter of a switching
- *                linear-Gaussian model).
+ *                linear-Gaussian model);
+ *                aesmc_switching_lookahead, aesmc_switching_kalman_draw (K32, K33: the exact first-stage weights and regime
+ *                posteriors of that model, and K31's step with the regime drawn from them — its fully adapted filter).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -675,6 +677,37 @@ int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_model *model,
                                 const double *mean_in, const double *cov_in, const int64_t *idx, const double *uniforms,
                                 const void *y, int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
                                 int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K32 — the look-ahead of the fully adapted filter of the same model (the mixture Kalman filter with the regimes drawn from
+ * their exact posterior: Chen & Liu 2000; Doucet, Gordon & Krishnamurthy 2001; Pitt & Shephard 1999): for the STORED particle
+ * (b,k) — no ancestors — one Kalman prediction per regime j = 0..M-1, each K31's arithmetic up to v under s = j:
+ *   l_j   = (-1/2 sum_i v_i^2 - sum_c log Lam_cc) - Dy * (1/2 log 2 pi)
+ *   g_j   = log_prior[regime_in[b,k], j] + l_j  (one rounded addition; step 0: log_prior[j]); -inf where the log-prior is
+ *           -inf whatever l_j and its pivots are; NaN where the log-prior is finite and a pivot is not positive
+ *   log_weight[b,k] = top + log(sum_j exp(g_j - top)), top = max_j g_j, the sum from 0 in ascending j
+ *   cdf[b,k,j]      = sum_{i <= j} exp(g_i - log_weight[b,k]) from 0 in ascending i; exactly 1 for every j from the last i
+ *                     with exp(g_i - log_weight) > 0 onwards
+ *   log_prior   float64 [M,M] with a state (rows: from-regime), [M] without one: the logarithms of Pi or pi0, -inf allowed
+ *   regime_in, mean_in, cov_in, y, flags as K31's (all three state pointers NULL: the step-0 form, every regime predicted
+ *               by m0 and diag(s0^2)); the model's cdf0 and cdf are not read
+ *   log_weight  float64 [B,K], cdf float64 [B,K,M]
+ * A stored regime outside [0, M) writes NaN to the particle's log-weight and CDF row and raises
+ * AESMC_FLAG_INDEX_OUT_OF_RANGE.  A NaN score, or no score above -inf, writes NaN to both (the resampling launch that
+ * follows raises AESMC_FLAG_NAN_LOG_WEIGHT by its own rules).  Statuses as K31's; an output that is another operand is an
+ * invalid argument. */
+int aesmc_switching_lookahead(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
+                              const int32_t *regime_in, const double *mean_in, const double *cov_in, const void *y,
+                              double *log_weight, double *cdf, int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K33 — K31 with the regime drawn from a cumulative row per particle: with j the ancestor as in K31 (step 0: k),
+ *   s = #{ i < M-1 : particle_cdf[b,j,i] <= uniforms[b,k] }
+ * and everything after it K31's, in K31's order; log_weight receives l_s, which the adapted filter does not use (it equals
+ * K32's g_s - log_prior[., s] to rounding).  particle_cdf: float64 [B,K,M] (K32's cdf), must not be an output; the model's
+ * cdf0 and cdf are not read.  Everything else, the conventions and the statuses as K31's. */
+int aesmc_switching_kalman_draw(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                const double *mean_in, const double *cov_in, const int64_t *idx, const double *uniforms,
+                                const double *particle_cdf, const void *y, int32_t *regime_out, double *mean_out,
+                                double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K, void *stream);
 
 /* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
