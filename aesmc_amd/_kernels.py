@@ -2537,6 +2537,111 @@ class HipKernels:
                       log_likelihood, block), name="switching_kalman_draw")
         return out_regime, out_mean, out_cov, log_likelihood
 
+    # ---- K34, K35 ------------------------------------------------------------------------------
+    def switching_backward_covers(self, observation, num_regimes, latent_dim, observation_dim, num_particles,
+                                  num_trajectories):
+        """Whether `switching_information_step` and `switching_backward_scores` take a backward step like this: what
+        `switching_covers` asks of the observation and the model for B N trajectories and for B K particles, and B N K
+        scores within 32-bit element arithmetic."""
+        if not (self.switching_covers(observation, num_regimes, latent_dim, observation_dim, num_particles) and
+                self.switching_covers(observation, num_regimes, latent_dim, observation_dim, num_trajectories)):
+            return False
+        return observation.size(0) * num_trajectories * max(num_particles, 1) <= 0x7fffffff
+
+    def switching_information_step(self, model, regime_next, info, observation):
+        """The information step of Rao-Blackwellised backward simulation (aesmc_switching_information_step, K34).  model as
+        `switching_kalman_step`'s; regime_next int32 [B,N]: the trajectories' regimes at time t+1; info: None (the zeros of
+        the last step) or (omega float64 [B,N,D(D+1)/2], lam float64 [B,N,D], c float64 [B,N]) of time t+1; observation
+        float32 / float64 [B,Dy]: that of time t+1.  Returns (omega, lam, c, factor [B,N,D(D+1)/2]) of time t, new tensors;
+        factor is the packed lower factor of omega, a pivot at or below 2^-40 of the largest diagonal entry giving a zero
+        column.  A regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        _require_hip(regime_next, "regime_next")
+        device = observation.device
+        if regime_next.dim() != 2 or regime_next.dtype != torch.int32 or regime_next.device != device:
+            raise ValueError("aesmc_amd: regime_next must be [batch_size, num_trajectories] int32 on {}".format(device))
+        B, N = regime_next.shape
+        block, M, D, Dy = self._switching_block(model, device)
+        TD = D * (D + 1) // 2
+        if tuple(observation.shape) != (B, Dy):
+            raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
+        if not self.switching_covers(observation, M, D, Dy, N):
+            raise ValueError("aesmc_amd: switching_information_step does not take these operands (see "
+                             "switching_backward_covers)")
+        omega = lam = c = None
+        if info is not None:
+            omega, lam, c = info
+            for tensor, shape, what in ((omega, (B, N, TD), "omega"), (lam, (B, N, D), "lam"), (c, (B, N), "c")):
+                _require_hip(tensor, what)
+                if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                    raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
+            omega, lam, c = omega.contiguous(), lam.contiguous(), c.contiguous()
+        regime_next, observation = regime_next.contiguous(), observation.contiguous()
+        out_omega = torch.empty((B, N, TD), dtype=torch.float64, device=device)
+        out_lam = torch.empty((B, N, D), dtype=torch.float64, device=device)
+        out_c = torch.empty((B, N), dtype=torch.float64, device=device)
+        factor = torch.empty((B, N, TD), dtype=torch.float64, device=device)
+        if out_c.numel() == 0:
+            return out_omega, out_lam, out_c, factor
+        per_trajectory = 4 + (2 if info is not None else 1) * 8 * (TD + D + 1) + 8 * TD
+        self._launch(device, self._lib.aesmc_switching_information_step,
+                     (tag, ctypes.byref(block), _ptr(regime_next), _ptr(omega), _ptr(lam), _ptr(c), _ptr(observation),
+                      _ptr(out_omega), _ptr(out_lam), _ptr(out_c), _ptr(factor), _ptr(self.flags(device)), B, N,
+                      self._stream(observation)),
+                     lambda: B * N * per_trajectory + B * Dy * observation.element_size() +
+                     8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
+                     (model, regime_next, omega, lam, c, observation, out_omega, out_lam, out_c, factor, block),
+                     name="switching_information_step")
+        return out_omega, out_lam, out_c, factor
+
+    def switching_backward_scores(self, log_Pi, regime_next, factor, lam, state, log_w=None):
+        """The pair scores of Rao-Blackwellised backward simulation (aesmc_switching_backward_scores, K35): log_Pi float64
+        [M,M] (-inf where a probability is 0); regime_next int32 [B,N]; factor [B,N,D(D+1)/2] and lam [B,N,D]:
+        `switching_information_step`'s; state: the stored (regime int32 [B,K], mean [B,K,D], cov [B,K,D(D+1)/2]) of step t;
+        log_w float64 [B,K] or None (equal weights).  Returns scores float64 [B,N,K], a new tensor: -inf where the
+        transition is impossible, NaN and FLAG_INDEX_OUT_OF_RANGE for a regime outside [0, M) on either side."""
+        _require_hip(log_Pi, "log_Pi")
+        _require_hip(regime_next, "regime_next")
+        device = log_Pi.device
+        if log_Pi.dim() != 2 or log_Pi.size(0) != log_Pi.size(1) or log_Pi.dtype != torch.float64:
+            raise ValueError("aesmc_amd: log_Pi must be [M, M] float64, got {} {}".format(tuple(log_Pi.shape), log_Pi.dtype))
+        M = log_Pi.size(0)
+        if regime_next.dim() != 2 or regime_next.dtype != torch.int32 or regime_next.device != device:
+            raise ValueError("aesmc_amd: regime_next must be [batch_size, num_trajectories] int32 on {}".format(device))
+        B, N = regime_next.shape
+        D = lam.size(-1) if torch.is_tensor(lam) and lam.dim() == 3 else 0
+        TD = D * (D + 1) // 2
+        for tensor, shape, what in ((factor, (B, N, TD), "factor"), (lam, (B, N, D), "lam")):
+            _require_hip(tensor, what)
+            if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
+        K = state[0].size(1) if torch.is_tensor(state[0]) and state[0].dim() == 2 else -1
+        regime, mean, cov = self._switching_state(state, B, K, D, device)
+        if log_w is not None:
+            _require_hip(log_w, "log_weight")
+            if tuple(log_w.shape) != (B, K) or log_w.dtype != torch.float64 or log_w.device != device:
+                raise ValueError("aesmc_amd: log_weight must be {} float64 on {}".format((B, K), device))
+            log_w = log_w.contiguous()
+        max_d, _, max_m = self.switching_limits()
+        limit = 0x7fffffff
+        if not (1 <= D <= max_d and 1 <= M <= max_m and B * N * max(K, 1) <= limit and
+                B * max(K, N) <= limit // (max_d * (max_d + 1) // 2)):
+            raise ValueError("aesmc_amd: switching_backward_scores does not take these operands (see "
+                             "switching_backward_covers)")
+        log_Pi, regime_next, factor, lam = log_Pi.contiguous(), regime_next.contiguous(), factor.contiguous(), lam.contiguous()
+        scores = torch.empty((B, N, K), dtype=torch.float64, device=device)
+        if scores.numel() == 0:
+            return scores
+        self._launch(device, self._lib.aesmc_switching_backward_scores,
+                     (_ptr(log_Pi), _ptr(regime_next), _ptr(factor), _ptr(lam), _ptr(regime), _ptr(mean), _ptr(cov),
+                      _ptr(log_w), _ptr(scores), _ptr(self.flags(device)), B, K, N, M, D, self._stream(log_Pi)),
+                     lambda: 8 * B * N * K + B * N * (4 + 8 * (TD + D)) * ((K + 255) // 256) +
+                     B * K * (4 + 8 * (D + TD) + (8 if log_w is not None else 0)) * ((N + 15) // 16),
+                     (log_Pi, regime_next, factor, lam, regime, mean, cov, log_w, scores),
+                     name="switching_backward_scores")
+        return scores
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 

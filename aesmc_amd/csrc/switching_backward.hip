@@ -1,0 +1,250 @@
+// The pair scores of Rao-Blackwellised backward simulation for a switching linear-Gaussian state-space model —
+// aesmc_switching_backward_scores (K35) of include/aesmc_hip.h; switching_information.hip (K34) writes what it reads.
+//
+// Trajectory n of batch row b carries lam and the lower factor F of Om (F F^T = Om, Phi = F^T); stored particle k of step t
+// carries (s, m, P, log w).  The score is the logarithm of w Pi[s, s'] times the closed-form integral of
+// exp(lam^T z - 1/2 z^T Om z) against N(m, P): with h = lam - Om m, v = Phi P h and Lam = I + Phi P Phi^T,
+//   log w + log Pi[s, s'] + lam^T m - 1/2 m^T Om m + 1/2 (h^T P h - v^T Lam^-1 v) - 1/2 log|Lam|.
+// Lam has pivots of at least 1 (no pivot test), P is never factored (P = 0 is fine), Om is never formed.
+//
+//   workgroup = (batch row, a tile of 16 trajectories, 256 consecutive particles); the tile's F, lam and, for every regime s,
+//               log Pi[s, s'_n] are staged into LDS once, zero-padded to the instantiation's extent DP (2, 4, 8), and read as
+//               broadcasts: every lane of a wavefront reads the same address;
+//   lane      = one particle: it loads its (s, m, P, log w) ONCE and walks the tile's trajectories — 16 scores for 8 + 4 +
+//               8 D + 4 D (D + 1) bytes read; the scores are written [B,N,K], consecutive lanes to consecutive addresses;
+//   registers   W = Phi P is formed one row at a time: row i gives row i of Lam and v_i, so m, h, Lam, one row of W and P are
+//               all that is live.  At DP = 8 that is still 36 + 36 + 8 + 8 + 8 + 8 float64 = 208 registers before addresses
+//               and temporaries, so the 8-wide instantiation keeps P in LDS in K31's [element][lane] layout (SkCov: 72 KB
+//               per workgroup, two workgroups per compute unit).  About D^3 float64 multiply-adds per pair;
+//   chains      every value is ONE chain of float64 __builtin_fma in the header's order; the triangular sums skip the
+//               structural zeros of F, a padded term multiplies a zero by a zero.
+//
+// Compiler's resource report (-Rpass-analysis=kernel-resource-usage, gfx950, 256 lanes per workgroup):
+//   <DP>  VGPRs  AGPRs  scratch B/lane  waves/SIMD
+//   <2>      58      0        0             8
+//   <4>     126      0        0             4
+//   <8>     174      0        0             2       P in LDS
+// Measured (profiles/switching_smoother.txt, B = 64, K = 1024, N = 64: 4.2 million pairs): 98 us at D = 4, 342 us at D = 8.
+#include "switching_kalman.hpp"
+
+namespace aesmc {
+
+constexpr int kSbTile = 16;      // trajectories per workgroup
+
+struct BackwardScoreArgs {
+  const double *log_Pi;             // [M,M]
+  const int32_t *regime_next;       // [B,N]
+  const double *factor, *lambda;    // [B,N,D(D+1)/2], [B,N,D]
+  const int32_t *regime;            // [B,K]
+  const double *mean, *cov, *log_w; // [B,K,D], [B,K,D(D+1)/2], [B,K] or NULL
+  double *scores;                   // [B,N,K]
+  int32_t *flags;
+  uint32_t K, N, k_tiles, n_tiles;
+  int M, D;
+};
+
+// LDS: F [kSbTile][TP], lam [kSbTile][DP], log Pi[., s'_n] [kSbTile][M]; then, for DP == 8, [TP][256] covariances
+template <int DP>
+__global__ __launch_bounds__(kSkBlock) void switching_backward_kernel(const BackwardScoreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sb_smem[];
+  constexpr int TP = DP * (DP + 1) / 2;
+  const int M = a.M, D = a.D;
+  const int TD = D * (D + 1) / 2;
+  const uint32_t kt = blockIdx.x % a.k_tiles;
+  const uint32_t rest = blockIdx.x / a.k_tiles;
+  const uint32_t nt = rest % a.n_tiles;
+  const int64_t b = rest / a.n_tiles;
+  const uint32_t n0 = nt * kSbTile;
+  const int count = (int)(a.N - n0 < (uint32_t)kSbTile ? a.N - n0 : (uint32_t)kSbTile);
+  double *Ft = sb_smem, *lt = Ft + kSbTile * TP, *pt = lt + kSbTile * DP;
+  for (int e = threadIdx.x; e < kSbTile * TP; e += kSkBlock) {
+    const int nn = e / TP, el = e - nn * TP;
+    Ft[e] = (nn < count && el < TD) ? a.factor[(b * a.N + n0 + nn) * TD + el] : 0.0;
+  }
+  for (int e = threadIdx.x; e < kSbTile * DP; e += kSkBlock) {
+    const int nn = e / DP, el = e - nn * DP;
+    lt[e] = (nn < count && el < D) ? a.lambda[(b * a.N + n0 + nn) * D + el] : 0.0;
+  }
+  for (int e = threadIdx.x; e < kSbTile * M; e += kSkBlock) {
+    const int nn = e / M, s = e - nn * M;
+    double v = 0.0;
+    if (nn < count) {
+      const int next = a.regime_next[b * a.N + n0 + nn];
+      if (next < 0 || next >= M) {      // (a NaN column: every score of the trajectory is NaN)
+        if (s == 0 && kt == 0) raise_flag(a.flags, AESMC_FLAG_INDEX_OUT_OF_RANGE);
+        v = Num<double>::nan();
+      } else {
+        v = a.log_Pi[s * M + next];
+      }
+    }
+    pt[e] = v;
+  }
+  __syncthreads();
+  const uint32_t k = kt * kSkBlock + threadIdx.x;
+  if (k >= a.K) return;
+  const int64_t particle = b * a.K + k;
+  double *out = a.scores + (b * a.N + n0) * a.K + k;
+
+  int s = a.regime[particle];
+  if (s < 0 || s >= M) {
+    raise_flag(a.flags, AESMC_FLAG_INDEX_OUT_OF_RANGE);
+    for (int nn = 0; nn < count; ++nn) out[(int64_t)nn * a.K] = Num<double>::nan();
+    return;
+  }
+  double m[DP];
+  SkCov<TP, sk_cov_in_lds(DP)> P;
+  P.lds = pt + kSbTile * M + threadIdx.x;
+  {
+    const double *mrow = a.mean + particle * D, *prow = a.cov + particle * TD;
+#pragma unroll
+    for (int i = 0; i < DP; ++i) m[i] = i < D ? mrow[i] : 0.0;
+#pragma unroll
+    for (int e = 0; e < TP; ++e) P.set(e, e < TD ? prow[e] : 0.0);
+  }
+  const double lw = a.log_w != nullptr ? a.log_w[particle] : 0.0;
+  const bool weighted = a.log_w != nullptr;
+
+  for (int nn = 0; nn < count; ++nn) {
+    const double *F = Ft + nn * TP, *lam = lt + nn * DP;      // F_ik, i >= k, at sk_tri(i, k)
+    // ---- t = F^T m, h = lam - F t, the two quadratic terms in m ---------------------------------------------------------------
+    double t[DP], h[DP], mq = 0.0, lm = 0.0;
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      double acc = 0.0;
+#pragma unroll
+      for (int l = i; l < DP; ++l) acc = __builtin_fma(F[sk_tri(l, i)], m[l], acc);
+      t[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < DP; ++i) mq = __builtin_fma(t[i], t[i], mq);
+#pragma unroll
+    for (int l = 0; l < DP; ++l) {
+      double acc = lam[l];
+#pragma unroll
+      for (int i = 0; i <= l; ++i) acc = __builtin_fma(-F[sk_tri(l, i)], t[i], acc);
+      h[l] = acc;
+      lm = __builtin_fma(lam[l], m[l], lm);
+    }
+    // ---- h^T P h -----------------------------------------------------------------------------------------------------------------
+    double hph = 0.0;
+#pragma unroll
+    for (int c = 0; c < DP; ++c) {
+      double acc = 0.0;
+#pragma unroll
+      for (int l = 0; l < DP; ++l) acc = __builtin_fma(P.get(sk_tri(c, l)), h[l], acc);
+      hph = __builtin_fma(h[c], acc, hph);
+    }
+    // ---- W = Phi P row by row: row i gives v_i and row i of Lam = I + W Phi^T ------------------------------------------------------
+    double v[DP], Lam[TP];
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      SK_REREAD_LDS();
+      double W[DP];
+#pragma unroll
+      for (int l = 0; l < DP; ++l) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = i; c < DP; ++c) acc = __builtin_fma(F[sk_tri(c, i)], P.get(sk_tri(c, l)), acc);
+        W[l] = acc;
+      }
+      double acc = 0.0;
+#pragma unroll
+      for (int l = 0; l < DP; ++l) acc = __builtin_fma(W[l], h[l], acc);
+      v[i] = acc;
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double w = i == j ? 1.0 : 0.0;
+#pragma unroll
+        for (int l = j; l < DP; ++l) w = __builtin_fma(W[l], F[sk_tri(l, j)], w);
+        Lam[sk_tri(i, j)] = w;
+      }
+    }
+    // ---- G = chol(Lam) in place, x = G^-1 v in step ---------------------------------------------------------------------------------
+    double inv[DP], log_det = 0.0;
+#pragma unroll
+    for (int j = 0; j < DP; ++j) {
+      double pivot = Lam[sk_tri(j, j)];
+#pragma unroll
+      for (int c = 0; c < j; ++c) pivot = __builtin_fma(-Lam[sk_tri(j, c)], Lam[sk_tri(j, c)], pivot);
+      const double gjj = __builtin_sqrt(pivot);
+      Lam[sk_tri(j, j)] = gjj;
+      inv[j] = 1.0 / gjj;
+      log_det += ::log(gjj);
+#pragma unroll
+      for (int i = j + 1; i < DP; ++i) {
+        double acc = Lam[sk_tri(i, j)];
+#pragma unroll
+        for (int c = 0; c < j; ++c) acc = __builtin_fma(-Lam[sk_tri(i, c)], Lam[sk_tri(j, c)], acc);
+        Lam[sk_tri(i, j)] = acc * inv[j];
+      }
+    }
+    double xq = 0.0;
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      double acc = v[i];
+#pragma unroll
+      for (int c = 0; c < i; ++c) acc = __builtin_fma(-Lam[sk_tri(i, c)], v[c], acc);
+      v[i] = acc * inv[i];
+      xq = __builtin_fma(v[i], v[i], xq);
+    }
+    // ---- the score ---------------------------------------------------------------------------------------------------------------
+    const double lp = pt[nn * M + s];
+    double score = weighted ? lw + lp : lp;
+    score = score + lm;
+    score = __builtin_fma(-0.5, mq, score);
+    score = __builtin_fma(0.5, hph - xq, score);
+    score = score - log_det;
+    out[(int64_t)nn * a.K] = lp == Num<double>::neg_inf() ? lp : score;
+  }
+}
+
+template <int DP>
+static bool sb_launch(dim3 grid, size_t lds, hipStream_t s, const BackwardScoreArgs &a) {
+  // the 8-wide instantiation (72 KB of covariances beside the tile) needs the limit raised, as K31's
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_backward_kernel<DP>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    return false;
+  hipLaunchKernelGGL((switching_backward_kernel<DP>), grid, dim3(kSkBlock), lds, s, a);
+  return true;
+}
+
+}  // namespace aesmc
+
+extern "C" int aesmc_switching_backward_scores(const double *log_Pi, const int32_t *regime_next, const double *factor,
+                                               const double *lambda, const int32_t *regime, const double *mean,
+                                               const double *cov, const double *log_w, double *scores, int32_t *flags,
+                                               int64_t B, int64_t K, int64_t N, int64_t M, int64_t D, void *stream) {
+  using namespace aesmc;
+  if (log_Pi == nullptr || regime_next == nullptr || factor == nullptr || lambda == nullptr || regime == nullptr ||
+      mean == nullptr || cov == nullptr || scores == nullptr || B < 0 || K < 0 || N < 0 || M < 1 || D < 1)
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_aligned(log_Pi, 8) || !sk_aligned(regime_next, 4) || !sk_aligned(factor, 8) || !sk_aligned(lambda, 8) ||
+      !sk_aligned(regime, 4) || !sk_aligned(mean, 8) || !sk_aligned(cov, 8) || !sk_aligned(log_w, 8) ||
+      !sk_aligned(scores, 8) || !sk_aligned(flags, 4))
+    return AESMC_ERR_INVALID_ARGUMENT;
+  const void *inputs[] = {log_Pi, regime_next, factor, lambda, regime, mean, cov, log_w};
+  for (const void *in : inputs)
+    if (in == scores) return AESMC_ERR_INVALID_ARGUMENT;
+  if (B == 0 || N == 0 || K == 0) return AESMC_OK;
+  if (D > kSkMaxDim || M > kSkMaxRegimes) return AESMC_ERR_UNSUPPORTED;
+  constexpr int64_t kLimit = 0x7fffffffLL;
+  constexpr int64_t kTri = kSkMaxDim * (kSkMaxDim + 1) / 2;
+  if (B > kLimit || K > kLimit || N > kLimit || B * K > kLimit / kTri || B * N > kLimit / kTri || B * N > kLimit / K)
+    return AESMC_ERR_UNSUPPORTED;
+  BackwardScoreArgs a;
+  a.log_Pi = log_Pi, a.regime_next = regime_next, a.factor = factor, a.lambda = lambda;
+  a.regime = regime, a.mean = mean, a.cov = cov, a.log_w = log_w;
+  a.scores = scores, a.flags = flags;
+  a.K = (uint32_t)K, a.N = (uint32_t)N;
+  a.k_tiles = (uint32_t)((K + kSkBlock - 1) / kSkBlock), a.n_tiles = (uint32_t)((N + kSbTile - 1) / kSbTile);
+  a.M = (int)M, a.D = (int)D;
+  const int dp = sk_pad(D);
+  const int tp = dp * (dp + 1) / 2;
+  const size_t lds = ((size_t)kSbTile * (tp + dp + a.M) + (sk_cov_in_lds(dp) ? (size_t)tp * kSkBlock : 0)) * sizeof(double);
+  const dim3 grid((unsigned)(B * a.n_tiles * a.k_tiles));      // (at most B N K workgroups: within 32 bits by the check above)
+  hipStream_t s = (hipStream_t)stream;
+  const bool launched = dp == 2 ? sb_launch<2>(grid, lds, s, a) : dp == 4 ? sb_launch<4>(grid, lds, s, a)
+                                                                          : sb_launch<8>(grid, lds, s, a);
+  return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+}

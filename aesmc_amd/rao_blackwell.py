@@ -27,6 +27,17 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                Liu 2000; Doucet, Gordon & Krishnamurthy 2001; Pitt & Shephard 1999)
     kalman_log_likelihood      one regime: the exact log p(y)
     unpack_covariance          packed lower triangles -> symmetric matrices
+    switching_backward_simulate   Rao-Blackwellised backward simulation (Fong, Godsill, Doucet & West 2002; Whiteley, Andrieu
+                               & Doucet 2010; Lindsten, Bunch, Saerkkae, Schoen & Godsill 2016) over the stored systems of
+                               either filter: equally weighted regime trajectories from p(s_{0:T-1} | y_{0:T-1}) and the
+                               smoothed regime probabilities p(s_t | y_{0:T-1}) — offline segmentation.  With z integrated
+                               out the regimes are not Markov, so `smoothing.backward_simulate` has no transition to score:
+                               every trajectory carries backwards a quadratic summary (Om, lam, c) of its future
+                               observations (K34, `aesmc_switching_information_step`, one lane per trajectory) and every
+                               stored particle is scored by a closed-form Gaussian integral against it (K35,
+                               `aesmc_switching_backward_scores`, one lane per particle walking a tile of trajectories);
+                               K21 then draws one particle per trajectory
+    switching_smooth           a filter, then that
 
 The reference has no counterpart; this module adds to its interface and changes none of it.
 """
@@ -370,6 +381,155 @@ def adapted_switching_filter(observations, model, num_particles, resampling=None
         inference._discard_pending_flags()
         raise
     return out
+
+
+def _stored_systems(name, filtered, num_timesteps, batch_size, latent_dim, device):
+    """(regimes, means, covariances, log_weights or None, K) of a filter's dict, validated: T stored systems each."""
+    for key in ("regimes", "means", "covariances"):
+        if key not in filtered or len(filtered[key]) != num_timesteps:
+            raise ValueError("{}: filtered must hold {} '{}' (the dict of switching_filter or adapted_switching_filter "
+                             "on these observations)".format(name, num_timesteps, key))
+    log_weights = filtered.get("log_weights")
+    if log_weights is not None and len(log_weights) != num_timesteps:
+        raise ValueError("{}: filtered must hold {} 'log_weights', got {}".format(name, num_timesteps, len(log_weights)))
+    regimes, means, covariances = filtered["regimes"], filtered["means"], filtered["covariances"]
+    num_particles = regimes[0].size(1) if torch.is_tensor(regimes[0]) and regimes[0].dim() == 2 else -1
+    if num_particles < 1:
+        raise ValueError("{}: filtered['regimes'] must be [batch_size, num_particles] tensors of at least one particle"
+                         .format(name))
+    packed = latent_dim * (latent_dim + 1) // 2
+    for time in range(num_timesteps):
+        wanted = [(regimes[time], (batch_size, num_particles), torch.int32, "regimes"),
+                  (means[time], (batch_size, num_particles, latent_dim), torch.float64, "means"),
+                  (covariances[time], (batch_size, num_particles, packed), torch.float64, "covariances")]
+        if log_weights is not None:
+            wanted.append((log_weights[time], (batch_size, num_particles), torch.float64, "log_weights"))
+        for tensor, shape, dtype, key in wanted:
+            if not torch.is_tensor(tensor) or tuple(tensor.shape) != shape or tensor.dtype != dtype or tensor.device != device:
+                raise ValueError("{}: filtered['{}'][{}] must be {} {} on {}".format(name, key, time, shape, dtype, device))
+    return regimes, means, covariances, log_weights, num_particles
+
+
+def switching_backward_simulate(filtered, model, observations, num_trajectories=None, uniforms=None, return_indices=False):
+    """Rao-Blackwellised backward simulation over the stored systems of one run of `switching_filter` or
+    `adapted_switching_filter`: regime trajectories from the joint smoothing distribution p(s_{0:T-1} | y_{0:T-1}).
+
+    filtered: the dict either filter returned for these observations (regimes, means, covariances; with `log_weights` the
+        stored systems are weighted by them — `switching_filter`'s — and without that key equally —
+        `adapted_switching_filter`'s).
+    model, observations: as the filter's.
+    num_trajectories: N per batch row (default: the number of particles).  0 gives empty tensors without a launch.
+    uniforms: `smoothing.backward_simulate`'s convention — None: one torch.rand((batch_size, N), float64) block per
+        timestep on the device, drawn for t = T-1 first and t = 0 last (seed with torch.manual_seed); or a length-T
+        sequence of such blocks, `uniforms[t]` for the draw at time t (replay).  None inside `distributed.shard_scope`
+        raises NotImplementedError for that function's reason.
+    return_indices: also `indices`: which stored particle each trajectory passes through, T int64 [batch_size, N].
+
+    At t = T-1 a trajectory draws a stored particle by its weight (K21).  For t = T-2 .. 0 it takes the quadratic summary
+    of its future observations one step back under its regime at t+1 (K34), every stored particle of step t is scored
+    against it (K35: scores [batch_size, N, K]), and K21 draws one particle per trajectory from those scores (rows
+    [batch_size N, K], one trajectory each); the trajectory's regime at t is that particle's.
+
+    Returns a dict: regimes (T int32 [batch_size, N]: trajectory n of row b is (regimes[0][b,n], .., regimes[T-1][b,n]), an
+    equally weighted draw) and smoothed_regime_probabilities ([T, batch_size, M] float64: the trajectories' frequencies,
+    the estimate of p(s_t = i | y_{0:T-1})); with return_indices, indices.
+
+    ValueError for an invalid model, T == 0, a `filtered` that does not hold T stored systems of the observations' batch
+    size, a negative num_trajectories and uniforms of the wrong length or shape; NotImplementedError naming the covered
+    class for anything past the limits (also batch_size N K beyond 32-bit element arithmetic).  NaN weights or scores (a
+    stored regime outside [0, M) gives them) raise FloatingPointError, a trajectory no stored particle can precede (a row of
+    -inf scores: every transition into its regime has probability zero) RuntimeError — read once, at the end; an exception
+    on the way discards whatever was flagged.  No host synchronisation inside the loop.  Runs under torch.no_grad(): NOT
+    differentiable.  Not sharded, not capturable into a hipGraph."""
+    name = "switching_backward_simulate"
+    num_timesteps = len(observations)
+    if num_timesteps == 0:
+        raise ValueError("{}: observations must hold at least one timestep".format(name))
+    if uniforms is not None and len(uniforms) != num_timesteps:
+        raise ValueError("{}: uniforms must hold one block per timestep ({}), got {}".format(name, num_timesteps,
+                                                                                              len(uniforms)))
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops = model.operands()
+            M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
+            # (the observations first, for one particle: what the stored systems must match; their number is checked
+            # with the number of trajectories below)
+            batch_size, device = _check_observations(name, provider, observations, model, 1)
+            regimes, means, covariances, log_weights, num_particles = _stored_systems(
+                name, filtered, num_timesteps, batch_size, D, device)
+            num_trajectories = num_particles if num_trajectories is None else int(num_trajectories)
+            if num_trajectories < 0:
+                raise ValueError("{}: num_trajectories must not be negative".format(name))
+            if uniforms is None:
+                from . import distributed
+                if distributed.active_shard() is not None:
+                    raise NotImplementedError(
+                        "aesmc_amd: {} inside distributed.shard_scope draws its uniforms on the device, where no global "
+                        "block exists that every rank could cut its rows from. Pass uniforms= (one [batch_size, "
+                        "num_trajectories] float64 block per timestep).".format(name))
+            if not provider.switching_backward_covers(observations[0], M, D, Dy, num_particles, num_trajectories):
+                _refuse("{} trajectories over {} particles in {} batch rows (batch_size * num_trajectories * num_particles "
+                        "beyond 32-bit element arithmetic)".format(num_trajectories, num_particles, batch_size))
+            shape = (batch_size, num_trajectories)
+
+            def block(time):
+                if uniforms is None:
+                    return torch.rand(shape, dtype=torch.float64, device=device)
+                u = uniforms[time]
+                if not torch.is_tensor(u) or tuple(u.shape) != shape or u.dtype != torch.float64 or u.device != device:
+                    raise ValueError("{}: uniforms[{}] must be {} float64 on {}".format(name, time, shape, device))
+                return u
+
+            if num_trajectories == 0:
+                out = {"regimes": [torch.empty(shape, dtype=torch.int32, device=device) for _ in range(num_timesteps)],
+                       "smoothed_regime_probabilities": torch.zeros((num_timesteps, batch_size, M), dtype=torch.float64,
+                                                                    device=device)}
+                if return_indices:
+                    out["indices"] = [torch.empty(shape, dtype=torch.int64, device=device) for _ in range(num_timesteps)]
+                return out
+            log_Pi = torch.log(ops["Pi"])      # (-inf where a probability is 0) once
+            equal = None if log_weights is not None else torch.zeros((batch_size, num_particles), dtype=torch.float64,
+                                                                     device=device)
+            drawn, indices = [None] * num_timesteps, [None] * num_timesteps
+            last = num_timesteps - 1
+            indices[last], _ = provider.backward_sample(equal if log_weights is None else log_weights[last], None, None,
+                                                        None, block(last))
+            # (a failed draw is position K, whose payload is particle K-1's by K21's convention; the flag is read at the end)
+            drawn[last] = torch.gather(regimes[last], 1, indices[last].clamp(max=num_particles - 1))
+            info = None
+            for time in range(last - 1, -1, -1):
+                u = block(time)      # (a replayed block of the wrong shape is refused before the step's launches)
+                omega, lam, c, factor = provider.switching_information_step(ops, drawn[time + 1], info,
+                                                                            observations[time + 1])
+                info = (omega, lam, c)
+                scores = provider.switching_backward_scores(log_Pi, drawn[time + 1], factor, lam,
+                                                            (regimes[time], means[time], covariances[time]),
+                                                            None if log_weights is None else log_weights[time])
+                index, _ = provider.backward_sample(scores.reshape(batch_size * num_trajectories, num_particles), None, None,
+                                                    None, u.reshape(batch_size * num_trajectories, 1))
+                indices[time] = index.reshape(shape)
+                drawn[time] = torch.gather(regimes[time], 1, indices[time].clamp(max=num_particles - 1))
+            probabilities = torch.stack([
+                torch.nn.functional.one_hot(regime.to(torch.int64).clamp(0, M - 1), M).to(torch.float64).mean(dim=1)
+                for regime in drawn])
+            out = {"regimes": drawn, "smoothed_regime_probabilities": probabilities}
+            if return_indices:
+                out["indices"] = indices
+            inference._raise_for_flags(provider.read_flags(device))
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
+
+
+def switching_smooth(observations, model, num_particles, num_trajectories=None, resampling=None, lookahead=False):
+    """Runs `switching_filter` (lookahead: `adapted_switching_filter`) and then `switching_backward_simulate` over what it
+    stored.  Returns (that function's dict, the filter's log_marginal_likelihood [batch_size])."""
+    run = adapted_switching_filter if lookahead else switching_filter
+    filtered = run(observations, model, num_particles, resampling=resampling)
+    out = switching_backward_simulate(filtered, model, observations, num_trajectories=num_trajectories)
+    return out, filtered["log_marginal_likelihood"]
 
 
 class _ZeroFeed:

@@ -739,3 +739,431 @@ def sticky_example(T=12, seed=0):
             model["A"][s] @ z + model["b"][s] + model["q"][s] * rng.standard_normal(D)
         series.append(model["C"][s] @ z + model["d"][s] + model["r"][s] * rng.standard_normal(Dy))
     return model, series
+
+
+# ---- Rao-Blackwellised backward simulation: the information step (K34), the pair scores (K35) and the pass they make -----------
+# Fong, Godsill, Doucet & West 2002; Whiteley, Andrieu & Doucet 2010; Lindsten, Bunch, Saerkkae, Schoen & Godsill 2016.  Once
+# z is integrated out the regimes are not Markov: a trajectory carries backwards, for its future regimes s'_{t+1..T-1},
+#
+#     p(y_{t+1..T-1} | z_t, s'_{t+1..T-1}) = exp(c_t + lam_t^T z_t - 1/2 z_t^T Om_t z_t),     Om_{T-1} = 0, lam_{T-1} = 0, c_{T-1} = 0
+#
+# and every stored particle (s, m, P, log w) of step t is scored by the closed-form integral of that against N(m, P).
+#
+# The information step, per trajectory, with j = s'_{t+1}, y = y_{t+1}, r2_i = r_j[i]^2, q2_i = q_j[i]^2, sq_i = sqrt(q2_i) (every
+# sum in ascending index order from the value named first; symmetric matrices as packed lower triangles, `tri`):
+#
+#     e_i    = y_i - d_j[i];  rho_i = 1 / r2_i;  G_il = C_j[i,l] rho_i
+#     Oh_ab  = Om_ab + sum_i G_ia C_j[i,b];   lh_a = lam_a + sum_i G_ia e_i
+#     ch     = ((c - 1/2 sum_i (e_i rho_i) e_i) - 1/2 sum_i log r2_i) - Dy (1/2 log 2 pi)
+#     Mm_ab  = (a == b) + (sq_a sq_b) Oh_ab;  L = chol(Mm) column by column as K31's (the pivots are at least 1)
+#     X      = L^-1 (diag(sq) Oh),  w = L^-1 (diag(sq) lh)       (forward substitutions, one reciprocal per pivot)
+#     Ot_ab  = Oh_ab - sum_i X_ia X_ib;   g_a = lh_a - sum_i X_ia w_i
+#     ob_a   = sum_l Ot_al b_j[l];  Om'_ab = sum_i A_j[i,a] (sum_c Ot_ic A_j[c,b]);  lam'_a = sum_i A_j[i,a] (g_i - ob_i)
+#     c'     = (((ch - sum_i log L_ii) + 1/2 sum_i w_i^2) + sum_i b_j[i] g_i) - sum_i (1/2 b_j[i]) ob_i
+#     F      = the lower factor of Om' (F F^T = Om', Phi = F^T), column by column; with tau = 2^-40 max_i Om'_ii:
+#              p_k = Om'_kk - sum_{c<k} F_kc^2;  p_k <= tau: column k of F is zero;  otherwise F_kk = sqrt(p_k),
+#              F_ik = (Om'_ik - sum_{c<k} F_ic F_kc) / F_kk       (Om' is only positive SEMI-definite: rank <= Dy at t = T-2)
+#
+# The pair score of trajectory n and particle k, reading only F and lam' (Om' m = F (F^T m)):
+#
+#     t_i = sum_{l>=i} F_li m_l;  mq = sum_i t_i^2;  h_l = lam'_l - sum_{i<=l} F_li t_i;  lm = sum_l lam'_l m_l
+#     hph = sum_c h_c (sum_l P_cl h_l)
+#     W_il = sum_{c>=i} F_ci P_cl;  v_i = sum_l W_il h_l;  Lam_ij = (i == j) + sum_{l>=j} W_il F_lj   (j <= i; pivots at least 1)
+#     G = chol(Lam);  x = G^-1 v;  xq = sum_i x_i^2;  ld = sum_i log G_ii
+#     score = ((((log w + log Pi[s, s']) + lm) - 1/2 mq) + 1/2 (hph - xq)) - ld;     -inf where log Pi[s, s'] is -inf
+def _information(model, regime_next, info, y, dtype, track):
+    regime_next = np.asarray(regime_next)
+    B, N = regime_next.shape
+    M, D = model["A"].shape[0], model["A"].shape[-1]
+    Dy = model["C"].shape[-2]
+    TD = D * (D + 1) // 2
+    zero = np.zeros((B, N), dtype=dtype)
+    given = lambda array: (np.asarray(array).astype(dtype), zero if track else None)
+    one = given(zero + 1.0)
+    bad = (regime_next < 0) | (regime_next >= M)
+    flags = FLAG_INDEX_OUT_OF_RANGE if bad.any() else 0
+    j = np.where(bad, 0, regime_next)
+    A, bb, q, C, d, r = (model[name][j] for name in ("A", "b", "q", "C", "d", "r"))      # [B,N,...]
+    y = np.asarray(y).astype(np.float64)
+    if info is None:
+        Om, lam, c = [given(zero)] * TD, [given(zero)] * D, given(zero)
+    else:
+        omega_in, lambda_in, c_in = (np.asarray(part) for part in info)
+        Om = [given(omega_in[:, :, e]) for e in range(TD)]
+        lam = [given(lambda_in[:, :, i]) for i in range(D)]
+        c = given(c_in)
+    Cm = [[given(C[:, :, i, l]) for l in range(D)] for i in range(Dy)]
+    Am = [[given(A[:, :, i, l]) for l in range(D)] for i in range(D)]
+    bv = [given(bb[:, :, i]) for i in range(D)]
+    # ---- the observation
+    e = [given(y[:, None, i] - d[:, :, i]) for i in range(Dy)]
+    r2 = [given(r[:, :, i] * r[:, :, i]) for i in range(Dy)]
+    rho = [_reciprocal(x) for x in r2]
+    G = [[_times(Cm[i][l], rho[i]) for l in range(D)] for i in range(Dy)]
+    Oh = [_chain(Om[tri(a, b)], [(G[i][a], Cm[i][b]) for i in range(Dy)]) for a in range(D) for b in range(a + 1)]
+    lh = [_chain(lam[a], [(G[i][a], e[i]) for i in range(Dy)]) for a in range(D)]
+    quad = _chain(given(zero), [(_times(e[i], rho[i]), e[i]) for i in range(Dy)])
+    logr = _chain(given(zero), [(_log(r2[i]), one) for i in range(Dy)])
+    ch = _chain(_chain(_chain(c, [(given(zero - 0.5), quad)]), [(given(zero - 0.5), logr)]),
+                [(given(zero + Dy), given(zero + HALF_LOG_2PI))], negate=True)
+    # ---- the transition's noise integrated out
+    # (the root of an exact argument, which may be zero: two units in its last place, as `_sqrt`'s own rounding term)
+    sq = [(value, 2 * UNIT * value if track else None)
+          for value in (np.sqrt((q[:, :, i] * q[:, :, i]).astype(dtype)) for i in range(D))]
+    Mm = {}
+    for a in range(D):
+        for b in range(a + 1):
+            Mm[tri(a, b)] = _chain(given(zero + (1.0 if a == b else 0.0)), [(_times(sq[a], sq[b]), Oh[tri(a, b)])])
+    inv, log_det = [], given(zero)
+    for k in range(D):
+        pivot = _chain(Mm[tri(k, k)], [(Mm[tri(k, c)], Mm[tri(k, c)]) for c in range(k)], negate=True)
+        Mm[tri(k, k)] = _sqrt(pivot)
+        inv.append(_reciprocal(Mm[tri(k, k)]))
+        log_det = _chain(log_det, [(_log(Mm[tri(k, k)]), one)])
+        for i in range(k + 1, D):
+            Mm[tri(i, k)] = _times(_chain(Mm[tri(i, k)], [(Mm[tri(i, c)], Mm[tri(k, c)]) for c in range(k)], negate=True),
+                                   inv[k])
+    X, w = [], []
+    for i in range(D):
+        X.append([_times(_chain(_times(sq[i], Oh[tri(i, l)]), [(Mm[tri(i, c)], X[c][l]) for c in range(i)], negate=True),
+                         inv[i]) for l in range(D)])
+        w.append(_times(_chain(_times(sq[i], lh[i]), [(Mm[tri(i, c)], w[c]) for c in range(i)], negate=True), inv[i]))
+    Ot = [_chain(Oh[tri(a, b)], [(X[i][a], X[i][b]) for i in range(D)], negate=True) for a in range(D) for b in range(a + 1)]
+    g = [_chain(lh[a], [(X[i][a], w[i]) for i in range(D)], negate=True) for a in range(D)]
+    ww = _chain(given(zero), [(w[i], w[i]) for i in range(D)])
+    # ---- back through the transition
+    ob = [_chain(given(zero), [(Ot[tri(a, l)], bv[l]) for l in range(D)]) for a in range(D)]
+    gb = [_chain(g[a], [(ob[a], one)], negate=True) for a in range(D)]
+    Wt = [[_chain(given(zero), [(Ot[tri(i, c)], Am[c][b]) for c in range(D)]) for b in range(D)] for i in range(D)]
+    Om_out = [_chain(given(zero), [(Am[i][a], Wt[i][b]) for i in range(D)]) for a in range(D) for b in range(a + 1)]
+    lam_out = [_chain(given(zero), [(Am[i][a], gb[i]) for i in range(D)]) for a in range(D)]
+    c_out = _chain(_chain(_chain(_chain(ch, [(log_det, one)], negate=True), [(given(zero + 0.5), ww)]),
+                          [(bv[i], g[i]) for i in range(D)]),
+                   [(given(0.5 * bb[:, :, i]), ob[i]) for i in range(D)], negate=True)
+    # ---- the factor of a matrix that is only positive semi-definite
+    F = {e_: Om_out[e_] for e_ in range(TD)}
+    top = Om_out[0][0]
+    for i in range(1, D):
+        top = np.maximum(top, Om_out[tri(i, i)][0])
+    tau = top * dtype(2.0 ** -40)
+    margin = np.full((B, N), np.inf)
+    for k in range(D):
+        pivot = _chain(F[tri(k, k)], [(F[tri(k, c)], F[tri(k, c)]) for c in range(k)], negate=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            keep = pivot[0] > tau
+            margin = np.minimum(margin, np.where(top > 0, np.abs((pivot[0] - tau).astype(np.float64)) /
+                                                 np.maximum(top.astype(np.float64), 1e-300), np.inf))
+        safe = (np.where(keep, pivot[0], 1.0), None if not track else np.where(keep, pivot[1], 0.0))
+        root = _sqrt(safe)
+        rk = _reciprocal(root)
+        F[tri(k, k)] = (np.where(keep, root[0], 0.0), None if not track else np.where(keep, root[1], 0.0))
+        for i in range(k + 1, D):
+            value = _times(_chain(F[tri(i, k)], [(F[tri(i, c)], F[tri(k, c)]) for c in range(k)], negate=True), rk)
+            F[tri(i, k)] = (np.where(keep, value[0], 0.0), None if not track else np.where(keep, value[1], 0.0))
+
+    def finish(parts):
+        values = np.stack([part[0] for part in parts], axis=-1)
+        values[bad] = np.nan
+        errors = None
+        if track:
+            errors = np.stack([part[1] for part in parts], axis=-1).astype(np.float64)
+            errors[bad] = 0.0
+        return values, errors
+
+    (om_v, om_e), (lam_v, lam_e), (c_v, c_e), (f_v, f_e) = finish(Om_out), finish(lam_out), finish([c_out]), \
+        finish([F[e_] for e_ in range(TD)])
+    margin = np.where(bad, np.inf, margin)
+    return (om_v, lam_v, c_v[..., 0], f_v, flags, float(margin.min()) if margin.size else float("inf")), \
+        (om_e, lam_e, None if c_e is None else c_e[..., 0], f_e)
+
+
+def switching_information_step(model, regime_next, info, y, dtype=np.float64):
+    """(Om [B,N,D(D+1)/2], lam [B,N,D], c [B,N], F [B,N,D(D+1)/2], flags, margin) of one information step
+    (include/aesmc_hip.h: aesmc_switching_information_step, K34) — the comment above states the arithmetic.
+
+    model: `operands`' dict (the probabilities are not read); regime_next: int32 [B,N], the trajectories' regimes s'_{t+1};
+    info: None (the last step's zeros) or (Om, lam, c) of time t+1; y: [B,Dy], the observation of time t+1, float32 or
+    float64, widened.  F is the packed LOWER factor of Om (element (i,k), i >= k, at `tri(i,k)`): Phi = F^T is the upper
+    triangle with Phi^T Phi = Om.  A pivot at or below 2^-40 max_i Om_ii gives a zero column; `margin` is the smallest
+    |pivot - threshold| / max_i Om_ii over all trajectories and columns — only a column whose pivot lies this close to the
+    threshold can be kept on one side and dropped on the other.  A regime outside [0, M): NaN outputs for that trajectory
+    and FLAG_INDEX_OUT_OF_RANGE."""
+    with np.errstate(all="ignore"):
+        return _information(model, regime_next, info, y, dtype, False)[0]
+
+
+def switching_information_step_bound(model, regime_next, info, y):
+    """(bound of Om, of lam, of c, of F), float64: `switching_kalman_step_bound`'s running analysis of the information
+    step, 2 * 1.01 times the running bound; the inputs enter exactly.  A dropped column of F is zero on both sides (its
+    bound is 0): the bound holds for a device that keeps and drops the same columns (`margin`).  Zero where the output is NaN."""
+    with np.errstate(all="ignore"):
+        _, errors = _information(model, regime_next, info, y, np.float64, True)
+    return tuple(np.where(np.isfinite(e), 2 * 1.01 * e, np.inf) for e in errors)
+
+
+def _scores(log_Pi, regime_next, factor, lam, particles, log_w, dtype, track):
+    regime, mean, cov = (np.asarray(part) for part in particles)
+    regime_next, factor, lam = np.asarray(regime_next), np.asarray(factor), np.asarray(lam)
+    log_Pi = np.asarray(log_Pi, dtype=np.float64)
+    (B, K), N = regime.shape, regime_next.shape[1]
+    M, D = log_Pi.shape[0], mean.shape[-1]
+    zero = np.zeros((B, N, K), dtype=dtype)
+    given = lambda array: (np.broadcast_to(np.asarray(array), (B, N, K)).astype(dtype), zero if track else None)
+    one = given(1.0)
+    over_n = lambda array: array[:, :, None]      # [B,N] -> [B,N,1]
+    over_k = lambda array: array[:, None, :]      # [B,K] -> [B,1,K]
+    bad = over_k((regime < 0) | (regime >= M)) | over_n((regime_next < 0) | (regime_next >= M))
+    flags = FLAG_INDEX_OUT_OF_RANGE if bad.any() else 0
+    prior = log_Pi[np.where((regime < 0) | (regime >= M), 0, regime)[:, None, :],
+                   np.where((regime_next < 0) | (regime_next >= M), 0, regime_next)[:, :, None]]
+    F = lambda i, k: given(over_n(factor[:, :, tri(i, k)]))      # F_ik, i >= k
+    lm_ = [given(over_n(lam[:, :, i])) for i in range(D)]
+    m = [given(over_k(mean[:, :, i])) for i in range(D)]
+    P = [given(over_k(cov[:, :, e])) for e in range(D * (D + 1) // 2)]
+    t = [_chain(given(0.0), [(F(l, i), m[l]) for l in range(i, D)]) for i in range(D)]
+    mq = _chain(given(0.0), [(t[i], t[i]) for i in range(D)])
+    h = [_chain(lm_[l], [(F(l, i), t[i]) for i in range(l + 1)], negate=True) for l in range(D)]
+    lm = _chain(given(0.0), [(lm_[l], m[l]) for l in range(D)])
+    hph = _chain(given(0.0), [(h[c], _chain(given(0.0), [(P[tri(c, l)], h[l]) for l in range(D)])) for c in range(D)])
+    v, Lam = [], {}
+    for i in range(D):
+        W = [_chain(given(0.0), [(F(c, i), P[tri(c, l)]) for c in range(i, D)]) for l in range(D)]
+        v.append(_chain(given(0.0), [(W[l], h[l]) for l in range(D)]))
+        for j in range(i + 1):
+            Lam[tri(i, j)] = _chain(given(1.0 if i == j else 0.0), [(W[l], F(l, j)) for l in range(j, D)])
+    inv, log_det = [], given(0.0)
+    for k in range(D):
+        pivot = _chain(Lam[tri(k, k)], [(Lam[tri(k, c)], Lam[tri(k, c)]) for c in range(k)], negate=True)
+        Lam[tri(k, k)] = _sqrt(pivot)
+        inv.append(_reciprocal(Lam[tri(k, k)]))
+        log_det = _chain(log_det, [(_log(Lam[tri(k, k)]), one)])
+        for i in range(k + 1, D):
+            Lam[tri(i, k)] = _times(_chain(Lam[tri(i, k)], [(Lam[tri(i, c)], Lam[tri(k, c)]) for c in range(k)],
+                                           negate=True), inv[k])
+    x = []
+    for i in range(D):
+        x.append(_times(_chain(v[i], [(Lam[tri(i, c)], x[c]) for c in range(i)], negate=True), inv[i]))
+    xq = _chain(given(0.0), [(x[i], x[i]) for i in range(D)])
+    excluded = np.isneginf(prior)
+    base = given(np.where(excluded, 0.0, prior))
+    if log_w is not None:
+        base = _chain(given(over_k(np.asarray(log_w))), [(base, one)])
+    score = _chain(_chain(_chain(_chain(base, [(lm, one)]), [(given(-0.5), mq)]),
+                          [(given(0.5), _chain(hph, [(xq, one)], negate=True))]), [(log_det, one)], negate=True)
+    value = np.where(bad, np.nan, np.where(excluded, -np.inf, score[0]))
+    error = None
+    if track:
+        error = np.where(bad | excluded, 0.0, score[1]).astype(np.float64)
+    return (value, flags), error
+
+
+def switching_backward_scores(log_Pi, regime_next, factor, lam, particles, log_w=None, dtype=np.float64):
+    """(scores [B,N,K], flags) of one backward step (include/aesmc_hip.h: aesmc_switching_backward_scores, K35) — the
+    comment above states the arithmetic.
+
+    log_Pi: float64 [M,M], -inf where a probability is 0; regime_next: int32 [B,N]; factor, lam: the information step's F
+    [B,N,D(D+1)/2] and lam [B,N,D]; particles: the stored (regime int32 [B,K], mean [B,K,D], cov [B,K,D(D+1)/2]) of step t;
+    log_w: [B,K] or None (equal weights: nothing is added).  The trajectory's constant c is left out: it does not change
+    the draw.  -inf where log Pi[s, s'] is -inf whatever the rest is; a regime outside [0, M) on either side: NaN and
+    FLAG_INDEX_OUT_OF_RANGE."""
+    with np.errstate(all="ignore"):
+        return _scores(log_Pi, regime_next, factor, lam, particles, log_w, dtype, False)[0]
+
+
+def switching_backward_scores_bound(log_Pi, regime_next, factor, lam, particles, log_w=None):
+    """The bound of `switching_backward_scores` [B,N,K], float64: the running analysis of `switching_kalman_step_bound`, 2 *
+    1.01 times the running bound; the inputs enter exactly.  Zero where the score is NaN or -inf by exclusion."""
+    with np.errstate(all="ignore"):
+        _, error = _scores(log_Pi, regime_next, factor, lam, particles, log_w, np.float64, True)
+    return np.where(np.isfinite(error), 2 * 1.01 * error, np.inf)
+
+
+def categorical_draw(scores, u):
+    """(idx int64 [R], margin [R], flags): K21's draw without a transition term, one trajectory per row — scores [R,K],
+    u [R]: idx = min(#{k : C_k <= u C_{K-1}}, the last k of positive weight), C the running sum of exp(score - row maximum)
+    (zero below -745.2).  A NaN in a row: idx = K and FLAG_NAN_LOG_WEIGHT; no finite maximum: idx = K and
+    FLAG_DEGENERATE_ROW.  margin: |u C_{K-1} - C_k| at the nearest step k of the running sum, over C_{K-1} — only a draw
+    this close to a step can differ between two evaluations of the scores."""
+    scores, u = np.asarray(scores, dtype=np.float64), np.asarray(u, dtype=np.float64)
+    R, K = scores.shape
+    with np.errstate(invalid="ignore", over="ignore"):
+        nan = np.isnan(scores).any(axis=1)
+        top = np.where(nan, 0.0, np.max(np.where(np.isnan(scores), -np.inf, scores), axis=1))
+        degenerate = ~nan & ~np.isfinite(top)
+        x = scores - np.where(nan | degenerate, 0.0, top)[:, None]
+        w = np.where(x > -745.2, np.exp(np.minimum(x, 0.0)), 0.0)
+        w = np.where((nan | degenerate)[:, None], 1.0, w)
+    running = np.cumsum(w, axis=1)
+    position = u * running[:, -1]
+    count = (running <= position[:, None]).sum(axis=1)
+    last = K - 1 - np.argmax(w[:, ::-1] > 0, axis=1)
+    idx = np.where(nan | degenerate, K, np.minimum(count, last)).astype(np.int64)
+    margin = np.abs(running - position[:, None]).min(axis=1) / running[:, -1]
+    margin = np.where(nan | degenerate, np.inf, margin)
+    flags = (FLAG_NAN_LOG_WEIGHT if nan.any() else 0) | (FLAG_DEGENERATE_ROW if degenerate.any() else 0)
+    return idx, margin, flags
+
+
+def switching_backward_pass(filtered, model, observations, uniforms):
+    """The whole Rao-Blackwellised backward simulation on replayed uniforms.  filtered: a pass's dict (`switching_pass`: with
+    log_weights; `adapted_switching_pass`: without, the stored systems are equally weighted); model: `operands`' dict;
+    observations: T x [B,Dy]; uniforms: T x float64 [B,N] (block t draws time t).
+
+    Returns a dict: regimes (T x int32 [B,N]), indices (T x int64 [B,N]: which stored particle), margins (T x [B,N]:
+    `categorical_draw`'s, per draw), score_bounds (T x [B,N]: the largest bound of a draw's scores, 0 at T-1 where the
+    scores are the stored log-weights), smoothed_regime_probabilities [T,B,M] (the trajectories' frequencies), information
+    ((T-1) tuples (Om, lam, c, F), the one of time t at position t), pivot_margins ((T-1) floats) and flags."""
+    T = len(observations)
+    B, N = np.asarray(uniforms[0]).shape
+    M = model["A"].shape[0]
+    K = np.asarray(filtered["regimes"][0]).shape[1]
+    with np.errstate(divide="ignore"):
+        log_Pi = np.log(model["Pi"])
+    weights = filtered.get("log_weights")
+    out = {"regimes": [None] * T, "indices": [None] * T, "margins": [None] * T, "score_bounds": [None] * T,
+           "information": [None] * (T - 1), "pivot_margins": [None] * (T - 1)}
+    flags, info, rows = 0, None, np.arange(B)[:, None]
+    for t in range(T - 1, -1, -1):
+        particles = tuple(np.asarray(filtered[name][t]) for name in ("regimes", "means", "covariances"))
+        log_w = None if weights is None else np.asarray(weights[t])
+        if t == T - 1:
+            scores = np.broadcast_to((np.zeros((B, K)) if log_w is None else log_w)[:, None, :], (B, N, K))
+            bound = np.zeros((B, N))
+        else:
+            om, lam, c, factor, bits, margin = switching_information_step(model, out["regimes"][t + 1], info,
+                                                                          observations[t + 1])
+            flags |= bits
+            info = (om, lam, c)
+            out["information"][t], out["pivot_margins"][t] = (om, lam, c, factor), margin
+            scores, bits = switching_backward_scores(log_Pi, out["regimes"][t + 1], factor, lam, particles, log_w)
+            flags |= bits
+            bound = switching_backward_scores_bound(log_Pi, out["regimes"][t + 1], factor, lam, particles, log_w).max(axis=2)
+        idx, margin, bits = categorical_draw(scores.reshape(B * N, K), np.asarray(uniforms[t]).reshape(-1))
+        flags |= bits
+        idx = idx.reshape(B, N)
+        out["indices"][t], out["margins"][t], out["score_bounds"][t] = idx, margin.reshape(B, N), bound
+        out["regimes"][t] = particles[0][rows, np.minimum(idx, K - 1)].astype(np.int32)
+    out["smoothed_regime_probabilities"] = np.stack([
+        np.stack([(s == i).mean(axis=1) if N else np.zeros(B) for i in range(M)], axis=1) for s in out["regimes"]])
+    out["flags"] = flags
+    return out
+
+
+def _information_sensitivities(model, regime_next, info, y):
+    """How an error of (Om, lam) at time t+1 reaches the information step's outputs, to first order (the largest over the
+    trajectories), from plain np.linalg on full matrices.  With Oh = Om + C^T R^-1 C, lh = lam + C^T R^-1 (y - d), Q =
+    diag(q^2), J = (I + Q Oh)^-1 and g = J^T lh the step is Om' = A^T Oh J A, lam' = A^T (g - Oh J b), so
+
+        dOm'  = (J A)^T dOm (J A)                                    |dOm'|  <= |J A|^2 |dOm|
+        dlam' = (J A)^T dlam - (J A)^T dOm (Q g + J b)               |dlam'| <= |J A| |dlam| + |J A| |Q g + J b| |dOm|
+
+    in the spectral norm (the Euclidean norm of a vector).  Returns (oo, ll, lo): the three factors."""
+    regime_next = np.asarray(regime_next)
+    B, N = regime_next.shape
+    M, D = model["A"].shape[0], model["A"].shape[-1]
+    j = np.clip(regime_next, 0, M - 1)
+    A, C = model["A"][j], model["C"][j]
+    q2, r2 = model["q"][j] ** 2, model["r"][j] ** 2
+    Om = np.zeros((B, N, D, D)) if info is None else unpack(np.asarray(info[0]), D)
+    lam = np.zeros((B, N, D)) if info is None else np.asarray(info[1])
+    weighted = np.swapaxes(C, -1, -2) / r2[:, :, None, :]                                  # C^T R^-1
+    Oh = Om + weighted @ C
+    lh = lam + np.einsum("bnij,bnj->bni", weighted, np.asarray(y, dtype=np.float64)[:, None, :] - model["d"][j])
+    J = np.linalg.inv(np.eye(D) + q2[:, :, :, None] * Oh)
+    JA = J @ A
+    g = np.einsum("bnji,bnj->bni", J, lh)
+    carried = q2 * g + np.einsum("bnij,bnj->bni", J, model["b"][j])
+    norm = np.linalg.norm(JA, 2, axis=(-2, -1))
+    return float((norm * norm).max()), float(norm.max()), float((norm * np.linalg.norm(carried, axis=-1)).max())
+
+
+def switching_information_pass(model, regimes, observations):
+    """The information steps of T-1 .. 1 chained along GIVEN regime paths (no draws): regimes T x int32 [B,N], observations
+    T x [B,Dy].  Returns a dict: information ((T-1) tuples (Om, lam, c, F), the one of time t at position t), pivot_margins
+    ((T-1) floats), flags, and tolerances {"omega": (T-1) floats, "lambda": (T-1) floats}, propagated as `switching_pass`
+    propagates the filter's — how far a device run whose launches stay within their bounds may lie from this one, on the
+    spectral norm of a trajectory's Om error and the Euclidean norm of its lam error; with the factors of
+    `_information_sensitivities`, the step's own bound in the Frobenius norm, and 1.01 for the terms of second order:
+
+        tol_Om[t]  = 1.01 oo tol_Om[t+1] + max |Om bound|_F
+        tol_lam[t] = 1.01 (ll tol_lam[t+1] + lo tol_Om[t+1]) + max |lam bound|_2."""
+    T = len(observations)
+    D = model["A"].shape[-1]
+    out = {"information": [None] * (T - 1), "pivot_margins": [None] * (T - 1), "flags": 0,
+           "tolerances": {"omega": [None] * (T - 1), "lambda": [None] * (T - 1)}}
+    info, tol_o, tol_l = None, 0.0, 0.0
+    for t in range(T - 2, -1, -1):
+        om, lam, c, factor, bits, margin = switching_information_step(model, regimes[t + 1], info, observations[t + 1])
+        bound_o, bound_l, _, _ = switching_information_step_bound(model, regimes[t + 1], info, observations[t + 1])
+        fresh_o = float(np.sqrt((unpack(bound_o, D) ** 2).sum(axis=(-2, -1))).max())
+        fresh_l = float(np.sqrt((bound_l ** 2).sum(axis=-1)).max())
+        if info is None:
+            tol_o, tol_l = fresh_o, fresh_l
+        else:
+            oo, ll, lo = _information_sensitivities(model, regimes[t + 1], info, observations[t + 1])
+            tol_o, tol_l = 1.01 * oo * tol_o + fresh_o, 1.01 * (ll * tol_l + lo * tol_o) + fresh_l
+        info = (om, lam, c)
+        out["information"][t], out["pivot_margins"][t] = (om, lam, c, factor), margin
+        out["tolerances"]["omega"][t], out["tolerances"]["lambda"][t] = tol_o, tol_l
+        out["flags"] |= bits
+    return out
+
+
+def exact_regime_marginals(model, ys):
+    """p(s_t = i | y_0..y_{T-1}) [T,M] of ONE series (ys: T x [Dy]) by enumerating all M^T regime sequences, each an exact
+    Kalman filter — `exact_log_likelihood`'s terms, normalised and summed per (t, regime)."""
+    ys = [np.asarray(y, dtype=np.float64).reshape(1, -1) for y in ys]
+    T, M = len(ys), model["A"].shape[0]
+    sequences = list(itertools.product(range(M), repeat=T))
+    terms = np.empty(len(sequences))
+    with np.errstate(divide="ignore"):
+        log_pi0, log_Pi = np.log(model["pi0"]), np.log(model["Pi"])
+    for position, sequence in enumerate(sequences):
+        prior = log_pi0[sequence[0]] + sum(log_Pi[a, b] for a, b in zip(sequence, sequence[1:]))
+        terms[position] = prior + _sequence_log_likelihood(model, sequence, ys)
+    weights = np.exp(terms - terms.max())
+    weights /= weights.sum()
+    marginals = np.zeros((T, M))
+    for weight, sequence in zip(weights, sequences):
+        for t, s in enumerate(sequence):
+            marginals[t, s] += weight
+    return marginals
+
+
+def _sequence_log_likelihood(model, sequence, ys):
+    """log p(y_0..y_{T-1} | s_0..s_{T-1}) of one series by the Kalman filter (plain np.linalg on full matrices)."""
+    D, Dy = model["A"].shape[-1], model["C"].shape[-2]
+    mean, cov, total = model["m0"].copy(), np.diag(model["s0"] ** 2), 0.0
+    for t, s in enumerate(sequence):
+        A, C = model["A"][s], model["C"][s]
+        if t > 0:
+            mean, cov = A @ mean + model["b"][s], A @ cov @ A.T + np.diag(model["q"][s] ** 2)
+        S = C @ cov @ C.T + np.diag(model["r"][s] ** 2)
+        residual = ys[t][0] - C @ mean - model["d"][s]
+        total -= 0.5 * (residual @ np.linalg.solve(S, residual) + np.linalg.slogdet(S)[1] + 2 * Dy * HALF_LOG_2PI)
+        gain = cov @ C.T @ np.linalg.inv(S)
+        mean, cov = mean + gain @ residual, cov - gain @ C @ cov
+    return total
+
+
+# (B, K, N, M, D, Dy): `STEP_SHAPES` with a number of trajectories each — one lane; a partial tile of trajectories; a tile of
+# particles that is not full beside every padded extent; more than one tile of trajectories; the largest M; several tiles
+# of particles
+BACKWARD_SHAPES = [(1, 1, 1, 1, 1, 1), (3, 7, 5, 2, 2, 1), (2, 65, 9, 3, 8, 8), (2, 300, 17, 4, 5, 3), (1, 257, 8, 16, 8, 1),
+                   (2, 1025, 3, 2, 3, 2)]
+
+
+def example_backward_step(B, K, N, M, D, Dy, steps=1, observation_dtype=np.float64, seed=0):
+    """(model, regime_next, info, y, particles, log_w) of one backward step: `example_step`'s model and stored particles,
+    random regimes for the trajectories, and `info` the result of `steps - 1` information steps from the zeros of the last
+    timestep (steps = 1: None, the first step; with Dy < D the Om that steps = 2 hands over is rank-deficient)."""
+    model, particles, _, _, _ = example_step(B, K, M, D, Dy, seed=seed)
+    rng = np.random.default_rng([seed, B, K, N, M, D, Dy, 34])
+    info = None
+    for _ in range(steps - 1):
+        om, lam, c, _, _, _ = switching_information_step(model, rng.integers(0, M, (B, N)).astype(np.int32), info,
+                                                         rng.standard_normal((B, Dy)))
+        info = (om, lam, c)
+    regime_next = rng.integers(0, M, (B, N)).astype(np.int32)
+    y = rng.standard_normal((B, Dy)).astype(observation_dtype)
+    return model, regime_next, info, y, particles, rng.standard_normal((B, K))

@@ -3,12 +3,15 @@
 covariance of the continuous state given its regime history (kernel K31).
 
     python examples/slds_filter.py [--regimes 2] [--dim 2] [--particles 256] [--batch 8] [--timesteps 200] [--short 6]
-                                   [--lookahead]
+                                   [--lookahead] [--smooth]
 
 Simulates a series whose regimes differ in their dynamics, filters it, and prints how often the most probable filtered
 regime is the true one and the error of the filtered mean; then, for a short series, log Z-hat beside the exact log p(y)
 from the enumeration of all M^T regime sequences.  With --lookahead the filter is `adapted_switching_filter`: every step
-resamples on the exact p(y_t | history) and draws the regime from its exact posterior (kernels K32 and K33).
+resamples on the exact p(y_t | history) and draws the regime from its exact posterior (kernels K32 and K33).  With
+--smooth the stored systems are smoothed by Rao-Blackwellised backward simulation (`switching_backward_simulate`, kernels
+K34 and K35) and the accuracy of the most probable SMOOTHED regime, which has seen the whole series, is printed beside the
+filtered one.
 """
 import argparse
 import os
@@ -44,6 +47,8 @@ def main():
     ap.add_argument("--short", type=int, default=6)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lookahead", action="store_true", help="the fully adapted filter: regimes from their exact posterior")
+    ap.add_argument("--smooth", action="store_true", help="also smooth: regime accuracy given the whole series")
+    ap.add_argument("--trajectories", type=int, default=None, help="backward trajectories per series (default: --particles)")
     args = ap.parse_args()
 
     device = torch.device("cuda", 0)
@@ -59,6 +64,11 @@ def main():
     print("T = {}, {} series, K = {}: filtered regime = true regime {:.1%} of the time; RMSE of the filtered mean {:.3f}; "
           "log Z-hat per step {:.4f}".format(args.timesteps, args.batch, args.particles, accuracy, error,
                                              out["log_marginal_likelihood"].mean().item() / args.timesteps))
+    if args.smooth:
+        smoothed = rao_blackwell.switching_backward_simulate(out, model, observations, num_trajectories=args.trajectories)
+        guess = smoothed["smoothed_regime_probabilities"].argmax(dim=-1)
+        print("smoothed regime = true regime {:.1%} of the time (filtered: {:.1%}); {} backward trajectories per series".format(
+            (guess == torch.stack(regimes)).double().mean().item(), accuracy, smoothed["regimes"][0].size(1)))
     short = [y[:1] for y in observations[:args.short]]
     ops = {name: value.cpu().numpy() for name, value in model.operands().items()}
     exact = contract.exact_log_likelihood(ops, [y.cpu().numpy() for y in short])[0]

@@ -79,7 +79,9 @@ extern "C" {
  *                aesmc_switching_max_regimes (K31: one step of the Rao-Blackwellised filter of a switching
  *                linear-Gaussian model);
  *                aesmc_switching_lookahead, aesmc_switching_kalman_draw (K32, K33: the exact first-stage weights and regime
- *                posteriors of that model, and K31's step with the regime drawn from them — its fully adapted filter).
+ *                posteriors of that model, and K31's step with the regime drawn from them — its fully adapted filter);
+ *                aesmc_switching_information_step, aesmc_switching_backward_scores (K34, K35: Rao-Blackwellised backward
+ *                simulation over the stored systems of either filter — its smoother).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -709,7 +711,60 @@ int aesmc_switching_kalman_draw(int y_dtype, const aesmc_switching_model *model,
                                 const double *particle_cdf, const void *y, int32_t *regime_out, double *mean_out,
                                 double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K, void *stream);
 
-/* K6 — reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
+/* K34 — the information step of Rao-Blackwellised backward simulation for the same model (Fong, Godsill, Doucet & West
+ * 2002; Whiteley, Andrieu & Doucet 2010; Lindsten, Bunch, Saerkkae, Schoen & Godsill 2016).  Trajectory (b,n) carries, for its
+ * future regimes, p(y_{t+1..T-1} | z_t) = exp(c + lam^T z_t - 1/2 z_t^T Om z_t); the call takes (Om, lam, c) of time t+1 to
+ * time t.  With j = regime_next[b,n] (the trajectory's regime at t+1), y the observation of time t+1, r2_i = r_j[i]^2,
+ * q2_i = q_j[i]^2, sq_i = sqrt(q2_i); float64, every sum ONE chain of fused multiply-adds in ascending index order starting
+ * from the value named first; symmetric matrices and the factor as packed lower triangles, (i,k) with i >= k at i(i+1)/2 + k:
+ *   e_i    = y[b,i] - d_j[i];  rho_i = 1 / r2_i;  G_il = C_j[i,l] rho_i
+ *   Oh_pq  = Om_pq + sum_i G_ip C_j[i,q];   lh_p = lam_p + sum_i G_ip e_i
+ *   ch     = ((c - 1/2 sum_i (e_i rho_i) e_i) - 1/2 sum_i log r2_i) - Dy * (1/2 log 2 pi)
+ *   Mm_pq  = (p == q) + (sq_p sq_q) Oh_pq;  L = chol(Mm) column by column as K31's Lam (the pivots are at least 1)
+ *   X_il   = (sq_i Oh_il - sum_{c<i} L_ic X_cl) / L_ii;   w_i = (sq_i lh_i - sum_{c<i} L_ic w_c) / L_ii
+ *   Ot_pq  = Oh_pq - sum_i X_ip X_iq;       g_p = lh_p - sum_i X_ip w_i
+ *   ob_p   = 0 + sum_l Ot_pl b_j[l]
+ *   omega_out_pq  = 0 + sum_i A_j[i,p] (0 + sum_c Ot_ic A_j[c,q]);      lambda_out_p = 0 + sum_i A_j[i,p] (g_i - ob_i)
+ *   c_out  = (((ch - sum_i log L_ii) + 1/2 sum_i w_i^2) + sum_i b_j[i] g_i) - sum_i (1/2 b_j[i]) ob_i
+ *   factor_out F: the lower factor of omega_out (F F^T = omega_out; Phi = F^T is upper-triangular with Phi^T Phi = omega_out),
+ *            column by column with tau = 2^-40 max_i omega_out_ii: p_k = omega_out_kk - sum_{c<k} F_kc^2; where p_k <= tau
+ *            (or is NaN) column k of F is ZERO, otherwise F_kk = sqrt(p_k), F_ik = (omega_out_ik - sum_{c<k} F_ic F_kc) / F_kk
+ *            — omega_out is only positive SEMI-definite (rank <= Dy at t = T-2)
+ *   regime_next int32 [B,N];  omega_in float64 [B,N,D(D+1)/2], lambda_in float64 [B,N,D], c_in float64 [B,N] — all three NULL:
+ *               the zeros of the last step;  y T [B,Dy] (`y_dtype`);  the outputs as the inputs, factor_out as omega_out,
+ *               out of place;  the model's cdf0, cdf, m0 and s0 are not read
+ * A regime outside [0, M) writes NaN to the trajectory's four outputs and raises AESMC_FLAG_INDEX_OUT_OF_RANGE.
+ * NULL or misaligned pointers, negative sizes, M, D or Dy below 1, an unknown dtype, an input given in part and an output
+ * that is another operand return AESMC_ERR_INVALID_ARGUMENT; B N == 0 is a no-op; D, Dy or M above the limits of K31 or B N
+ * beyond 32-bit element arithmetic return AESMC_ERR_UNSUPPORTED.  Every check runs before any launch.  `flags` may be NULL. */
+int aesmc_switching_information_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_next,
+                                     const double *omega_in, const double *lambda_in, const double *c_in, const void *y,
+                                     double *omega_out, double *lambda_out, double *c_out, double *factor_out,
+                                     int32_t *flags, int64_t B, int64_t N, void *stream);
+
+/* K35 — the pair scores of that backward simulation: for trajectory (b,n) with K34's F and lam of time t and stored particle
+ * (b,k) of step t with regime s, mean m, packed covariance P and log-weight log w, the logarithm of w Pi[s, s'] times the
+ * integral of exp(lam^T z - 1/2 z^T Om z) against N(m, P) (the trajectory's c is left out: it does not change the draw).
+ * Only F and lam are read (Om m = F (F^T m)); chains as K34's:
+ *   t_i = 0 + sum_{l>=i} F_li m_l;   mq = 0 + sum_i t_i^2;   h_l = lam_l - sum_{i<=l} F_li t_i;   lm = 0 + sum_l lam_l m_l
+ *   hph = 0 + sum_c h_c (0 + sum_l P_cl h_l)
+ *   W_il = 0 + sum_{c>=i} F_ci P_cl;  v_i = 0 + sum_l W_il h_l;  Lam_ij = (i == j) + sum_{l>=j} W_il F_lj,  j <= i
+ *   G = chol(Lam) as K31's (the pivots are at least 1: no test, no flag);  x_i = (v_i - sum_{c<i} G_ic x_c) / G_ii
+ *   scores[b,n,k] = ((((log_w[b,k] + log_Pi[s, s']) + lm) - 1/2 mq) + 1/2 (hph - sum_i x_i^2)) - sum_i log G_ii
+ *                   and -inf where log_Pi[s, s'] is -inf, whatever the rest is
+ *   log_Pi float64 [M,M] (rows: from-regime; -inf allowed);  regime_next int32 [B,N];  factor float64 [B,N,D(D+1)/2], lambda
+ *   float64 [B,N,D];  regime int32 [B,K], mean float64 [B,K,D], cov float64 [B,K,D(D+1)/2];  log_w float64 [B,K] or NULL
+ *   (equal weights: nothing is added);  scores float64 [B,N,K]
+ * A regime outside [0, M) on either side writes NaN and raises AESMC_FLAG_INDEX_OUT_OF_RANGE.  P is never factored: P = 0
+ * is fine.  NULL (but log_w, flags) or misaligned pointers, negative sizes, M or D below 1 and scores being another operand
+ * return AESMC_ERR_INVALID_ARGUMENT; B N == 0 or K == 0 is a no-op; D or M above the limits of K31 or B N K (or B K D(D+1)/2,
+ * B N D(D+1)/2) beyond 32-bit element arithmetic return AESMC_ERR_UNSUPPORTED.  Every check runs before any launch. */
+int aesmc_switching_backward_scores(const double *log_Pi, const int32_t *regime_next, const double *factor,
+                                    const double *lambda, const int32_t *regime, const double *mean, const double *cov,
+                                    const double *log_w, double *scores, int32_t *flags, int64_t B, int64_t K, int64_t N,
+                                    int64_t M, int64_t D, void *stream);
+
+/* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
  * Replaces the broadcast multiply and the add that follow the noise draw in
  * torch.distributions.Normal.rsample as aesmc/state.py:61-111 (`state.sample`) calls it; the
