@@ -2642,6 +2642,65 @@ class HipKernels:
                      name="switching_backward_scores")
         return scores
 
+    # ---- K36 -----------------------------------------------------------------------------------
+    def switching_smooth_combine(self, model, regime_next, filtered, factor, lam, omega_next=None, cov_next=None):
+        """The two-filter combination of the state smoother (aesmc_switching_smooth_combine, K36).  filtered: (mean float64
+        [B,N,D], cov float64 [B,N,D(D+1)/2]), the conditional filter's of time t; factor [B,N,D(D+1)/2], lam [B,N,D]:
+        `switching_information_step`'s of time t.  The lag-one cross-covariance is formed when cov_next (the smoothed packed
+        covariance of time t+1) is given: model as `switching_kalman_step`'s, regime_next int32 [B,N] (the regimes at t+1),
+        omega_next: `switching_information_step`'s omega of time t+1 or None (t+1 = T-1).  Without cov_next the model,
+        regime_next and omega_next are not read (pass None).  Returns (mean [B,N,D], cov [B,N,D(D+1)/2], cross [B,N,D,D] or
+        None), new tensors.  With cov_next a regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE."""
+        mean, cov = filtered
+        _require_hip(mean, "mean")
+        device = mean.device
+        if mean.dim() != 3 or mean.dtype != torch.float64:
+            raise ValueError("aesmc_amd: mean must be [batch_size, num_trajectories, D] float64, got {} {}".format(
+                tuple(mean.shape), mean.dtype))
+        B, N, D = mean.shape
+        TD = D * (D + 1) // 2
+        cross = cov_next is not None
+        wanted = [(cov, (B, N, TD), "cov"), (factor, (B, N, TD), "factor"), (lam, (B, N, D), "lam")]
+        if cross:
+            wanted.append((cov_next, (B, N, TD), "cov_next"))
+            if omega_next is not None:
+                wanted.append((omega_next, (B, N, TD), "omega_next"))
+        elif model is not None or regime_next is not None or omega_next is not None:
+            raise ValueError("aesmc_amd: switching_smooth_combine reads model, regime_next and omega_next only with cov_next")
+        for tensor, shape, what in wanted:
+            _require_hip(tensor, what)
+            if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
+        max_d, max_dy, max_m = self.switching_limits()
+        block, M, Dy = None, 0, 0
+        if cross:
+            _require_hip(regime_next, "regime_next")
+            if tuple(regime_next.shape) != (B, N) or regime_next.dtype != torch.int32 or regime_next.device != device:
+                raise ValueError("aesmc_amd: regime_next must be [{}, {}] int32 on {}".format(B, N, device))
+            block, M, model_d, Dy = self._switching_block(model, device)
+            if model_d != D:
+                raise ValueError("aesmc_amd: the model's latent has {} values, the mean {}".format(model_d, D))
+            regime_next, cov_next = regime_next.contiguous(), cov_next.contiguous()
+            omega_next = None if omega_next is None else omega_next.contiguous()
+        if not (1 <= D <= max_d and M <= max_m and Dy <= max_dy and B * N <= 0x7fffffff // (max_d * max_d)):
+            raise ValueError("aesmc_amd: switching_smooth_combine does not take these operands (see switching_covers)")
+        mean, cov, factor, lam = mean.contiguous(), cov.contiguous(), factor.contiguous(), lam.contiguous()
+        out_mean = torch.empty((B, N, D), dtype=torch.float64, device=device)
+        out_cov = torch.empty((B, N, TD), dtype=torch.float64, device=device)
+        out_cross = torch.empty((B, N, D, D), dtype=torch.float64, device=device) if cross else None
+        if out_mean.numel() == 0:
+            return out_mean, out_cov, out_cross
+        per_trajectory = 8 * (2 * D + 3 * TD) + \
+            ((4 + 8 * (TD + D * D) + (8 * TD if omega_next is not None else 0)) if cross else 0)
+        self._launch(device, self._lib.aesmc_switching_smooth_combine,
+                     (None if block is None else ctypes.byref(block), _ptr(regime_next), _ptr(mean), _ptr(cov), _ptr(factor),
+                      _ptr(lam), _ptr(omega_next), _ptr(cov_next), _ptr(out_mean), _ptr(out_cov), _ptr(out_cross),
+                      _ptr(self.flags(device)), B, N, D, self._stream(mean)),
+                     lambda: B * N * per_trajectory + 8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
+                     (model, regime_next, mean, cov, factor, lam, omega_next, cov_next, out_mean, out_cov, out_cross, block),
+                     name="switching_smooth_combine")
+        return out_mean, out_cov, out_cross
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 

@@ -38,6 +38,16 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                `aesmc_switching_backward_scores`, one lane per particle walking a tile of trajectories);
                                K21 then draws one particle per trajectory
     switching_smooth           a filter, then that
+    conditional_kalman_filter  the exact Kalman filter of z along GIVEN regime paths, one per trajectory: K31 with the regime
+                               forced; log p(y | s_{0:T-1}) per trajectory
+    switching_state_smooth     the smoothed continuous state from regime trajectories: E[z_t | y], Cov[z_t | y] and the lag-one
+                               moments E[z_{t+1} z_t^T | y] (what an EM M-step for A, b, q needs) as the average of the EXACT
+                               state smoothers along the trajectories — still only the regimes are sampled.  Per timestep
+                               K34 along the trajectory's regimes and K36 (`aesmc_switching_smooth_combine`, one lane per
+                               trajectory): the two-filter combination of the filter's N(m, P) with K34's information, which
+                               factors I + F^T P F (pivots at least 1) and never a predicted covariance — q = 0 components
+                               and P = 0 are fine where an RTS step would divide by a singular matrix
+    switching_smooth_states    a filter, the backward simulation, then that (examples/slds_em.py: Monte Carlo EM on it)
 
 The reference has no counterpart; this module adds to its interface and changes none of it.
 """
@@ -66,7 +76,9 @@ class SwitchingLinearGaussian(torch.nn.Module):
 
     pi0 [M], Pi [M,M] (rows: from-regime); m0 [D], s0 (one value or D); A [M,D,D], b [M,D], q [M,D]; C [M,Dy,D], d [M,Dy],
     r [M,Dy].  A leading extent of 1 in place of M means shared across regimes.  Everything is held as a float64 buffer
-    (`.to(device)` moves the model); nothing here is learned: the filter is not differentiable."""
+    (`.to(device)` moves the model).  The filters are not differentiable and the buffers are no parameters: a model is
+    learned by EM — `switching_smooth_states` gives the E-step's smoothed moments E[z_t z_t^T | y], E[z_{t+1} z_t^T | y] and
+    regime trajectories, the M-step builds a new model from them (examples/slds_em.py)."""
 
     def __init__(self, pi0, Pi, m0, s0, A, b, q, C, d, r):
         super().__init__()
@@ -529,6 +541,199 @@ def switching_smooth(observations, model, num_particles, num_trajectories=None, 
     run = adapted_switching_filter if lookahead else switching_filter
     filtered = run(observations, model, num_particles, resampling=resampling)
     out = switching_backward_simulate(filtered, model, observations, num_trajectories=num_trajectories)
+    return out, filtered["log_marginal_likelihood"]
+
+
+def _check_regimes(name, regimes, num_timesteps, batch_size, device):
+    """N of a regime path per trajectory: T int32 [batch_size, N] tensors on the device."""
+    if regimes is None or len(regimes) != num_timesteps:
+        raise ValueError("{}: regimes must hold one tensor per timestep ({}), got {}".format(
+            name, num_timesteps, 0 if regimes is None else len(regimes)))
+    first = regimes[0]
+    if not torch.is_tensor(first) or first.dim() != 2:
+        raise ValueError("{}: regimes[0] must be a [batch_size, num_trajectories] int32 tensor".format(name))
+    shape = (batch_size, first.size(1))
+    for time, regime in enumerate(regimes):
+        if not torch.is_tensor(regime) or tuple(regime.shape) != shape or regime.dtype != torch.int32 or \
+                regime.device != device:
+            raise ValueError("{}: regimes[{}] must be {} int32 on {}".format(name, time, shape, device))
+    return shape[1]
+
+
+def _conditional_filter(provider, ops, observations, regimes, num_regimes):
+    """(means, covariances, log_likelihood, whether a regime was out of range: a device flag) of K31 forced along `regimes`
+    — `testing.rao_blackwell._forced`: every cumulative row (1/M, .., 1), the uniform (s + 1/2) / M, no ancestors.  Reads no
+    flags and nothing else from the device."""
+    device = regimes[0].device
+    edges = (torch.arange(num_regimes, dtype=torch.float64, device=device) + 1.0) / num_regimes
+    forced = dict(ops, cdf0=edges, cdf=edges.expand(num_regimes, num_regimes).contiguous())
+    log_likelihood = torch.zeros(regimes[0].shape, dtype=torch.float64, device=device)
+    outside = torch.zeros((), dtype=torch.bool, device=device)
+    means, covariances, state = [], [], None
+    for regime, observation in zip(regimes, observations):
+        outside = outside | ((regime < 0) | (regime >= num_regimes)).any()
+        uniforms = (regime.to(torch.float64) + 0.5) / num_regimes
+        drawn, mean, cov, log_w = provider.switching_kalman_step(forced, state, None, uniforms, observation)
+        state = (drawn, mean, cov)
+        log_likelihood = log_likelihood + log_w
+        means.append(mean), covariances.append(cov)
+    return means, covariances, log_likelihood, outside
+
+
+def _finish_conditional(name, provider, device, outside, log_likelihood):
+    """The one read at the end of a run along given regimes: the flags, the out-of-range marker, the NaN check."""
+    flags = provider.read_flags(device)
+    if bool(outside):
+        raise ValueError("{}: regimes holds a value outside [0, M)".format(name))
+    inference._raise_for_flags(flags)
+    if bool(torch.isnan(log_likelihood).any()):
+        raise FloatingPointError("log_weight contains nan element(s)")
+
+
+def _prepare_conditional(name, provider, observations, model, regimes):
+    num_timesteps = len(observations)
+    if num_timesteps == 0:
+        raise ValueError("{}: observations must hold at least one timestep".format(name))
+    ops = model.operands()
+    num_trajectories = regimes[0].size(1) if regimes is not None and len(regimes) and torch.is_tensor(regimes[0]) and \
+        regimes[0].dim() == 2 else 1
+    batch_size, device = _check_observations(name, provider, observations, model, num_trajectories)
+    num_trajectories = _check_regimes(name, regimes, num_timesteps, batch_size, device)
+    if batch_size * num_trajectories > 0x7fffffff // (MAX_LATENT_DIM * MAX_LATENT_DIM):
+        _refuse("{} trajectories in {} batch rows (batch_size * num_trajectories * D^2 beyond 32-bit element arithmetic)"
+                .format(num_trajectories, batch_size))
+    return ops, num_timesteps, batch_size, num_trajectories, device
+
+
+def conditional_kalman_filter(observations, model, regimes):
+    """The exact Kalman filter of z given a regime path per trajectory: K31 with the regime FORCED (every cumulative row
+    replaced by (1/M, .., 1) and the uniform by (s + 1/2) / M), no ancestors, one particle per trajectory.
+
+    observations, model: as `switching_filter`'s.  regimes: T int32 [batch_size, N] tensors on the device — what
+    `switching_backward_simulate` returns, or any paths of the caller's.
+
+    Returns a dict: means (T float64 [batch_size, N, D]), covariances (T float64 [batch_size, N, D(D+1)/2], packed) — the
+    moments of p(z_t | y_{0:t}, s_{0:t}) — and log_likelihood [batch_size, N] float64: log p(y_{0:T-1} | s_{0:T-1}), the sum of
+    the steps' log-weights.
+
+    ValueError for an invalid model, T == 0, regimes of the wrong length, shape or dtype, and — read once, at the end, with
+    the flags — a regime outside [0, M) (a forced uniform built from one would draw a wrong regime silently).  Refusals,
+    flags and NaNs as `switching_filter`'s; an exception on the way discards whatever was flagged.  No host synchronisation
+    inside the loop.  N == 0 gives empty tensors without a launch.  Runs under torch.no_grad(): NOT differentiable."""
+    name = "conditional_kalman_filter"
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops, num_timesteps, batch_size, num_trajectories, device = _prepare_conditional(name, provider, observations,
+                                                                                            model, regimes)
+            D = model.latent_dim
+            if num_trajectories == 0:
+                empty = lambda *tail: torch.empty((batch_size, 0) + tail, dtype=torch.float64, device=device)
+                return {"means": [empty(D) for _ in range(num_timesteps)],
+                        "covariances": [empty(D * (D + 1) // 2) for _ in range(num_timesteps)], "log_likelihood": empty()}
+            means, covariances, log_likelihood, outside = _conditional_filter(provider, ops, observations, regimes,
+                                                                              model.num_regimes)
+            _finish_conditional(name, provider, device, outside, log_likelihood)
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return {"means": means, "covariances": covariances, "log_likelihood": log_likelihood}
+
+
+def switching_state_smooth(observations, model, regimes, return_cross_moments=False, return_trajectories=False):
+    """The smoothed continuous state of a `SwitchingLinearGaussian` from regime trajectories: along a trajectory the model is
+    linear-Gaussian and its smoother exact, and the estimate is the average of those exact smoothers over the trajectories
+    (Fong, Godsill, Doucet & West 2002; Lindsten, Bunch, Saerkkae, Schoen & Godsill 2016) — the regimes alone are sampled.
+
+    observations, model: as `switching_filter`'s.  regimes: T int32 [batch_size, N] on the device: equally weighted
+    trajectories, `switching_backward_simulate`'s (or any paths: the result is then the exact smoother given them).
+
+    `conditional_kalman_filter` runs forward; for t = T-2 .. 0 K34 takes the trajectory's information one step back under its
+    regime at t+1 and K36 (`aesmc_switching_smooth_combine`) combines it with the filter's moments of time t — the two-filter
+    form, which factors I + F^T P F (pivots at least 1) and never the predicted covariance: models with q = 0 components
+    and P = 0 are fine.  At T-1 the smoothed moments are the filtered ones.
+
+    Returns a dict: smoothed_mean [T, batch_size, D] (the average over the N trajectories: the estimate of E[z_t | y_{0:T-1}]);
+    smoothed_covariance [T, batch_size, D, D] (the mixture's, mean(P^s + m^s m^sT) - mean mean^T: of Cov[z_t | y_{0:T-1}]);
+    log_likelihood [batch_size, N] (`conditional_kalman_filter`'s).  With return_cross_moments, smoothed_cross_moment
+    [T-1, batch_size, D, D]: mean_n(cross_n + m^s_{t+1,n} m^sT_{t,n}), the estimate of E[z_{t+1} z_t^T | y_{0:T-1}] (rows: t+1)
+    — what an EM M-step for A, b, q needs.  With return_trajectories, the per-trajectory means (T [batch_size, N, D]),
+    covariances (T [batch_size, N, D(D+1)/2], packed) and cross_covariances (T-1 [batch_size, N, D, D]: Cov(z_{t+1,i},
+    z_{t,l} | y, s)).  The cross-covariances are asked of K36 only with one of the two.
+
+    Validation, refusals and flags as `conditional_kalman_filter`'s: one read at the end, an exception on the way discards
+    whatever was flagged, no host synchronisation inside the loops.  N == 0 gives zero moments and empty trajectories
+    without a launch; T == 1 launches no K34 and no K36.  Runs under torch.no_grad(): NOT differentiable."""
+    name = "switching_state_smooth"
+    provider = _kernels.get()
+    want_cross = bool(return_cross_moments or return_trajectories)
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops, num_timesteps, batch_size, num_trajectories, device = _prepare_conditional(name, provider, observations,
+                                                                                            model, regimes)
+            D = model.latent_dim
+            last = num_timesteps - 1
+            if num_trajectories == 0:
+                zeros = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
+                empty = lambda *tail: torch.empty((batch_size, 0) + tail, dtype=torch.float64, device=device)
+                out = {"smoothed_mean": zeros(num_timesteps, batch_size, D),
+                       "smoothed_covariance": zeros(num_timesteps, batch_size, D, D), "log_likelihood": empty()}
+                if return_cross_moments:
+                    out["smoothed_cross_moment"] = zeros(last, batch_size, D, D)
+                if return_trajectories:
+                    out.update(means=[empty(D) for _ in range(num_timesteps)],
+                               covariances=[empty(D * (D + 1) // 2) for _ in range(num_timesteps)],
+                               cross_covariances=[empty(D, D) for _ in range(last)])
+                return out
+            filtered_means, filtered_covs, log_likelihood, outside = _conditional_filter(provider, ops, observations, regimes,
+                                                                                         model.num_regimes)
+            means, covs, crosses = [None] * num_timesteps, [None] * num_timesteps, [None] * last
+            means[last], covs[last] = filtered_means[last], filtered_covs[last]
+            info = None
+            for time in range(last - 1, -1, -1):
+                omega_next = None if info is None else info[0]
+                omega, lam, c, factor = provider.switching_information_step(ops, regimes[time + 1], info,
+                                                                            observations[time + 1])
+                info = (omega, lam, c)
+                if want_cross:
+                    means[time], covs[time], crosses[time] = provider.switching_smooth_combine(
+                        ops, regimes[time + 1], (filtered_means[time], filtered_covs[time]), factor, lam, omega_next,
+                        covs[time + 1])
+                else:
+                    means[time], covs[time], _ = provider.switching_smooth_combine(
+                        None, None, (filtered_means[time], filtered_covs[time]), factor, lam)
+            stacked = torch.stack(means)                                                   # [T,B,N,D]
+            average = stacked.mean(dim=2)
+            second = (unpack_covariance(torch.stack(covs), D) + stacked.unsqueeze(-1) * stacked.unsqueeze(-2)).mean(dim=2)
+            out = {"smoothed_mean": average,
+                   "smoothed_covariance": second - average.unsqueeze(-1) * average.unsqueeze(-2),
+                   "log_likelihood": log_likelihood}
+            if return_cross_moments:
+                out["smoothed_cross_moment"] = (torch.stack(crosses) + stacked[1:].unsqueeze(-1) *
+                                                stacked[:-1].unsqueeze(-2)).mean(dim=2) if last > 0 else \
+                    torch.zeros((0, batch_size, D, D), dtype=torch.float64, device=device)
+            if return_trajectories:
+                out.update(means=means, covariances=covs, cross_covariances=crosses)
+            _finish_conditional(name, provider, device, outside, log_likelihood)
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
+
+
+def switching_smooth_states(observations, model, num_particles, num_trajectories=None, resampling=None, lookahead=False,
+                            return_trajectories=False):
+    """Runs `switching_filter` (lookahead: `adapted_switching_filter`), `switching_backward_simulate` over what it stored and
+    `switching_state_smooth` along the drawn trajectories with return_cross_moments (K34 runs once more along the drawn
+    regimes: B N lanes, a tenth of a backward step).  Returns (a dict: `switching_backward_simulate`'s regimes and
+    smoothed_regime_probabilities with `switching_state_smooth`'s smoothed_mean, smoothed_covariance, smoothed_cross_moment
+    and log_likelihood — with return_trajectories its per-trajectory means, covariances and cross_covariances too —, the
+    filter's log_marginal_likelihood [batch_size])."""
+    run = adapted_switching_filter if lookahead else switching_filter
+    filtered = run(observations, model, num_particles, resampling=resampling)
+    out = switching_backward_simulate(filtered, model, observations, num_trajectories=num_trajectories)
+    out.update(switching_state_smooth(observations, model, out["regimes"], return_cross_moments=True,
+                                      return_trajectories=return_trajectories))
     return out, filtered["log_marginal_likelihood"]
 
 

@@ -1167,3 +1167,320 @@ def example_backward_step(B, K, N, M, D, Dy, steps=1, observation_dtype=np.float
     regime_next = rng.integers(0, M, (B, N)).astype(np.int32)
     y = rng.standard_normal((B, Dy)).astype(observation_dtype)
     return model, regime_next, info, y, particles, rng.standard_normal((B, K))
+
+
+# ---- the smoothed continuous state: the two-filter combination (K36) and the pass it makes with K31 and K34 ------------------------
+# Given a regime trajectory the model is linear-Gaussian and its state smoother exact (Fong, Godsill, Doucet & West 2002;
+# Lindsten, Bunch, Saerkkae, Schoen & Godsill 2016).  At time t the trajectory has the conditional Kalman filter's N(m, P) (the
+# step under `_forced`) and the information step's (F, lam) of time t, Om = F F^T.  Their product is N(m^s, P^s), per trajectory
+# (sums and packing as above):
+#
+#     t_i  = sum_{l>=i} F_li m_l;   h_l = lam_l - sum_{i<=l} F_li t_i
+#     W_il = sum_{c>=i} F_ci P_cl;  Lam_ij = (i == j) + sum_{l>=j} W_il F_lj   (j <= i; pivots at least 1)
+#     G = chol(Lam);  U_il = (W_il - sum_{c<i} G_ic U_cl) / G_ii
+#     P^s_pq = P_pq - sum_i U_ip U_iq;   m^s_p = m_p + sum_l P^s_pl h_l
+#
+# and, with j = s'_{t+1}, the smoothed P^s_{t+1} and the information step's Om_{t+1} (zeros at t+1 = T-1), the lag-one
+# cross-covariance Cov(z_{t+1,i}, z_{t,l} | y, s) — the off-diagonal block of (Sigma^-1 + diag(0, Oh))^-1 for the joint Sigma of
+# (z_t, z_{t+1}) given y_{0:t}, which inverts no predicted covariance (q = 0 and P = 0 are fine):
+#
+#     rho_i = 1 / r_j[i]^2;  Gc_il = C_j[i,l] rho_i;  Oh_pq = Om_{t+1,pq} + sum_i Gc_ip C_j[i,q]
+#     V_il = sum_c A_j[i,c] P_cl;   Y_pl = sum_q Oh_pq V_ql;   cross_il = V_il - sum_p P^s_{t+1,ip} Y_pl
+def _combine(model, regime_next, filtered, factor, lam, omega_next, cov_next, dtype, track):
+    mean_in, cov_in = (np.asarray(part) for part in filtered)
+    factor, lam = np.asarray(factor), np.asarray(lam)
+    B, N, D = mean_in.shape
+    TD = D * (D + 1) // 2
+    zero = np.zeros((B, N), dtype=dtype)
+    given = lambda array: (np.asarray(array).astype(dtype), zero if track else None)
+    m = [given(mean_in[:, :, i]) for i in range(D)]
+    P = [given(cov_in[:, :, e]) for e in range(TD)]
+    Fv = [given(factor[:, :, e]) for e in range(TD)]
+    F = lambda i, k: Fv[tri(i, k)]      # F_ik, i >= k
+    lm = [given(lam[:, :, i]) for i in range(D)]
+    t = [_chain(given(zero), [(F(l, i), m[l]) for l in range(i, D)]) for i in range(D)]
+    h = [_chain(lm[l], [(F(l, i), t[i]) for i in range(l + 1)], negate=True) for l in range(D)]
+    W = [[_chain(given(zero), [(F(c, i), P[tri(c, l)]) for c in range(i, D)]) for l in range(D)] for i in range(D)]
+    Lam = {}
+    for i in range(D):
+        for j in range(i + 1):
+            Lam[tri(i, j)] = _chain(given(zero + (1.0 if i == j else 0.0)), [(W[i][l], F(l, j)) for l in range(j, D)])
+    inv = []
+    for k in range(D):
+        pivot = _chain(Lam[tri(k, k)], [(Lam[tri(k, c)], Lam[tri(k, c)]) for c in range(k)], negate=True)
+        Lam[tri(k, k)] = _sqrt(pivot)
+        inv.append(_reciprocal(Lam[tri(k, k)]))
+        for i in range(k + 1, D):
+            Lam[tri(i, k)] = _times(_chain(Lam[tri(i, k)], [(Lam[tri(i, c)], Lam[tri(k, c)]) for c in range(k)],
+                                           negate=True), inv[k])
+    U = []
+    for i in range(D):
+        U.append([_times(_chain(W[i][l], [(Lam[tri(i, c)], U[c][l]) for c in range(i)], negate=True), inv[i])
+                  for l in range(D)])
+    S = [_chain(P[tri(p, q)], [(U[i][p], U[i][q]) for i in range(D)], negate=True) for p in range(D) for q in range(p + 1)]
+    ms = [_chain(m[p], [(S[tri(p, l)], h[l]) for l in range(D)]) for p in range(D)]
+    bad, flags, X = np.zeros((B, N), dtype=bool), 0, None
+    if cov_next is not None:
+        regime_next = np.asarray(regime_next)
+        M, Dy = model["A"].shape[0], model["C"].shape[-2]
+        bad = (regime_next < 0) | (regime_next >= M)
+        flags = FLAG_INDEX_OUT_OF_RANGE if bad.any() else 0
+        j = np.where(bad, 0, regime_next)
+        A, C, r = (model[name][j] for name in ("A", "C", "r"))
+        Am = [[given(A[:, :, i, l]) for l in range(D)] for i in range(D)]
+        Cm = [[given(C[:, :, i, l]) for l in range(D)] for i in range(Dy)]
+        rho = [_reciprocal(given(r[:, :, i] * r[:, :, i])) for i in range(Dy)]
+        Gc = [[_times(Cm[i][l], rho[i]) for l in range(D)] for i in range(Dy)]
+        Om = [given(zero)] * TD if omega_next is None else [given(np.asarray(omega_next)[:, :, e]) for e in range(TD)]
+        Oh = [_chain(Om[tri(a, b)], [(Gc[i][a], Cm[i][b]) for i in range(Dy)]) for a in range(D) for b in range(a + 1)]
+        Sn = [given(np.asarray(cov_next)[:, :, e]) for e in range(TD)]
+        V = [[_chain(given(zero), [(Am[i][c], P[tri(c, l)]) for c in range(D)]) for l in range(D)] for i in range(D)]
+        Y = [[_chain(given(zero), [(Oh[tri(p, q)], V[q][l]) for q in range(D)]) for l in range(D)] for p in range(D)]
+        X = [_chain(V[i][l], [(Sn[tri(i, p)], Y[p][l]) for p in range(D)], negate=True) for i in range(D) for l in range(D)]
+
+    def finish(parts):
+        values = np.stack([part[0] for part in parts], axis=-1)
+        values[bad] = np.nan
+        errors = None
+        if track:
+            errors = np.stack([part[1] for part in parts], axis=-1).astype(np.float64)
+            errors[bad] = 0.0
+        return values, errors
+
+    (mean_v, mean_e), (cov_v, cov_e) = finish(ms), finish(S)
+    cross_v = cross_e = None
+    if X is not None:
+        cross_v, cross_e = finish(X)
+        cross_v = cross_v.reshape(B, N, D, D)
+        cross_e = None if cross_e is None else cross_e.reshape(B, N, D, D)
+    return (mean_v, cov_v, cross_v, flags), (mean_e, cov_e, cross_e)
+
+
+def switching_smooth_combine(model, regime_next, filtered, factor, lam, omega_next, cov_next, dtype=np.float64):
+    """(mean [B,N,D], cov [B,N,D(D+1)/2], cross [B,N,D,D] or None, flags) of one combination (include/aesmc_hip.h:
+    aesmc_switching_smooth_combine, K36) — the comment above states the arithmetic.
+
+    filtered: (mean [B,N,D], cov [B,N,D(D+1)/2]), the conditional filter's of time t; factor, lam: the information step's F
+    and lam of time t.  The cross-covariance is formed when `cov_next` (the smoothed packed covariance of time t+1) is given:
+    model: `operands`' dict (A, C, r are read); regime_next int32 [B,N]; omega_next: the information step's Om of time t+1 or
+    None (t+1 = T-1: zeros).  With cov_next None the cross-covariance is None and model, regime_next and omega_next are not
+    read (pass None).  cross[b,n,i,l] = Cov(z_{t+1,i}, z_{t,l}).  A regime outside [0, M), where it is read: NaN in all three
+    outputs of that trajectory and FLAG_INDEX_OUT_OF_RANGE."""
+    with np.errstate(all="ignore"):
+        return _combine(model, regime_next, filtered, factor, lam, omega_next, cov_next, dtype, False)[0]
+
+
+def switching_smooth_combine_bound(model, regime_next, filtered, factor, lam, omega_next, cov_next):
+    """(bound of mean, of cov, of cross or None), float64: `switching_kalman_step_bound`'s running analysis of the
+    combination, 2 * 1.01 times the running bound; the inputs enter exactly.  Zero where the output is NaN."""
+    with np.errstate(all="ignore"):
+        _, errors = _combine(model, regime_next, filtered, factor, lam, omega_next, cov_next, np.float64, True)
+    return tuple(None if e is None else np.where(np.isfinite(e), 2 * 1.01 * e, np.inf) for e in errors)
+
+
+def _combine_sensitivities(model, regime_next, filtered, factor, lam, omega_next, cov_next):
+    """How errors of its inputs reach the combination's outputs, to first order (the largest over the trajectories), from
+    plain np.linalg on full matrices.  With Om = F F^T, J = (I + P Om)^-1, P^s = J P, m^s = J (m + P lam), h = lam - Om m:
+
+        dP^s = J dP J^T - P^s dOm P^s                          |dP^s| <= |J|^2 |dP| + |P^s|^2 |dOm|
+        dm^s = J dm + P^s dlam - P^s dOm m^s + J dP J^T h      |dm^s| <= |J| |dm| + |P^s| |dlam| + |P^s| |m^s| |dOm| + |J| |J^T h| |dP|
+
+    and with Oh = Om_{t+1} + C^T R^-1 C, cross = (I - P^s_{t+1} Oh) A P:
+
+        dcross = (I - P^s_{t+1} Oh) A dP - dP^s_{t+1} Oh A P - P^s_{t+1} dOm_{t+1} A P
+        |dcross| <= |(I - P^s_{t+1} Oh) A| |dP| + |Oh A P| |dP^s_{t+1}| + |P^s_{t+1}| |A P| |dOm_{t+1}|
+
+    in the spectral norm (the Euclidean norm of a vector).  Returns (pp, po, mm, ml, mo, mp) and (xp, xs, xo) — the second
+    triple None without cov_next."""
+    mean, cov = filtered
+    B, N, D = mean.shape
+    P = unpack(np.asarray(cov), D)
+    lower = np.tril(unpack(np.asarray(factor), D))
+    Om = lower @ np.swapaxes(lower, -1, -2)
+    J = np.linalg.inv(np.eye(D) + P @ Om)
+    Ps = J @ P
+    h = lam - np.einsum("bnij,bnj->bni", Om, mean)
+    ms = mean + np.einsum("bnij,bnj->bni", Ps, h)
+    norm = lambda matrix: np.linalg.norm(matrix, 2, axis=(-2, -1))
+    nj, ns = norm(J), norm(Ps)
+    first = (float((nj * nj).max()), float((ns * ns).max()), float(nj.max()), float(ns.max()),
+             float((ns * np.linalg.norm(ms, axis=-1)).max()),
+             float((nj * np.linalg.norm(np.einsum("bnji,bnj->bni", J, h), axis=-1)).max()))
+    if cov_next is None:
+        return first, None
+    M = model["A"].shape[0]
+    j = np.clip(regime_next, 0, M - 1)
+    A, C, r2 = model["A"][j], model["C"][j], model["r"][j] ** 2
+    Oh = (np.zeros((B, N, D, D)) if omega_next is None else unpack(np.asarray(omega_next), D)) + \
+        (np.swapaxes(C, -1, -2) / r2[:, :, None, :]) @ C
+    Sn = unpack(np.asarray(cov_next), D)
+    V = A @ P
+    return first, (float(norm((np.eye(D) - Sn @ Oh) @ A).max()), float(norm(Oh @ V).max()), float((norm(Sn) * norm(V)).max()))
+
+
+def _dropped_amplification(omega, factor, D):
+    """(1 + |Om_KK^+ Om_KZ|)^2, the largest over the trajectories: how an error of Om reaches what the factor DROPS (the Schur
+    complement of the kept columns K in the dropped ones Z), to first order; 1 where nothing is dropped."""
+    full, lower = unpack(np.asarray(omega), D), np.tril(unpack(np.asarray(factor), D))
+    worst = 1.0
+    kept = lower[..., np.arange(D), np.arange(D)] > 0
+    for index in np.argwhere(~kept.all(axis=-1)):
+        keep = kept[tuple(index)]
+        if keep.any():
+            block = full[tuple(index)]
+            solved = np.linalg.lstsq(block[np.ix_(keep, keep)], block[np.ix_(keep, ~keep)], rcond=None)[0]
+            worst = max(worst, (1.0 + float(np.linalg.norm(solved, 2))) ** 2)
+    return worst
+
+
+def switching_state_pass(model, regimes, observations):
+    """The state smoother along GIVEN regime paths (no draws): the conditional Kalman filter forward (`switching_kalman_step`
+    under `_forced`, one particle per trajectory, no ancestors), `switching_information_pass` backward, and the combination
+    at every t < T-1 (at T-1 the smoothed moments are the filtered ones).  regimes: T x int32 [B,N]; observations: T x [B,Dy].
+
+    Returns a dict: means (T x [B,N,D]), covariances (T x [B,N,D(D+1)/2]), cross_covariances ((T-1) x [B,N,D,D], the one of
+    (t+1, t) at position t), log_likelihood [B,N] (log p(y | s_{0:T-1}): the steps' log-weights summed in time order),
+    filtered_means, filtered_covariances (T each), information (`switching_information_pass`'s), pivot_margins, flags, and
+    tolerances, propagated as `switching_pass` and `switching_information_pass` propagate theirs — how far a device run
+    whose launches stay within their bounds may lie from this one: `filtered_means`, `filtered_covariances` (T floats each,
+    `switching_pass`'s recurrences), `log_likelihood` (one float: the steps' summed, plus T u |log_likelihood| for the sums),
+    `means`, `covariances` (T floats each) and `cross_covariances` (T-1 floats): on the Euclidean norm of a trajectory's mean
+    error and the spectral norm of its (cross-)covariance error, which bound every element's.  With the factors of
+    `_combine_sensitivities`, the combination's own bound in the Frobenius norm, 1.01 for the terms of second order, tol_m,
+    tol_P the filter's and tol_lam, tol_Om the information pass's:
+
+        tol_FF[t]  = 1.01 amp tol_Om[t] + max 2 |F|_F |F bound|_F       (of F F^T, which the combination reads in place of Om:
+                                                                         `_dropped_amplification` for what the factor drops)
+        tol_Ps[t]  = 1.01 (pp tol_P[t] + po tol_FF[t]) + max |cov bound|_F
+        tol_ms[t]  = 1.01 (mm tol_m[t] + ml tol_lam[t] + mo tol_FF[t] + mp tol_P[t]) + max |mean bound|_2
+        tol_x[t]   = 1.01 (xp tol_P[t] + xs tol_Ps[t+1] + xo tol_Om[t+1]) + max |cross bound|_F      (tol_Om[T-1] = 0)."""
+    T = len(observations)
+    regimes = [np.asarray(regime).astype(np.int32) for regime in regimes]
+    D = model["A"].shape[-1]
+    frob = lambda packed: float(np.sqrt((unpack(packed, D) ** 2).sum(axis=(-2, -1))).max())
+    two = lambda vector: float(np.sqrt((vector ** 2).sum(axis=-1)).max())
+    filtered_m, filtered_p, tol_m, tol_p = [], [], [], []
+    state, flags, total, tol_total = None, 0, 0.0, 0.0
+    for t in range(T):
+        shim, forced = _forced(model, regimes[t])
+        regime, mean, cov, log_w, bits = switching_kalman_step(shim, state, None, forced, observations[t])
+        bound_m, bound_p, bound_w = switching_kalman_step_bound(shim, state, None, forced, observations[t])
+        flags |= bits
+        if t == 0:
+            tm, tp, tw = two(bound_m), frob(bound_p), float(bound_w.max())
+        else:
+            pp, mm, mp, wm, wp = _sensitivities(shim, state, None, regime, observations[t])
+            tm = 1.01 * (mm * tol_m[-1] + mp * tol_p[-1]) + two(bound_m)
+            tw = 1.01 * (wm * tol_m[-1] + wp * tol_p[-1]) + float(bound_w.max())
+            tp = 1.01 * pp * tol_p[-1] + frob(bound_p)
+        state = (regime, mean, cov)
+        total = total + log_w
+        tol_total += tw
+        filtered_m.append(mean), filtered_p.append(cov), tol_m.append(tm), tol_p.append(tp)
+    with np.errstate(invalid="ignore"):
+        tol_total += T * UNIT * float(np.nanmax(np.abs(total))) if np.isfinite(total).any() else 0.0
+    backward = switching_information_pass(model, regimes, observations)
+    flags |= backward["flags"]
+    means, covs, crosses = [None] * T, [None] * T, [None] * (T - 1)
+    tol_ms, tol_ps, tol_x = [None] * T, [None] * T, [None] * (T - 1)
+    means[T - 1], covs[T - 1], tol_ms[T - 1], tol_ps[T - 1] = filtered_m[-1], filtered_p[-1], tol_m[-1], tol_p[-1]
+    for t in range(T - 2, -1, -1):
+        om, lam, _, factor = backward["information"][t]
+        later = t + 1 < T - 1
+        omega_next = backward["information"][t + 1][0] if later else None
+        args = (model, regimes[t + 1], (filtered_m[t], filtered_p[t]), factor, lam, omega_next, covs[t + 1])
+        means[t], covs[t], crosses[t], bits = switching_smooth_combine(*args)
+        bound_m, bound_p, bound_x = switching_smooth_combine_bound(*args)
+        flags |= bits
+        with np.errstate(invalid="ignore"):
+            (pp, po, mm, ml, mo, mp), (xp, xs, xo) = _combine_sensitivities(*args)
+        _, _, _, bound_f = switching_information_step_bound(model, regimes[t + 1], None if not later else
+                                                            backward["information"][t + 1][:3], observations[t + 1])
+        tol_om, tol_lam = backward["tolerances"]["omega"][t], backward["tolerances"]["lambda"][t]
+        tol_ff = 1.01 * _dropped_amplification(om, factor, D) * tol_om + \
+            float((2.0 * np.sqrt((np.tril(unpack(factor, D)) ** 2).sum(axis=(-2, -1))) *
+                   np.sqrt((np.tril(unpack(bound_f, D)) ** 2).sum(axis=(-2, -1)))).max())
+        tol_ps[t] = 1.01 * (pp * tol_p[t] + po * tol_ff) + frob(bound_p)
+        tol_ms[t] = 1.01 * (mm * tol_m[t] + ml * tol_lam + mo * tol_ff + mp * tol_p[t]) + two(bound_m)
+        tol_x[t] = 1.01 * (xp * tol_p[t] + xs * tol_ps[t + 1] +
+                           xo * (backward["tolerances"]["omega"][t + 1] if later else 0.0)) + \
+            float(np.sqrt((bound_x ** 2).sum(axis=(-2, -1))).max())
+    return {"means": means, "covariances": covs, "cross_covariances": crosses, "log_likelihood": total,
+            "filtered_means": filtered_m, "filtered_covariances": filtered_p, "information": backward["information"],
+            "pivot_margins": backward["pivot_margins"], "flags": flags,
+            "tolerances": {"filtered_means": tol_m, "filtered_covariances": tol_p, "log_likelihood": float(tol_total),
+                           "means": tol_ms, "covariances": tol_ps, "cross_covariances": tol_x}}
+
+
+def exact_state_smoother(model, sequence, ys):
+    """(means [T,D], covariances [T,D,D], cross_covariances [T-1,D,D]) of ONE series (ys: T x [Dy]) under ONE regime sequence:
+    the dense joint Gaussian of (z_0..z_{T-1}, y_0..y_{T-1}) conditioned on the observations with plain np.linalg — the
+    independent statement of what the pass computes.  cross_covariances[t][i,l] = Cov(z_{t+1,i}, z_{t,l} | y)."""
+    T = len(sequence)
+    D, Dy = model["A"].shape[-1], model["C"].shape[-2]
+    mu, Sigma = np.zeros(T * D), np.zeros((T * D, T * D))
+    at = lambda t: slice(t * D, (t + 1) * D)
+    for t, s in enumerate(sequence):
+        if t == 0:
+            mu[at(0)], Sigma[at(0), at(0)] = model["m0"], np.diag(model["s0"] ** 2)
+            continue
+        A = model["A"][s]
+        mu[at(t)] = A @ mu[at(t - 1)] + model["b"][s]
+        Sigma[at(t), :t * D] = A @ Sigma[at(t - 1), :t * D]
+        Sigma[:t * D, at(t)] = Sigma[at(t), :t * D].T
+        Sigma[at(t), at(t)] = A @ Sigma[at(t - 1), at(t - 1)] @ A.T + np.diag(model["q"][s] ** 2)
+    H, offset, R = np.zeros((T * Dy, T * D)), np.zeros(T * Dy), np.zeros(T * Dy)
+    for t, s in enumerate(sequence):
+        rows = slice(t * Dy, (t + 1) * Dy)
+        H[rows, at(t)], offset[rows], R[rows] = model["C"][s], model["d"][s], model["r"][s] ** 2
+    y = np.concatenate([np.asarray(part, dtype=np.float64).reshape(-1) for part in ys])
+    Szy = Sigma @ H.T
+    Syy = H @ Szy + np.diag(R)
+    mean = mu + Szy @ np.linalg.solve(Syy, y - H @ mu - offset)
+    cov = Sigma - Szy @ np.linalg.solve(Syy, Szy.T)
+    return (np.stack([mean[at(t)] for t in range(T)]), np.stack([cov[at(t), at(t)] for t in range(T)]),
+            np.stack([cov[at(t + 1), at(t)] for t in range(T - 1)]) if T > 1 else np.zeros((0, D, D)))
+
+
+def exact_smoothed_state(model, ys):
+    """(E[z_t | y] [T,D], Cov[z_t | y] [T,D,D], E[z_{t+1} z_t^T | y] [T-1,D,D]) of ONE series (ys: T x [Dy]): the mixture of
+    `exact_state_smoother` over all M^T regime sequences with `exact_regime_marginals`' weights (the sequences' posterior
+    probabilities)."""
+    rows = [np.asarray(y, dtype=np.float64).reshape(1, -1) for y in ys]
+    T, M, D = len(rows), model["A"].shape[0], model["A"].shape[-1]
+    sequences = list(itertools.product(range(M), repeat=T))
+    terms = np.empty(len(sequences))
+    with np.errstate(divide="ignore"):
+        log_pi0, log_Pi = np.log(model["pi0"]), np.log(model["Pi"])
+    for position, sequence in enumerate(sequences):
+        prior = log_pi0[sequence[0]] + sum(log_Pi[a, b] for a, b in zip(sequence, sequence[1:]))
+        terms[position] = prior + _sequence_log_likelihood(model, sequence, rows)
+    weights = np.exp(terms - terms.max())
+    weights /= weights.sum()
+    first, second, lagged = np.zeros((T, D)), np.zeros((T, D, D)), np.zeros((max(T - 1, 0), D, D))
+    for weight, sequence in zip(weights, sequences):
+        if weight == 0.0:
+            continue
+        mean, cov, cross = exact_state_smoother(model, sequence, ys)
+        first += weight * mean
+        second += weight * (cov + mean[:, :, None] * mean[:, None, :])
+        if T > 1:
+            lagged += weight * (cross + mean[1:, :, None] * mean[:-1, None, :])
+    return first, second - first[:, :, None] * first[:, None, :], lagged
+
+
+def example_smooth_combine(B, N, M, D, Dy, steps=1, seed=0):
+    """(model, regime_next, filtered, factor, lam, omega_next, cov_next) of one combination at a time t: `example_model`, the
+    information of time t after `steps` information steps from the zeros of the last timestep (steps = 1: t+1 = T-1 and
+    omega_next None; steps = 2: with Dy < D the Om of time t+1 is rank-deficient), a standard-normal filtered mean and
+    filtered and next smoothed covariances F F^T / D + 0.1 I."""
+    model, regime_next, info, y, _, _ = example_backward_step(B, 1, N, M, D, Dy, steps=steps, seed=seed)
+    _, lam, _, factor, _, _ = switching_information_step(model, regime_next, info, y)
+    rng = np.random.default_rng([seed, B, N, M, D, Dy, 36])
+
+    def covariance():
+        root = rng.standard_normal((B, N, D, D))
+        return np.ascontiguousarray(pack(root @ np.swapaxes(root, -1, -2) / D + 0.1 * np.eye(D)))
+
+    filtered = (rng.standard_normal((B, N, D)), covariance())
+    return model, regime_next, filtered, factor, lam, None if info is None else info[0], covariance()

@@ -11,7 +11,8 @@ from the enumeration of all M^T regime sequences.  With --lookahead the filter i
 resamples on the exact p(y_t | history) and draws the regime from its exact posterior (kernels K32 and K33).  With
 --smooth the stored systems are smoothed by Rao-Blackwellised backward simulation (`switching_backward_simulate`, kernels
 K34 and K35) and the accuracy of the most probable SMOOTHED regime, which has seen the whole series, is printed beside the
-filtered one.
+filtered one; then the continuous state is smoothed along the drawn trajectories (`switching_state_smooth`, kernel K36) and
+the error of the smoothed state mean is printed beside the filtered one's.
 """
 import argparse
 import os
@@ -69,6 +70,9 @@ def main():
         guess = smoothed["smoothed_regime_probabilities"].argmax(dim=-1)
         print("smoothed regime = true regime {:.1%} of the time (filtered: {:.1%}); {} backward trajectories per series".format(
             (guess == torch.stack(regimes)).double().mean().item(), accuracy, smoothed["regimes"][0].size(1)))
+        state = rao_blackwell.switching_state_smooth(observations, model, smoothed["regimes"])
+        print("RMSE of the smoothed state mean {:.3f} (filtered: {:.3f})".format(
+            (state["smoothed_mean"] - torch.stack(states)).pow(2).mean().sqrt().item(), error))
     short = [y[:1] for y in observations[:args.short]]
     ops = {name: value.cpu().numpy() for name, value in model.operands().items()}
     exact = contract.exact_log_likelihood(ops, [y.cpu().numpy() for y in short])[0]

@@ -81,7 +81,9 @@ extern "C" {
  *                aesmc_switching_lookahead, aesmc_switching_kalman_draw (K32, K33: the exact first-stage weights and regime
  *                posteriors of that model, and K31's step with the regime drawn from them — its fully adapted filter);
  *                aesmc_switching_information_step, aesmc_switching_backward_scores (K34, K35: Rao-Blackwellised backward
- *                simulation over the stored systems of either filter — its smoother).
+ *                simulation over the stored systems of either filter — its smoother);
+ *                aesmc_switching_smooth_combine (K36: the smoothed moments and lag-one cross-covariance of the continuous
+ *                state along a regime trajectory, from the conditional filter and K34 — the two-filter state smoother).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -763,6 +765,38 @@ int aesmc_switching_backward_scores(const double *log_Pi, const int32_t *regime_
                                     const double *lambda, const int32_t *regime, const double *mean, const double *cov,
                                     const double *log_w, double *scores, int32_t *flags, int64_t B, int64_t K, int64_t N,
                                     int64_t M, int64_t D, void *stream);
+
+/* K36 — the two-filter combination of the state smoother of the same model (Fong, Godsill, Doucet & West 2002; Lindsten et
+ * al. 2016).  Along a regime trajectory the model is linear-Gaussian: trajectory (b,n) has at time t the conditional Kalman
+ * filter's mean m and packed covariance P (K31 under its regimes) and K34's F and lam of time t (Om = F F^T).  The call
+ * writes the smoothed mean and packed covariance of z_t given ALL observations and the trajectory's regimes and, on
+ * request, the lag-one cross-covariance.  No predicted covariance is inverted: q = 0 components and P = 0 are fine.
+ * Chains as K34's (float64, every sum ONE chain of fused multiply-adds in ascending index order from the value named first):
+ *   t_i  = 0 + sum_{l>=i} F_li m_l;   h_l = lam_l - sum_{i<=l} F_li t_i                                        (K35's t, h)
+ *   W_il = 0 + sum_{c>=i} F_ci P_cl;  Lam_ij = (i == j) + sum_{l>=j} W_il F_lj,  j <= i                         (K35's W, Lam)
+ *   G = chol(Lam) as K31's (the pivots are at least 1: no test, no flag);  U_il = (W_il - sum_{c<i} G_ic U_cl) / G_ii
+ *   cov_out_pq  = P_pq - sum_i U_ip U_iq,  p >= q
+ *   mean_out_p  = m_p + sum_l cov_out_pl h_l
+ * and with cross_out, j = regime_next[b,n] (the trajectory's regime at t+1), r2_i = r_j[i]^2:
+ *   rho_i = 1 / r2_i;  Gc_il = C_j[i,l] rho_i;  Oh_pq = omega_next_pq + sum_i Gc_ip C_j[i,q]                    (K34's Oh)
+ *   V_il  = 0 + sum_c A_j[i,c] P_cl;   Y_pl = 0 + sum_q Oh_pq V_ql
+ *   cross_out[b,n,i,l] = V_il - sum_p cov_next_ip Y_pl           = Cov(z_{t+1,i}, z_{t,l} | y_{0:T-1}, s_{0:T-1})
+ * (divisions by a pivot are one reciprocal per pivot and a product, as K34's).
+ *   mean float64 [B,N,D], cov float64 [B,N,D(D+1)/2], factor float64 [B,N,D(D+1)/2], lambda float64 [B,N,D]: of time t
+ *   regime_next int32 [B,N];  omega_next float64 [B,N,D(D+1)/2]: K34's omega_out of time t+1, NULL at t+1 = T-1 (zeros);
+ *   cov_next float64 [B,N,D(D+1)/2]: this call's cov_out of time t+1 (at t+1 = T-1 the filter's own covariance)
+ *   mean_out, cov_out as mean, cov, out of place;  cross_out float64 [B,N,D,D] row-major, or NULL
+ * Only the cross-covariance reads model (A, C, r of it; its D must be the argument D), regime_next, omega_next and cov_next:
+ * with cross_out NULL all four MUST be NULL (an invalid argument otherwise: who hands them over expects a cross-covariance),
+ * nothing of them is read and no regime is checked.  With cross_out a regime outside [0, M) writes NaN to the trajectory's
+ * three outputs and raises AESMC_FLAG_INDEX_OUT_OF_RANGE.  NULL (but omega_next, flags, and the four above) or misaligned
+ * pointers, negative sizes, D (with cross_out: M, Dy) below 1 and an output that is an input or another output return
+ * AESMC_ERR_INVALID_ARGUMENT; B N == 0 is a no-op; D (with cross_out: Dy, M) above the limits of K31 or B N D^2 beyond 32-bit
+ * element arithmetic return AESMC_ERR_UNSUPPORTED.  Every check runs before any launch.  `flags` may be NULL. */
+int aesmc_switching_smooth_combine(const aesmc_switching_model *model, const int32_t *regime_next, const double *mean,
+                                   const double *cov, const double *factor, const double *lambda,
+                                   const double *omega_next, const double *cov_next, double *mean_out, double *cov_out,
+                                   double *cross_out, int32_t *flags, int64_t B, int64_t N, int64_t D, void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *

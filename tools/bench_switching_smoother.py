@@ -1,5 +1,6 @@
 """K34 (aesmc_switching_information_step) and K35 (aesmc_switching_backward_scores) alone, beside K21's draw on the scores
-(rows [B N, K], one trajectory each) and, in the same run, the batched `torch.linalg` composition of the same scores: timed
+(rows [B N, K], one trajectory each), K36 (aesmc_switching_smooth_combine, the state smoother's launch per timestep, over the
+same B N trajectories as K34) without and with the cross-covariance and, in the same run, the batched `torch.linalg` composition of the same scores: timed
 warm between HIP events, the median per call with the spread.  Then, on `contract.sticky_example` (sticky regimes,
 well-separated emissions), how often the most probable smoothed regime is the true one beside the filtered one, and the
 device time of the whole backward pass beside the filter's.
@@ -87,6 +88,13 @@ def kernels(lines, B, K, N, M, D, Dy):
     difference = float((scores - composed).abs().max())
     flags = k.read_flags(dev)
     t_info = timed(lambda: k.switching_information_step(ops, regime_next, info, y), 3, 10, 8)
+    root = torch.randn(2, B, N, D, D, generator=gen, device=dev, dtype=torch.float64)
+    packed = (root @ root.transpose(-1, -2) / D + 0.1 * torch.eye(D, device=dev, dtype=torch.float64))[..., rows, cols]
+    moments, cov_next = (torch.randn(B, N, D, generator=gen, device=dev, dtype=torch.float64), packed[0].contiguous()), \
+        packed[1].contiguous()
+    t_combine = timed(lambda: k.switching_smooth_combine(None, None, moments, F, lam), 3, 10, 8)
+    t_cross = timed(lambda: k.switching_smooth_combine(ops, regime_next, moments, F, lam, info[0], cov_next), 3, 10, 8)
+    flags |= k.read_flags(dev)
     t_score = timed(lambda: k.switching_backward_scores(log_Pi, regime_next, F, lam, state, log_w), 3, 10, 8)
     t_draw = timed(lambda: k.backward_sample(scores.reshape(B * N, K), None, None, None, u), 3, 10, 8)
     t_torch = timed(lambda: composed_scores(log_Pi, regime_next, F, lam, state, log_w, D), 2, 5, 2)
@@ -94,6 +102,10 @@ def kernels(lines, B, K, N, M, D, Dy):
     lines.append("B={} K={} N={} M={} D={} Dy={} (flags {}; largest |K35 - torch.linalg| {:.2e})".format(
         B, K, N, M, D, Dy, flags, difference))
     lines.append("  {:<34} {:10.1f} ({:.1f} .. {:.1f}) us".format("K34 information step", *t_info))
+    lines.append("  {:<34} {:10.1f} ({:.1f} .. {:.1f}) us   {:.1f} times K34".format(
+        "K36 smoothed moments", *t_combine, t_combine[0] / t_info[0]))
+    lines.append("  {:<34} {:10.1f} ({:.1f} .. {:.1f}) us   {:.1f} times K34".format(
+        "K36 with the cross-covariance", *t_cross, t_cross[0] / t_info[0]))
     lines.append("  {:<34} {:10.1f} ({:.1f} .. {:.1f}) us   {:.3f} ns per pair, {:.1f} MB of scores written".format(
         "K35 pair scores", *t_score, t_score[0] * 1e3 / pairs, 8 * pairs / 1e6))
     lines.append("  {:<34} {:10.1f} ({:.1f} .. {:.1f}) us".format("K21 draw, rows [B N, K]", *t_draw))
