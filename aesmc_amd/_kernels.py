@@ -2701,6 +2701,120 @@ class HipKernels:
                      name="switching_smooth_combine")
         return out_mean, out_cov, out_cross
 
+    # ---- K37, K38 ------------------------------------------------------------------------------
+    def switching_conditional_max_particles(self, latent_dim):
+        """The largest K of `switching_conditional_ancestor_index` for a latent of D values, as the library exports it (0
+        for a D it does not take)."""
+        return int(self._lib.aesmc_switching_conditional_max_particles(int(latent_dim)))
+
+    def switching_conditional_covers(self, observation, num_regimes, latent_dim, observation_dim, num_particles):
+        """Whether `switching_conditional_ancestor_index` and `switching_kalman_conditional_step` take a conditional sweep
+        like this: what `switching_covers` asks, and at most `switching_conditional_max_particles(latent_dim)` particles."""
+        return self.switching_covers(observation, num_regimes, latent_dim, observation_dim, num_particles) and \
+            num_particles <= self.switching_conditional_max_particles(latent_dim)
+
+    def switching_conditional_ancestor_index(self, log_w, u, log_Pi, regime_next, factor, lam, state):
+        """The ancestors of one step of a conditional Rao-Blackwellised filter (aesmc_switching_conditional_ancestor_index,
+        K37): log_w, u float64 [B,K]; log_Pi float64 [M,M]; regime_next int32 [B] (the reference's regime at the step being
+        entered); factor [B,D(D+1)/2] and lam [B,D]: `switching_information_step`'s with one trajectory per row, squeezed, or
+        both None (no ancestor sampling: slot K-1 keeps ancestor K-1); state: the stored (regime, mean, cov) the weights
+        belong to.  Slots 0 .. K-2 draw multinomial ancestors as `conditional_ancestor_index` does, slot K-1 from
+        `switching_backward_scores`' scores of that one trajectory.  Returns idx int64 [B,K]."""
+        _require_hip(log_w, "log_weight")
+        _require_hip(u, "uniforms")
+        device = log_w.device
+        if log_w.dim() != 2 or log_w.dtype != torch.float64:
+            raise ValueError("aesmc_amd: log_weight must be [batch_size, num_particles] float64")
+        B, K = log_w.shape
+        if tuple(u.shape) != (B, K) or u.dtype != torch.float64 or u.device != device:
+            raise ValueError("aesmc_amd: uniforms must be [{}, {}] float64 on {}".format(B, K, device))
+        _require_hip(log_Pi, "log_Pi")
+        if log_Pi.dim() != 2 or log_Pi.size(0) != log_Pi.size(1) or log_Pi.dtype != torch.float64 or log_Pi.device != device:
+            raise ValueError("aesmc_amd: log_Pi must be [M, M] float64 on {}".format(device))
+        M = log_Pi.size(0)
+        D = state[1].size(-1) if torch.is_tensor(state[1]) and state[1].dim() == 3 else 0
+        TD = D * (D + 1) // 2
+        regime, mean, cov = self._switching_state(state, B, K, D, device)
+        _require_hip(regime_next, "regime_next")
+        if tuple(regime_next.shape) != (B,) or regime_next.dtype != torch.int32 or regime_next.device != device:
+            raise ValueError("aesmc_amd: regime_next must be [{}] int32 on {}".format(B, device))
+        if (factor is None) != (lam is None):
+            raise ValueError("aesmc_amd: factor and lam come together")
+        if factor is not None:
+            for tensor, shape, what in ((factor, (B, TD), "factor"), (lam, (B, D), "lam")):
+                _require_hip(tensor, what)
+                if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                    raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
+            factor, lam = factor.contiguous(), lam.contiguous()
+        max_d, _, max_m = self.switching_limits()
+        if not (1 <= D <= max_d and 1 <= M <= max_m and K <= self.switching_conditional_max_particles(D) and
+                B * K <= 0x7fffffff // (max_d * (max_d + 1) // 2)):
+            raise ValueError("aesmc_amd: switching_conditional_ancestor_index does not take these operands (see "
+                             "switching_conditional_covers)")
+        log_w, u, log_Pi, regime_next = log_w.contiguous(), u.contiguous(), log_Pi.contiguous(), regime_next.contiguous()
+        idx = torch.empty((B, K), dtype=torch.int64, device=device)
+        if idx.numel() == 0:
+            return idx
+        self._launch(device, self._lib.aesmc_switching_conditional_ancestor_index,
+                     (_ptr(log_w), _ptr(u), _ptr(log_Pi), _ptr(regime_next), _ptr(factor), _ptr(lam), _ptr(regime),
+                      _ptr(mean), _ptr(cov), _ptr(idx), _ptr(self.flags(device)), B, K, M, D, self._stream(log_w)),
+                     lambda: B * K * 24 + (B * K * (4 + 8 * (D + TD)) + B * (4 + 8 * (TD + D)) + 8 * M * M
+                                           if factor is not None else 0),
+                     (log_w, u, log_Pi, regime_next, factor, lam, regime, mean, cov, idx),
+                     name="switching_conditional_ancestor_index")
+        return idx
+
+    def switching_kalman_conditional_step(self, model, state, index, uniforms, pinned_regime, observation):
+        """`switching_kalman_step` with the regime of slot K-1 pinned (aesmc_switching_kalman_conditional_step, K38):
+        pinned_regime int32 [B], the regime particle (b, K-1) takes in place of its draw.  Returns (regime, mean, cov,
+        log_weight [B,K] float64), new tensors; flags and NaNs as `switching_kalman_step`'s, a pinned regime outside [0, M)
+        as a stored one."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        _require_hip(uniforms, "regime uniforms")
+        device = observation.device
+        if uniforms.dim() != 2 or uniforms.dtype != torch.float64 or uniforms.device != device:
+            raise ValueError("aesmc_amd: regime uniforms must be [batch_size, num_particles] float64 on {}".format(device))
+        B, K = uniforms.shape
+        block, M, D, Dy = self._switching_block(model, device)
+        TD = D * (D + 1) // 2
+        if tuple(observation.shape) != (B, Dy):
+            raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
+        if not self.switching_covers(observation, M, D, Dy, K):
+            raise ValueError("aesmc_amd: switching_kalman_conditional_step does not take these operands (see "
+                             "switching_covers)")
+        _require_hip(pinned_regime, "pinned_regime")
+        if tuple(pinned_regime.shape) != (B,) or pinned_regime.dtype != torch.int32 or pinned_regime.device != device:
+            raise ValueError("aesmc_amd: pinned_regime must be [{}] int32 on {}".format(B, device))
+        pinned_regime = pinned_regime.contiguous()
+        if state is not None:
+            regime, mean, cov = self._switching_state(state, B, K, D, device)
+            if index is not None:
+                index = as_index(index)
+                if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != device:
+                    raise ValueError("aesmc_amd: index must be [{}, {}] int64 on {}".format(B, K, device))
+                index = index.contiguous()
+        else:
+            regime = mean = cov = index = None
+        uniforms, observation = uniforms.contiguous(), observation.contiguous()
+        out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
+        out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
+        out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
+        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
+        if log_weight.numel() == 0:
+            return out_regime, out_mean, out_cov, log_weight
+        per_particle = 8 + 2 * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) if state is not None else \
+            8 + (4 + 8 * D + 8 * TD) + 8
+        self._launch(device, self._lib.aesmc_switching_kalman_conditional_step,
+                     (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
+                      _ptr(pinned_regime), _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov),
+                      _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
+                     lambda: B * K * per_particle + 4 * B + B * Dy * observation.element_size() +
+                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                     (model, regime, mean, cov, index, uniforms, pinned_regime, observation, out_regime, out_mean, out_cov,
+                      log_weight, block), name="switching_kalman_conditional_step")
+        return out_regime, out_mean, out_cov, log_weight
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 

@@ -138,6 +138,9 @@ SIGNATURES = {
     "aesmc_switching_information_step": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 10 + [_i64, _i64, _vp]),
     "aesmc_switching_backward_scores": (_i32, [_vp] * 10 + [_i64] * 5 + [_vp]),
     "aesmc_switching_smooth_combine": (_i32, [ctypes.POINTER(SwitchingModel)] + [_vp] * 11 + [_i64] * 3 + [_vp]),
+    "aesmc_switching_conditional_max_particles": (_i64, [_i64]),
+    "aesmc_switching_conditional_ancestor_index": (_i32, [_vp] * 11 + [_i64] * 4 + [_vp]),
+    "aesmc_switching_kalman_conditional_step": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 12 + [_i64, _i64, _vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

@@ -21,6 +21,7 @@
 //
 // LDS: 8 K bytes per array, two arrays when there is a transition term, and 4.4 KiB besides: 132 KiB at the cap K = 8192.
 #include "ancestor_index.hpp"
+#include "conditional_cdf.hpp"
 #include "pairwise_gaussian.hpp"
 
 namespace aesmc {
@@ -44,39 +45,6 @@ template <typename T> struct ConditionalArgs {
 static inline size_t conditional_lds_bytes(int64_t K, int64_t D) {
   return ((size_t)K * (D > 0 ? 2 : 1) + 2 * kCondMaxDim + 2 * kCondMaxWaves + 2) * sizeof(double) +
          2 * kCondMaxWaves * sizeof(int);
-}
-
-// c[j] <- c[0] + ... + c[j], added one at a time in this order (the contract's sum), by the calling lane; returns the total.
-// Runs of eight are loaded ahead of the additions that wait for one another.
-__device__ __forceinline__ double running_sum_in_place(double *c, int K) {
-  constexpr int kRun = 8;
-  double run = 0.0;
-  int k = 0;
-  for (; k + kRun <= K; k += kRun) {
-    double w[kRun];
-#pragma unroll
-    for (int i = 0; i < kRun; ++i) w[i] = c[k + i];
-#pragma unroll
-    for (int i = 0; i < kRun; ++i) {
-      run += w[i];
-      c[k + i] = run;
-    }
-  }
-  for (; k < K; ++k) {
-    run += c[k];
-    c[k] = run;
-  }
-  return run;
-}
-
-// #{ j < n : c[j] <= thr } for non-decreasing c: a fixed number of probes, strides top, top / 2, ..., 1
-__device__ __forceinline__ int count_not_above(const double *c, int n, double thr, int top) {
-  int pos = 0;
-  for (int step = top; step > 0; step >>= 1) {
-    const int probe = pos + step;
-    if (probe <= n && c[probe - 1] <= thr) pos = probe;
-  }
-  return pos;
 }
 
 template <typename T>
@@ -203,11 +171,7 @@ static int launch_conditional_ancestor_index(const void *log_w, const double *u,
   a.idx = out_idx;
   a.flags = flags;
   a.K = (int)K, a.D = (int)D;
-  a.top = 0;
-  if (K > 1) {
-    a.top = 1;
-    while ((int64_t)a.top * 2 < K) a.top *= 2;      // 2^(ceil(log2 K) - 1)
-  }
+  a.top = bisection_top(K);
   // a lane per particle up to 256 lanes, then four particles per lane up to 1024 lanes (the scores are latency-bound
   // reads of `loc`: a long row wants the wavefronts in flight)
   int64_t want = K <= 256 ? K : (K / 4 > 256 ? K / 4 : 256);

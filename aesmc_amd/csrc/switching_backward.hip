@@ -16,16 +16,17 @@
 //               all that is live.  At DP = 8 that is still 36 + 36 + 8 + 8 + 8 + 8 float64 = 208 registers before addresses
 //               and temporaries, so the 8-wide instantiation keeps P in LDS in K31's [element][lane] layout (SkCov: 72 KB
 //               per workgroup, two workgroups per compute unit).  About D^3 float64 multiply-adds per pair;
-//   chains      every value is ONE chain of float64 __builtin_fma in the header's order; the triangular sums skip the
+//   chains      (switching_score.hpp) every value is ONE chain of float64 __builtin_fma in the header's order; the triangular sums skip the
 //               structural zeros of F, a padded term multiplies a zero by a zero.
 //
 // Compiler's resource report (-Rpass-analysis=kernel-resource-usage, gfx950, 256 lanes per workgroup):
 //   <DP>  VGPRs  AGPRs  scratch B/lane  waves/SIMD
 //   <2>      58      0        0             8
 //   <4>     126      0        0             4
-//   <8>     174      0        0             2       P in LDS
+//   <8>     200      0        0             2       P in LDS
+// (the score itself is switching_pair_score of switching_score.hpp, which K37 calls too)
 // Measured (profiles/switching_smoother.txt, B = 64, K = 1024, N = 64: 4.2 million pairs): 98 us at D = 4, 342 us at D = 8.
-#include "switching_kalman.hpp"
+#include "switching_score.hpp"
 
 namespace aesmc {
 
@@ -105,96 +106,7 @@ __global__ __launch_bounds__(kSkBlock) void switching_backward_kernel(const Back
   const bool weighted = a.log_w != nullptr;
 
   for (int nn = 0; nn < count; ++nn) {
-    const double *F = Ft + nn * TP, *lam = lt + nn * DP;      // F_ik, i >= k, at sk_tri(i, k)
-    // ---- t = F^T m, h = lam - F t, the two quadratic terms in m ---------------------------------------------------------------
-    double t[DP], h[DP], mq = 0.0, lm = 0.0;
-#pragma unroll
-    for (int i = 0; i < DP; ++i) {
-      double acc = 0.0;
-#pragma unroll
-      for (int l = i; l < DP; ++l) acc = __builtin_fma(F[sk_tri(l, i)], m[l], acc);
-      t[i] = acc;
-    }
-#pragma unroll
-    for (int i = 0; i < DP; ++i) mq = __builtin_fma(t[i], t[i], mq);
-#pragma unroll
-    for (int l = 0; l < DP; ++l) {
-      double acc = lam[l];
-#pragma unroll
-      for (int i = 0; i <= l; ++i) acc = __builtin_fma(-F[sk_tri(l, i)], t[i], acc);
-      h[l] = acc;
-      lm = __builtin_fma(lam[l], m[l], lm);
-    }
-    // ---- h^T P h -----------------------------------------------------------------------------------------------------------------
-    double hph = 0.0;
-#pragma unroll
-    for (int c = 0; c < DP; ++c) {
-      double acc = 0.0;
-#pragma unroll
-      for (int l = 0; l < DP; ++l) acc = __builtin_fma(P.get(sk_tri(c, l)), h[l], acc);
-      hph = __builtin_fma(h[c], acc, hph);
-    }
-    // ---- W = Phi P row by row: row i gives v_i and row i of Lam = I + W Phi^T ------------------------------------------------------
-    double v[DP], Lam[TP];
-#pragma unroll
-    for (int i = 0; i < DP; ++i) {
-      SK_REREAD_LDS();
-      double W[DP];
-#pragma unroll
-      for (int l = 0; l < DP; ++l) {
-        double acc = 0.0;
-#pragma unroll
-        for (int c = i; c < DP; ++c) acc = __builtin_fma(F[sk_tri(c, i)], P.get(sk_tri(c, l)), acc);
-        W[l] = acc;
-      }
-      double acc = 0.0;
-#pragma unroll
-      for (int l = 0; l < DP; ++l) acc = __builtin_fma(W[l], h[l], acc);
-      v[i] = acc;
-#pragma unroll
-      for (int j = 0; j <= i; ++j) {
-        double w = i == j ? 1.0 : 0.0;
-#pragma unroll
-        for (int l = j; l < DP; ++l) w = __builtin_fma(W[l], F[sk_tri(l, j)], w);
-        Lam[sk_tri(i, j)] = w;
-      }
-    }
-    // ---- G = chol(Lam) in place, x = G^-1 v in step ---------------------------------------------------------------------------------
-    double inv[DP], log_det = 0.0;
-#pragma unroll
-    for (int j = 0; j < DP; ++j) {
-      double pivot = Lam[sk_tri(j, j)];
-#pragma unroll
-      for (int c = 0; c < j; ++c) pivot = __builtin_fma(-Lam[sk_tri(j, c)], Lam[sk_tri(j, c)], pivot);
-      const double gjj = __builtin_sqrt(pivot);
-      Lam[sk_tri(j, j)] = gjj;
-      inv[j] = 1.0 / gjj;
-      log_det += ::log(gjj);
-#pragma unroll
-      for (int i = j + 1; i < DP; ++i) {
-        double acc = Lam[sk_tri(i, j)];
-#pragma unroll
-        for (int c = 0; c < j; ++c) acc = __builtin_fma(-Lam[sk_tri(i, c)], Lam[sk_tri(j, c)], acc);
-        Lam[sk_tri(i, j)] = acc * inv[j];
-      }
-    }
-    double xq = 0.0;
-#pragma unroll
-    for (int i = 0; i < DP; ++i) {
-      double acc = v[i];
-#pragma unroll
-      for (int c = 0; c < i; ++c) acc = __builtin_fma(-Lam[sk_tri(i, c)], v[c], acc);
-      v[i] = acc * inv[i];
-      xq = __builtin_fma(v[i], v[i], xq);
-    }
-    // ---- the score ---------------------------------------------------------------------------------------------------------------
-    const double lp = pt[nn * M + s];
-    double score = weighted ? lw + lp : lp;
-    score = score + lm;
-    score = __builtin_fma(-0.5, mq, score);
-    score = __builtin_fma(0.5, hph - xq, score);
-    score = score - log_det;
-    out[(int64_t)nn * a.K] = lp == Num<double>::neg_inf() ? lp : score;
+    out[(int64_t)nn * a.K] = switching_pair_score<DP>(Ft + nn * TP, lt + nn * DP, m, P, pt + nn * M + s, lw, weighted);
   }
 }
 

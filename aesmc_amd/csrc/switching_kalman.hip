@@ -5,6 +5,10 @@
 // position the regime is drawn instead of from the chain's rows (the fully adapted filter: switching_lookahead.hip writes
 // those rows).  NULL for K31, whose arithmetic and order it does not touch.
 //
+// And aesmc_switching_kalman_conditional_step (K38), the step of a conditional sweep (particle Gibbs on the regimes): one more
+// pointer, `pinned_regime` [B], whose entry slot K-1 of the row takes as its regime in place of the draw — the reference
+// path's.  NULL for K31 and K33; everything after the regime is chosen is the same code for every slot.
+//
 // Only the regimes are sampled.  Particle k of batch row b carries (s, m, P): its regime and the exact Kalman mean and
 // covariance of the continuous state given its regime history.  One launch, per particle: the gather through the ancestors,
 // the inverse-CDF regime draw, the Kalman predict, the Dy x Dy Cholesky factor of the innovation covariance, two triangular
@@ -48,6 +52,7 @@ namespace aesmc {
 struct SwitchingArgs {
   const double *cdf;                // [M,M] (later steps) or [M] (step 0); not read when particle_cdf is given
   const double *particle_cdf;       // K33: [B,K,M], the row of the ancestor's position; NULL: K31
+  const int32_t *pinned_regime;     // K38: [B], the regime of slot K-1; NULL: K31, K33
   const double *m0, *s0;            // [D]
   const double *A, *b, *q, *C, *d, *r;
   const int32_t *regime_in;         // NULL: step 0
@@ -106,6 +111,18 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
   const double *row = a.particle_cdf != nullptr ? a.particle_cdf + src * M : cdf + (later ? s_prev * M : 0);
   int s = 0;
   for (int i = 0; i < M - 1; ++i) s += row[i] <= u ? 1 : 0;
+  if (a.pinned_regime != nullptr && k == (int64_t)a.K - 1) {      // K38: the pinned slot takes the reference's regime
+    s = a.pinned_regime[b];
+    if (s < 0 || s >= M) {      // (as a stored regime outside [0, M))
+      raise_flag(a.flags, AESMC_FLAG_INDEX_OUT_OF_RANGE);
+      const double nan = Num<double>::nan();
+      a.regime_out[n] = 0;
+      a.log_weight[n] = nan;
+      for (int i = 0; i < D; ++i) a.mean_out[n * D + i] = nan;
+      for (int e = 0; e < TD; ++e) a.cov_out[n * TD + e] = nan;
+      return;
+    }
+  }
 
   const double *Am = mdl + s * kPer, *bv = Am + DP * DP, *q2 = bv + DP, *Cm = q2 + DP, *dv = Cm + DYP * DP, *r2 = dv + DYP;
 
@@ -290,13 +307,16 @@ extern "C" int64_t aesmc_switching_max_regimes(void) { return aesmc::kSkMaxRegim
 
 namespace aesmc {
 
-// K31 (particle_cdf NULL, `draw` false) and K33 (`draw`: the regime from particle_cdf [B,K,M], the model's own cumulative
-// rows not read): one set of checks, one launch
-static int sk_step(bool draw, int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+// K31 (particle_cdf NULL, `draw` false), K33 (`draw`: the regime from particle_cdf [B,K,M], the model's own cumulative
+// rows not read) and K38 (`pinned`: pinned_regime [B] given): one set of checks, one launch
+static int sk_step(bool draw, bool pinned, int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
                    const double *mean_in, const double *cov_in, const int64_t *idx, const double *uniforms,
-                   const double *particle_cdf, const void *y, int32_t *regime_out, double *mean_out, double *cov_out,
-                   double *log_weight, int32_t *flags, int64_t B, int64_t K, void *stream) {
+                   const double *particle_cdf, const int32_t *pinned_regime, const void *y, int32_t *regime_out,
+                   double *mean_out, double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
+                   void *stream) {
   if (draw && (particle_cdf == nullptr || !sk_aligned(particle_cdf, 8))) return AESMC_ERR_INVALID_ARGUMENT;
+  if (pinned && (pinned_regime == nullptr || !sk_aligned(pinned_regime, 4) || pinned_regime == regime_out))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (model == nullptr || uniforms == nullptr || y == nullptr || regime_out == nullptr || mean_out == nullptr ||
       cov_out == nullptr || log_weight == nullptr || B < 0 || K < 0)
     return AESMC_ERR_INVALID_ARGUMENT;
@@ -323,6 +343,7 @@ static int sk_step(bool draw, int y_dtype, const aesmc_switching_model *model, c
   SwitchingArgs a;
   a.cdf = draw ? nullptr : later ? model->cdf : model->cdf0;
   a.particle_cdf = draw ? particle_cdf : nullptr;
+  a.pinned_regime = pinned ? pinned_regime : nullptr;
   a.m0 = model->m0, a.s0 = model->s0;
   a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
   a.regime_in = regime_in, a.mean_in = mean_in, a.cov_in = cov_in;
@@ -350,8 +371,8 @@ extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_mo
                                            const double *uniforms, const void *y, int32_t *regime_out, double *mean_out,
                                            double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
                                            void *stream) {
-  return aesmc::sk_step(false, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, y, regime_out, mean_out,
-                        cov_out, log_weight, flags, B, K, stream);
+  return aesmc::sk_step(false, false, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, nullptr, y,
+                        regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
 }
 
 extern "C" int aesmc_switching_kalman_draw(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
@@ -359,6 +380,16 @@ extern "C" int aesmc_switching_kalman_draw(int y_dtype, const aesmc_switching_mo
                                            const double *uniforms, const double *particle_cdf, const void *y,
                                            int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
                                            int32_t *flags, int64_t B, int64_t K, void *stream) {
-  return aesmc::sk_step(true, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, particle_cdf, y, regime_out,
-                        mean_out, cov_out, log_weight, flags, B, K, stream);
+  return aesmc::sk_step(true, false, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, particle_cdf, nullptr, y,
+                        regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
+}
+
+extern "C" int aesmc_switching_kalman_conditional_step(int y_dtype, const aesmc_switching_model *model,
+                                                       const int32_t *regime_in, const double *mean_in, const double *cov_in,
+                                                       const int64_t *idx, const double *uniforms,
+                                                       const int32_t *pinned_regime, const void *y, int32_t *regime_out,
+                                                       double *mean_out, double *cov_out, double *log_weight, int32_t *flags,
+                                                       int64_t B, int64_t K, void *stream) {
+  return aesmc::sk_step(false, true, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, pinned_regime, y,
+                        regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
 }

@@ -19,16 +19,16 @@ __host__ __device__ constexpr bool sk_cov_in_lds(int dp) { return dp == 8; }
 __host__ __device__ constexpr int sk_tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
 // A lane's packed predicted covariance P-: in registers, or (the 8-wide instantiations, which would spill) in LDS in an
-// [element][lane] layout — consecutive lanes on consecutive banks, no conflicts
-template <int TP, bool InLds> struct SkCov {
+// [element][lane] layout — consecutive lanes on consecutive banks, no conflicts; Lanes: the workgroup's size (K37 has two)
+template <int TP, bool InLds, int Lanes = kSkBlock> struct SkCov {
   double reg[InLds ? 1 : TP];
   double *lds;
   __device__ __forceinline__ double get(int e) const {
-    if constexpr (InLds) return lds[e * kSkBlock];
+    if constexpr (InLds) return lds[e * Lanes];
     else return reg[e];
   }
   __device__ __forceinline__ void set(int e, double v) {
-    if constexpr (InLds) lds[e * kSkBlock] = v;
+    if constexpr (InLds) lds[e * Lanes] = v;
     else reg[e] = v;
   }
 };

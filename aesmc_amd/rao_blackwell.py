@@ -48,6 +48,15 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                factors I + F^T P F (pivots at least 1) and never a predicted covariance — q = 0 components
                                and P = 0 are fine where an RTS step would divide by a singular matrix
     switching_smooth_states    a filter, the backward simulation, then that (examples/slds_em.py: Monte Carlo EM on it)
+    conditional_switching_filter   one sweep of particle Gibbs with ancestor sampling on the regimes (Andrieu, Doucet &
+                               Holenstein 2010; Whiteley, Andrieu & Doucet 2010; Lindsten et al. 2016): a conditional
+                               Rao-Blackwellised filter whose last slot carries a reference regime path — a Markov kernel on
+                               paths that leaves p(s_{0:T-1} | y) invariant for ANY number of particles, O(K) per step where the
+                               smoother above costs O(N K).  Backwards K34 along the reference; per step K37
+                               (`aesmc_switching_conditional_ancestor_index`: K26 with the pinned slot scored by K35's integral)
+                               and K38 (`aesmc_switching_kalman_conditional_step`: K31 with that slot's regime pinned)
+    switching_particle_gibbs   the chain of such sweeps; its paths are what `switching_state_smooth` takes
+                               (examples/slds_gibbs.py: Gibbs over Pi with Dirichlet rows)
 
 The reference has no counterpart; this module adds to its interface and changes none of it.
 """
@@ -735,6 +744,167 @@ def switching_smooth_states(observations, model, num_particles, num_trajectories
     out.update(switching_state_smooth(observations, model, out["regimes"], return_cross_moments=True,
                                       return_trajectories=return_trajectories))
     return out, filtered["log_marginal_likelihood"]
+
+
+def conditional_switching_filter(observations, model, num_particles, reference, ancestor_sampling=True, uniforms=None,
+                                 regime_uniforms=None, return_particles=False):
+    """One sweep of particle Gibbs on the regimes of a `SwitchingLinearGaussian`: a Rao-Blackwellised conditional particle
+    filter whose slot num_particles - 1 carries the regime path `reference`, then one draw of a path from the final weights
+    along the ancestors.  The kernel leaves p(s_{0:T-1} | y_{0:T-1}) invariant for ANY number of particles (Andrieu, Doucet &
+    Holenstein 2010; with z integrated out: Whiteley, Andrieu & Doucet 2010).
+
+    observations, model, num_particles: as `switching_filter`'s.
+    reference: T int32 [batch_size] tensors on the device, one regime path per batch row.
+    ancestor_sampling: True — backwards first: for t = T-1 .. 1 the information step K34 along the reference (one trajectory
+        per row) stores (F, lam) per step; going forwards, the pinned slot's ancestor at step t is drawn in proportion to
+        weight x Pi[s, reference[t]] x the closed-form integral of the reference's future against the stored particle's
+        N(m, P) (K35's score; Lindsten, Bunch, Saerkkae, Schoen & Godsill 2016).  False — the pinned slot keeps ancestor
+        num_particles - 1 and no backward pass runs.
+    uniforms: `particle_gibbs.conditional_smc`'s convention — None: fresh float64 blocks from torch's generator for the
+        device (seed with torch.manual_seed); or a length-T sequence: `uniforms[t]` [batch_size, num_particles] for t <=
+        T-2 — the ancestors of step t+1, from step t's weights (column k is slot k's) — and `uniforms[T-1]` [batch_size, 1]
+        for the final draw (replay).
+    regime_uniforms: None, or T float64 [batch_size, num_particles] tensors: the regime draws of every step (column
+        num_particles - 1 is not used: that slot's regime is the reference's).
+        Fresh blocks are drawn in this order: step 0's regime block; then per step t = 1 .. T-1 the resampling block
+        `uniforms[t-1]` and the step's regime block; last the [batch_size, 1] block of the final draw.  Inside
+        `distributed.shard_scope` a None of either raises NotImplementedError, as `switching_filter`'s does.
+    return_particles: also a dict with the stored systems — regimes (T int32 [batch_size, K], the reference in slot K-1),
+        means, covariances (packed), log_weights — and ancestral_indices ((T-1) int64 [batch_size, K]) and indices (T int64
+        [batch_size]: the slot the new path passes through).
+
+    Returns T int32 [batch_size] tensors, the new path.  With return_particles: (path, particles).
+
+    Per step one launch of K37 (`aesmc_switching_conditional_ancestor_index`: the K-1 free multinomial ancestors and the
+    pinned slot's in one go) and one of K38 (`aesmc_switching_kalman_conditional_step`: K31 with slot K-1's regime pinned);
+    every slot, the pinned one included, is weighted by its Kalman predictive likelihood.  At the end one K21 draw per row and
+    the walk back.  A sweep costs O(K) per step.
+
+    ValueError for an invalid model, T == 0, K < 1, a reference, uniforms or regime_uniforms of the wrong length, shape or
+    dtype; NotImplementedError naming the covered class past the limits (K above 8192, above 4096 for a latent of more than
+    4 values).  NaN weights or scores raise FloatingPointError, a regime outside [0, M) and a row without a finite maximum
+    (also: no stored particle can precede the reference) RuntimeError — read once, at the end; an exception on
+    the way discards whatever was flagged.  No host synchronisation inside the loops.  Runs under torch.no_grad()."""
+    name = "conditional_switching_filter"
+    num_timesteps, num_particles = len(observations), int(num_particles)
+    if num_timesteps == 0:
+        raise ValueError("{}: observations must hold at least one timestep".format(name))
+    if num_particles < 1:
+        raise ValueError("{}: num_particles must be at least 1".format(name))
+    if reference is None or len(reference) != num_timesteps:
+        raise ValueError("{}: reference must hold one tensor per timestep ({}), got {}".format(
+            name, num_timesteps, 0 if reference is None else len(reference)))
+    for what, feed in (("uniforms", uniforms), ("regime_uniforms", regime_uniforms)):
+        if feed is not None and len(feed) != num_timesteps:
+            raise ValueError("{}: {} must hold one block per timestep ({}), got {}".format(name, what, num_timesteps,
+                                                                                           len(feed)))
+    if uniforms is None or regime_uniforms is None:
+        from . import distributed
+        if distributed.active_shard() is not None:
+            raise NotImplementedError(
+                "aesmc_amd.rao_blackwell: {} inside distributed.shard_scope draws its uniforms on the device, where no "
+                "global block exists that every rank could cut its rows from. Pass uniforms= and regime_uniforms=."
+                .format(name))
+    provider = _kernels.get()
+    pinned = num_particles - 1
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops = model.operands()
+            M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
+            batch_size, device = _check_observations(name, provider, observations, model, num_particles)
+            if not provider.switching_conditional_covers(observations[0], M, D, Dy, num_particles):
+                _refuse("num_particles = {} with a latent of {} values (conditional resampling keeps its running sums in "
+                        "LDS: at most 8192 particles, 4096 for a latent of more than 4 values)".format(num_particles, D))
+            for time, regime in enumerate(reference):
+                if not torch.is_tensor(regime) or tuple(regime.shape) != (batch_size,) or regime.dtype != torch.int32 or \
+                        regime.device != device:
+                    raise ValueError("{}: reference[{}] must be {} int32 on {}".format(name, time, (batch_size,), device))
+            draw = _regime_draws(name, regime_uniforms, (batch_size, num_particles), device)
+
+            def block(time):
+                shape = (batch_size, 1 if time == num_timesteps - 1 else num_particles)
+                if uniforms is None:
+                    return torch.rand(shape, dtype=torch.float64, device=device)
+                u = uniforms[time]
+                if not torch.is_tensor(u) or tuple(u.shape) != shape or u.dtype != torch.float64 or u.device != device:
+                    raise ValueError("{}: uniforms[{}] must be {} float64 on {}".format(name, time, shape, device))
+                return u
+
+            log_Pi = torch.log(ops["Pi"])      # (-inf where a probability is 0) once
+            information = [None] * num_timesteps      # at position t: (F, lam) of the reference's future from t on
+            if ancestor_sampling:
+                info = None
+                for time in range(num_timesteps - 1, 0, -1):
+                    omega, lam, c, factor = provider.switching_information_step(ops, reference[time].unsqueeze(1), info,
+                                                                                observations[time])
+                    info = (omega, lam, c)
+                    information[time] = (factor[:, 0], lam[:, 0])
+            regimes, means, covariances, log_weights, ancestral = [], [], [], [], []
+            state, index = None, None
+            for time in range(num_timesteps):
+                if time > 0:
+                    factor, lam = information[time] if ancestor_sampling else (None, None)
+                    index = provider.switching_conditional_ancestor_index(log_weights[-1], block(time - 1), log_Pi,
+                                                                          reference[time], factor, lam, state)
+                    ancestral.append(index)
+                    # (a failed draw is position K: the step reads particle K-1 in its place, the flag raises at the end)
+                    index = index.clamp(max=pinned)
+                regime, mean, cov, log_w = provider.switching_kalman_conditional_step(ops, state, index, draw(time),
+                                                                                      reference[time], observations[time])
+                state = (regime, mean, cov)
+                regimes.append(regime), means.append(mean), covariances.append(cov), log_weights.append(log_w)
+            last, _ = provider.backward_sample(log_weights[-1], None, None, None, block(num_timesteps - 1))
+            indices = [None] * num_timesteps
+            indices[-1] = last[:, 0]
+            for time in range(num_timesteps - 2, -1, -1):
+                # (an index of a flagged row is num_particles: the clamp keeps the read in range, the flag raises below)
+                at = indices[time + 1].clamp(max=pinned).unsqueeze(1)
+                indices[time] = torch.gather(ancestral[time], 1, at)[:, 0]
+            path = [torch.gather(regimes[time], 1, indices[time].clamp(max=pinned).unsqueeze(1))[:, 0]
+                    for time in range(num_timesteps)]
+            inference._raise_for_flags(provider.read_flags(device))
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    if return_particles:
+        return path, {"regimes": regimes, "means": means, "covariances": covariances, "log_weights": log_weights,
+                      "ancestral_indices": ancestral, "indices": indices}
+    return path
+
+
+def switching_particle_gibbs(observations, model, num_particles, num_sweeps, reference=None, ancestor_sampling=True,
+                             burn_in=0):
+    """Runs `num_sweeps` sweeps of `conditional_switching_filter`, each from the path the one before returned: batch_size
+    independent Markov chains on regime paths whose stationary law is p(s_{0:T-1} | y_{0:T-1}) for any num_particles; with
+    ancestor sampling 8 .. 64 particles mix.
+
+    reference: the first path, T int32 [batch_size] tensors; None — one trajectory of `switching_smooth` with num_particles
+        particles (which consumes numpy's RandomState as `switching_filter` does; the sweeps draw from torch's generator).
+    burn_in: the first `burn_in` sweeps are run and not returned.
+    The other arguments are `conditional_switching_filter`'s.
+
+    Returns a dict: regimes (T int32 [batch_size, num_sweeps - burn_in]: regimes[t][b, s] is s_t of chain b after sweep
+    burn_in + s — the shape `switching_state_smooth` and `conditional_kalman_filter` take, successive sweeps of a chain being
+    dependent draws) and smoothed_regime_probabilities ([T, batch_size, M] float64: the frequencies over the kept sweeps)."""
+    num_sweeps, burn_in = int(num_sweeps), int(burn_in)
+    if not 0 <= burn_in < num_sweeps:
+        raise ValueError("switching_particle_gibbs: 0 <= burn_in < num_sweeps, got burn_in = {} and num_sweeps = {}".format(
+            burn_in, num_sweeps))
+    if reference is None:
+        drawn, _ = switching_smooth(observations, model, num_particles, num_trajectories=1)
+        reference = [regime[:, 0].contiguous() for regime in drawn["regimes"]]
+    path, kept = list(reference), []
+    for sweep in range(num_sweeps):
+        path = conditional_switching_filter(observations, model, num_particles, path, ancestor_sampling=ancestor_sampling)
+        if sweep >= burn_in:
+            kept.append(path)
+    M = model.num_regimes
+    regimes = [torch.stack([paths[time] for paths in kept], dim=1) for time in range(len(path))]
+    with torch.no_grad():
+        probabilities = torch.stack([
+            torch.nn.functional.one_hot(regime.to(torch.int64).clamp(0, M - 1), M).to(torch.float64).mean(dim=1)
+            for regime in regimes])
+    return {"regimes": regimes, "smoothed_regime_probabilities": probabilities}
 
 
 class _ZeroFeed:

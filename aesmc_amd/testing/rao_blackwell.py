@@ -1484,3 +1484,217 @@ def example_smooth_combine(B, N, M, D, Dy, steps=1, seed=0):
 
     filtered = (rng.standard_normal((B, N, D)), covariance())
     return model, regime_next, filtered, factor, lam, None if info is None else info[0], covariance()
+
+
+# ---- particle Gibbs on the regimes: conditional resampling (K37), the conditional step (K38) and the sweep they make -------------
+# Conditional SMC (Andrieu, Doucet & Holenstein 2010) on the regimes of the Rao-Blackwellised filter: slot K-1 carries a
+# reference regime path s'_0..s'_{T-1}.  With z integrated out the regimes are not Markov, so the ancestor-sampling weight of
+# stored particle j at the step entering time t is (Whiteley, Andrieu & Doucet 2010; Lindsten, Bunch, Saerkkae, Schoen &
+# Godsill 2016)
+#
+#     w_j Pi[s_j, s'_t] p(y_{t..T-1} | s'_{t..T-1}, m_j, P_j)
+#
+# — exactly `switching_backward_scores` of the ONE trajectory s' against the information (F, lam) that
+# `switching_information_step` carries backwards along it, with log w included.
+def _step_margins(w, bad, u):
+    """|u C[K-1] - C[j]| at the nearest step j of the running sum, over C[K-1], per row and column of u [B,R]; inf for a bad
+    row.  Only a draw this close to a step can differ between two evaluations of the weights."""
+    B, K = w.shape
+    running = np.cumsum(np.where(bad[:, None], 1.0, w), axis=1)
+    out = np.full(u.shape, np.inf)
+    for b in range(B):
+        if bad[b] or u.shape[1] == 0:
+            continue
+        position = u[b] * running[b, -1]
+        right = np.minimum(np.searchsorted(running[b], position, side="left"), K - 1)
+        left = np.maximum(right - 1, 0)
+        out[b] = np.minimum(np.abs(running[b, right] - position), np.abs(running[b, left] - position)) / running[b, -1]
+    return out
+
+
+def switching_conditional_ancestor_index(log_w, u, log_Pi, regime_next, factor, lam, particles):
+    """(idx int64 [B,K], flags, margins [B,K], score_bound [B]) of one conditional resampling step (include/aesmc_hip.h:
+    aesmc_switching_conditional_ancestor_index, K37).
+
+    log_w, u: float64 [B,K]; log_Pi: float64 [M,M]; regime_next: int32 [B], the reference's regime at the step being
+    entered; factor [B,D(D+1)/2], lam [B,D]: `switching_information_step`'s F and lam of the reference (N = 1, squeezed), or
+    both None (no ancestor sampling); particles: the stored (regime, mean, cov) the weights belong to.
+
+        idx[b,k]   = `testing.particle_gibbs.conditional_ancestor_index`'s free slots, k = 0 .. K-2
+        idx[b,K-1] = K - 1 without ancestor sampling; else the same draw at u[b,K-1] over
+                     s[j] = switching_backward_scores(log_Pi, regime_next[:,None], factor[:,None], lam[:,None], particles,
+                                                      log_w)[b,0,j]
+
+    Bad rows as that function's: a NaN among log_w — FLAG_NAN_LOG_WEIGHT, every slot K; no finite maximum —
+    FLAG_DEGENERATE_ROW, every slot K; the same among s, where only idx[b,K-1] = K.  A regime outside [0, M) on either side:
+    NaN scores and FLAG_INDEX_OUT_OF_RANGE beside them.
+    margins: `_step_margins` of every draw (inf where nothing is drawn); score_bound: the largest
+    `switching_backward_scores_bound` among a row's finite scores (0 without ancestor sampling)."""
+    from . import particle_gibbs as _pg
+    log_w = np.asarray(log_w, dtype=np.float64)
+    B, K = log_w.shape
+    u = np.asarray(u, dtype=np.float64)
+    if u.shape != (B, K):
+        raise ValueError("one uniform per slot: u must be [{}, {}], got {}".format(B, K, u.shape))
+    if (factor is None) != (lam is None):
+        raise ValueError("factor and lam come together")
+    w, nan, degenerate = _pg._weights(log_w)
+    flags = (FLAG_NAN_LOG_WEIGHT if nan.any() else 0) | (FLAG_DEGENERATE_ROW if degenerate.any() else 0)
+    bad_row = nan | degenerate
+    idx = np.empty((B, K), dtype=np.int64)
+    margins = np.full((B, K), np.inf)
+    idx[:, :K - 1] = _pg._draw(w, bad_row, u[:, :K - 1])
+    margins[:, :K - 1] = _step_margins(w, bad_row, u[:, :K - 1])
+    if factor is None:
+        idx[:, K - 1] = np.where(bad_row, K, K - 1)
+        return idx, flags, margins, np.zeros(B)
+    args = (log_Pi, np.asarray(regime_next).reshape(B, 1), np.asarray(factor)[:, None, :], np.asarray(lam)[:, None, :],
+            particles, log_w)
+    scores, bits = switching_backward_scores(*args)
+    scores = scores[:, 0, :]
+    bound = np.where(np.isfinite(scores), switching_backward_scores_bound(*args)[:, 0, :], 0.0).max(axis=1)
+    flags |= bits
+    w, nan, degenerate = _pg._weights(scores)
+    flags |= (FLAG_NAN_LOG_WEIGHT if nan.any() else 0) | (FLAG_DEGENERATE_ROW if degenerate.any() else 0)
+    pinned = _pg._draw(w, nan | degenerate, u[:, K - 1:])[:, 0]
+    idx[:, K - 1] = np.where(bad_row, K, pinned)
+    margins[:, K - 1] = np.where(bad_row, np.inf, _step_margins(w, nan | degenerate, u[:, K - 1:])[:, 0])
+    return idx, flags, margins, bound
+
+
+def _conditional_step(model, state, idx, uniforms, pinned_regime, y, dtype, track):
+    """`_step`, and `_step` under `_forced` for the pinned regime, whose slot K-1 replaces the first's."""
+    uniforms = np.asarray(uniforms, dtype=np.float64)
+    B, K = uniforms.shape
+    M = model["A"].shape[0]
+    pinned_regime = np.asarray(pinned_regime)
+    outside = (pinned_regime < 0) | (pinned_regime >= M)
+    shim, forced = _forced(model, np.broadcast_to(np.where(outside, 0, pinned_regime)[:, None], (B, K)))
+    (regime, mean, cov, log_w, flags), errors = _step(model, state, idx, uniforms, y, dtype, track)
+    (regime_p, mean_p, cov_p, log_w_p, _), errors_p = _step(shim, state, idx, forced, y, dtype, track)
+    regime, mean, cov, log_w = regime.copy(), mean.copy(), cov.copy(), log_w.copy()
+    regime[:, K - 1], mean[:, K - 1], cov[:, K - 1], log_w[:, K - 1] = regime_p[:, K - 1], mean_p[:, K - 1], cov_p[:, K - 1], \
+        log_w_p[:, K - 1]
+    regime[outside, K - 1], mean[outside, K - 1], cov[outside, K - 1], log_w[outside, K - 1] = 0, np.nan, np.nan, np.nan
+    if track:
+        for e, e_p in zip(errors, errors_p):
+            e[:, K - 1] = e_p[:, K - 1]
+            e[outside, K - 1] = 0.0
+    # the flag of slot K-1 is its own: its ancestor, its stored regime, its pinned regime
+    if state is None:
+        bad = np.zeros((B, K), dtype=bool)
+    else:
+        ancestors = np.broadcast_to(np.arange(K), (B, K)) if idx is None else np.asarray(idx)
+        bad = (ancestors < 0) | (ancestors >= K)
+        previous = np.asarray(state[0])[np.arange(B)[:, None], np.where(bad, 0, ancestors)]
+        bad = bad | (previous < 0) | (previous >= M)
+    bad[:, K - 1] |= outside
+    flags = FLAG_INDEX_OUT_OF_RANGE if bad.any() else 0
+    return (regime, mean, cov, log_w, flags), errors
+
+
+def switching_kalman_conditional_step(model, state, idx, uniforms, pinned_regime, y, dtype=np.float64):
+    """`switching_kalman_step` with the regime of slot K-1 replaced by pinned_regime [B] (include/aesmc_hip.h:
+    aesmc_switching_kalman_conditional_step, K38): slots 0 .. K-2 are that function's, slot K-1 is that function's under
+    `_forced` for the pinned regime.  A pinned regime outside [0, M): regime 0, NaN mean, covariance and log-weight for
+    slot K-1 and FLAG_INDEX_OUT_OF_RANGE, as a stored regime outside it."""
+    with np.errstate(all="ignore"):
+        return _conditional_step(model, state, idx, uniforms, pinned_regime, y, dtype, False)[0]
+
+
+def switching_kalman_conditional_step_bound(model, state, idx, uniforms, pinned_regime, y):
+    """`switching_kalman_step_bound` of the conditional step: (bound of mean, of cov, of log_weight)."""
+    with np.errstate(all="ignore"):
+        _, (mean_e, cov_e, lw_e) = _conditional_step(model, state, idx, uniforms, pinned_regime, y, np.float64, True)
+    clean = lambda e: np.where(np.isfinite(e), 2 * 1.01 * e, np.inf)
+    return clean(mean_e), clean(cov_e), clean(lw_e)
+
+
+def conditional_switching_pass(observations, model, num_particles, reference, uniforms, regime_uniforms,
+                               ancestor_sampling=True):
+    """One whole conditional sweep on replayed uniforms (`aesmc_amd.rao_blackwell.conditional_switching_filter`).
+    observations: T x [B,Dy]; model: `operands`' dict; reference: T x int32 [B]; uniforms: T blocks, [B,K] for t <= T-2 (the
+    ancestors of step t+1, from step t's weights) and [B,1] for the final draw; regime_uniforms: T x float64 [B,K].
+
+    Backwards first, `switching_information_pass` along the reference (ancestor sampling only); then per step the
+    conditional resampling and the conditional Kalman step; then one `categorical_draw` from the last weights and the walk
+    back through the ancestors.
+
+    Returns a dict: path (T x int32 [B], the new regime path); regimes, means, covariances, log_weights (T arrays each: the
+    stored systems, the reference in slot K-1); ancestral_indices ((T-1) x int64 [B,K]); indices (T x int64 [B], the slot the
+    new path passes through); margins (T entries: [B,K] of step t's resampling draws for t <= T-2, [B] of the final draw);
+    score_bounds ((T-1) x [B]: the pinned scores' bounds); information ((T-1) tuples or None); flags; and tolerances
+    {"means", "covariances", "log_weights"} (T floats each), propagated as `switching_pass` propagates them."""
+    T, K = len(observations), int(num_particles)
+    B = np.asarray(regime_uniforms[0]).shape[0]
+    reference = [np.asarray(r).astype(np.int32) for r in reference]
+    with np.errstate(divide="ignore"):
+        log_Pi = np.log(model["Pi"])
+    flags, information = 0, [None] * (T - 1)
+    if ancestor_sampling and T > 1:
+        backward = switching_information_pass(model, [r[:, None] for r in reference], observations)
+        information, flags = backward["information"], backward["flags"]
+    out = {name: [] for name in ("regimes", "means", "covariances", "log_weights", "ancestral_indices", "margins",
+                                 "score_bounds")}
+    tolerances = {"means": [], "covariances": [], "log_weights": []}
+    state, idx = None, None
+    for t in range(T):
+        if t > 0:
+            factor = lam = None
+            if ancestor_sampling:
+                factor, lam = information[t - 1][3][:, 0, :], information[t - 1][1][:, 0, :]
+            idx, bits, margins, bound = switching_conditional_ancestor_index(out["log_weights"][-1], uniforms[t - 1], log_Pi,
+                                                                             reference[t], factor, lam, state)
+            flags |= bits
+            out["ancestral_indices"].append(idx), out["margins"].append(margins), out["score_bounds"].append(bound)
+        step_idx = None if idx is None else np.minimum(idx, K - 1)      # (a failed draw is K: the flag says so)
+        regime, mean, cov, log_w, bits = switching_kalman_conditional_step(model, state, step_idx, regime_uniforms[t],
+                                                                           reference[t], observations[t])
+        bound_m, bound_p, bound_w = switching_kalman_conditional_step_bound(model, state, step_idx, regime_uniforms[t],
+                                                                            reference[t], observations[t])
+        flags |= bits
+        D = mean.shape[-1]
+        fresh_m = float(np.sqrt((bound_m ** 2).sum(axis=-1)).max())
+        fresh_p = float(np.sqrt((unpack(bound_p, D) ** 2).sum(axis=(-2, -1))).max())
+        fresh_w = float(bound_w.max())
+        if t == 0:
+            tol_m, tol_p, tol_w = fresh_m, fresh_p, fresh_w
+        else:
+            pp, mm, mp, wm, wp = _sensitivities(model, state, step_idx, regime, observations[t])
+            before_m, before_p = tolerances["means"][-1], tolerances["covariances"][-1]
+            tol_p = 1.01 * pp * before_p + fresh_p
+            tol_m = 1.01 * (mm * before_m + mp * before_p) + fresh_m
+            tol_w = 1.01 * (wm * before_m + wp * before_p) + fresh_w
+        tolerances["means"].append(tol_m), tolerances["covariances"].append(tol_p), tolerances["log_weights"].append(tol_w)
+        state = (regime, mean, cov)
+        out["regimes"].append(regime), out["means"].append(mean), out["covariances"].append(cov)
+        out["log_weights"].append(log_w)
+    last, margin, bits = categorical_draw(out["log_weights"][-1], np.asarray(uniforms[T - 1], dtype=np.float64).reshape(B))
+    flags |= bits
+    out["margins"].append(margin)
+    indices, rows = [None] * T, np.arange(B)
+    indices[T - 1] = last
+    for t in range(T - 2, -1, -1):
+        indices[t] = out["ancestral_indices"][t][rows, np.minimum(indices[t + 1], K - 1)]
+    out["indices"] = indices
+    out["path"] = [out["regimes"][t][rows, np.minimum(indices[t], K - 1)].astype(np.int32) for t in range(T)]
+    out.update(information=information, flags=flags, tolerances=tolerances)
+    return out
+
+
+def exact_regime_posterior(model, ys):
+    """(sequences [M^T, T] int, probabilities [M^T]) of ONE series (ys: T x [Dy]): the joint law p(s_0..s_{T-1} |
+    y_0..y_{T-1}) over all M^T regime sequences by enumeration, each an exact Kalman filter (`_sequence_log_likelihood`) —
+    what `exact_regime_marginals` sums per (t, regime)."""
+    ys = [np.asarray(y, dtype=np.float64).reshape(1, -1) for y in ys]
+    T, M = len(ys), model["A"].shape[0]
+    sequences = np.array(list(itertools.product(range(M), repeat=T)), dtype=np.int64)
+    with np.errstate(divide="ignore"):
+        log_pi0, log_Pi = np.log(model["pi0"]), np.log(model["Pi"])
+    terms = np.empty(len(sequences))
+    for position, sequence in enumerate(sequences):
+        prior = log_pi0[sequence[0]] + sum(log_Pi[a, b] for a, b in zip(sequence, sequence[1:]))
+        terms[position] = prior + _sequence_log_likelihood(model, tuple(int(s) for s in sequence), ys) if np.isfinite(prior) \
+            else -np.inf
+    weights = np.exp(terms - terms.max())
+    return sequences, weights / weights.sum()

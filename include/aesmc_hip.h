@@ -83,7 +83,10 @@ extern "C" {
  *                aesmc_switching_information_step, aesmc_switching_backward_scores (K34, K35: Rao-Blackwellised backward
  *                simulation over the stored systems of either filter — its smoother);
  *                aesmc_switching_smooth_combine (K36: the smoothed moments and lag-one cross-covariance of the continuous
- *                state along a regime trajectory, from the conditional filter and K34 — the two-filter state smoother).
+ *                state along a regime trajectory, from the conditional filter and K34 — the two-filter state smoother);
+ *                aesmc_switching_conditional_ancestor_index with aesmc_switching_conditional_max_particles,
+ *                aesmc_switching_kalman_conditional_step (K37, K38: conditional resampling with ancestor sampling against
+ *                K34's information, and K31's step with one slot's regime pinned — particle Gibbs on the regimes).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -797,6 +800,49 @@ int aesmc_switching_smooth_combine(const aesmc_switching_model *model, const int
                                    const double *cov, const double *factor, const double *lambda,
                                    const double *omega_next, const double *cov_next, double *mean_out, double *cov_out,
                                    double *cross_out, int32_t *flags, int64_t B, int64_t N, int64_t D, void *stream);
+
+/* K37 — conditional multinomial resampling for the regimes of the same model: the ancestors of one step of a conditional
+ * Rao-Blackwellised filter with ancestor sampling (particle Gibbs on the regimes; Whiteley, Andrieu & Doucet 2010; Lindsten,
+ * Bunch, Saerkkae, Schoen & Godsill 2016).  K26 with the pinned slot's transition score replaced by K35's integral for the ONE
+ * reference trajectory of the batch row.  Per batch row, in one launch, everything in float64:
+ *   log_w   float64 [B,K]      the step's log-weights              u   float64 [B,K] in [0, 1), one uniform per slot
+ *   log_Pi  float64 [M,M]      rows: from-regime, -inf allowed     regime_next int32 [B]: the reference's regime at the step
+ *                                                                  being entered
+ *   factor  float64 [B,D(D+1)/2], lambda float64 [B,D]: K34's factor_out and lambda_out with N = 1 along the reference
+ *   regime  int32 [B,K], mean float64 [B,K,D], cov float64 [B,K,D(D+1)/2]: the stored particles the weights belong to
+ *   w[j]       = exp(log_w[b,j] - max_j log_w[b,:]);  C[j] = w[0] + ... + w[j]  (added front to back, one at a time)
+ *   idx[b,k]   = min( #{j : C[j] <= u[b,k] * C[K-1]},  max{j : w[j] > 0} )               k = 0 .. K-2: K26's, bit for bit
+ *   idx[b,K-1] = the same formula at u[b,K-1] over s[j] = K35's scores[b,0,j] of particle j against (regime_next[b], factor[b],
+ *                lambda[b]) with log_w[b,j] included — K35's chains in K35's order; -inf where log_Pi[regime[b,j],
+ *                regime_next[b]] is -inf
+ *   idx[b,K-1] = K - 1         factor and lambda both NULL (no ancestor sampling: log_Pi, regime_next and the stored
+ *                              particles are not read and may be NULL)
+ * Bad rows, by K26's conventions: a NaN among log_w[b,:] raises AESMC_FLAG_NAN_LOG_WEIGHT, a maximum that is not finite
+ * AESMC_FLAG_DEGENERATE_ROW, and every slot of the row is K; a NaN among s or no finite maximum of s (every transition into
+ * regime_next[b] has probability zero) raises the same flags and only idx[b,K-1] = K.  A stored regime or regime_next[b]
+ * outside [0, M) gives NaN scores (and so the above) and raises AESMC_FLAG_INDEX_OUT_OF_RANGE.  K == 1 gives idx = 0.
+ * The CDFs, and for D above 4 the covariances, live in LDS: K above aesmc_switching_conditional_max_particles(D) (8192 up to
+ * D = 4, 4096 above; 0 for a D outside 1 .. aesmc_switching_max_latent_dim()), D or M above the limits of K31 or B K beyond
+ * 32-bit element arithmetic return AESMC_ERR_UNSUPPORTED.  NULL (but flags; factor and lambda together; what they make
+ * unread) or misaligned pointers, negative sizes, M or D below 1 and out_idx being another operand return
+ * AESMC_ERR_INVALID_ARGUMENT; B K == 0 is a no-op.  No workspace.  Every check runs before any launch. */
+int64_t aesmc_switching_conditional_max_particles(int64_t D);
+int aesmc_switching_conditional_ancestor_index(const double *log_w, const double *u, const double *log_Pi,
+                                               const int32_t *regime_next, const double *factor, const double *lambda,
+                                               const int32_t *regime, const double *mean, const double *cov,
+                                               int64_t *out_idx, int32_t *flags, int64_t B, int64_t K, int64_t M, int64_t D,
+                                               void *stream);
+
+/* K38 — K31 with the regime of slot K-1 pinned: s = pinned_regime[b] for particle (b, K-1) in place of its inverse-CDF draw
+ * (the reference path's regime in a conditional sweep); every other slot, and everything after the regime is chosen, is K31's,
+ * in K31's order.  pinned_regime: int32 [B], must not be regime_out.  A pinned regime outside [0, M) writes regime 0 and NaN
+ * to that particle and raises AESMC_FLAG_INDEX_OUT_OF_RANGE, as a stored regime outside it does.  Everything else, the
+ * step-0 form, the conventions and the statuses as K31's. */
+int aesmc_switching_kalman_conditional_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                            const double *mean_in, const double *cov_in, const int64_t *idx,
+                                            const double *uniforms, const int32_t *pinned_regime, const void *y,
+                                            int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
+                                            int32_t *flags, int64_t B, int64_t K, void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
