@@ -185,6 +185,8 @@ TEST_HOOKS = {
     "aesmc_test_last_k2_form": (_i32, []),
     "aesmc_test_last_logweight_backward_form": (_i32, []),
     "aesmc_test_last_affine_backward_particles_per_lane": (_i32, []),
+    "aesmc_test_last_logweight_form": (_i32, []),
+    "aesmc_test_last_particle_summary_form": (_i32, []),
     "aesmc_test_set_pairwise_lse_form": (_i32, [_i32, _i32, _i32]),
     "aesmc_test_set_pairwise_mean_form": (_i32, [_i32]),
 }

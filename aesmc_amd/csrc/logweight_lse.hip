@@ -213,6 +213,9 @@ static inline bool use_whole_workgroup_per_row(int64_t B, int64_t K) {
   return K > 1024 || (K >= 256 && B < 2048);
 }
 
+// Which form K1 launched last, forward or backward (test hook at the end of the file): 2 * TPR + VEC.
+static int g_logweight_last_form = 0;
+
 static inline bool aligned16(const void *p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
 template <typename T>
@@ -226,6 +229,7 @@ static int launch_fwd(const void *a, const void *b, const void *c, void *lw, voi
   const int64_t grid64 = (B + rows - 1) / rows;
   if (grid64 > 0x7fffffffLL) return AESMC_ERR_UNSUPPORTED;
   dim3 grid((unsigned)grid64), block(kBlock);
+  g_logweight_last_form = 2 * (wide ? 256 : 64) + (vec ? 1 : 0);
   auto A = (const T *)a;
   auto Bp = (const T *)b;
   auto C = (const T *)c;
@@ -259,6 +263,7 @@ static int launch_bwd(const void *lw, const void *lse, const void *glw, const vo
   const int64_t grid64 = (B + rows - 1) / rows;
   if (grid64 > 0x7fffffffLL) return AESMC_ERR_UNSUPPORTED;
   dim3 grid((unsigned)grid64), block(kBlock);
+  g_logweight_last_form = 2 * (wide ? 256 : 64) + (vec ? 1 : 0);
   auto X = (const T *)lw;
   auto S = (const T *)lse;
   auto GW = (const T *)glw;
@@ -280,6 +285,8 @@ static int launch_bwd(const void *lw, const void *lse, const void *glw, const vo
 }
 
 }  // namespace aesmc
+
+extern "C" int aesmc_test_last_logweight_form(void) { return aesmc::g_logweight_last_form; }
 
 extern "C" int aesmc_logweight_lse(int dtype, const void *lp_a, const void *lp_b, const void *lp_c,
                                    void *out_lw, void *out_lse, int64_t B, int64_t K,

@@ -392,6 +392,16 @@ __global__ __launch_bounds__(kSumBlock) void particle_summary_merge_kernel(
     out_log_ess[b] = usable ? T(2) * Num<T>::log(s1) - Num<T>::log(s2) : Num<T>::nan();
 }
 
+// Which launch ran last (test hook at the end of the file): kernel (1 small, 2 general with 4-byte loads, 3 general with
+// 16-byte loads) | dense << 2 | S << 3 | TX << 12 | sweeps << 21.  For the small kernel TX holds R, the particles per
+// lane per tile, and sweeps the tiles per slice; for the general one sweeps counts the column sweeps (1 without values).
+static int g_summary_last_form = 0;
+
+static inline int summary_form(int kernel, bool dense, uint32_t S, uint32_t TX, uint64_t sweeps) {
+  if (sweeps > 1023) sweeps = 1023;
+  return kernel | (dense ? 4 : 0) | (int)(S << 3) | (int)(TX << 12) | (int)(sweeps << 21);
+}
+
 template <typename T>
 static int launch_summary(const void *log_w, const aesmc_view3 *value, void *out_log_ess, void *out_mean,
                           void *out_second, int64_t B, int64_t K, int64_t D, void *ws, size_t ws_bytes,
@@ -430,20 +440,25 @@ static int launch_summary(const void *log_w, const aesmc_view3 *value, void *out
                        ((reinterpret_cast<uintptr_t>(v) & 15u) == 0) && ((sv.b * (int64_t)sizeof(T)) % 16 == 0) &&
                        (((uint64_t)per_slice * D) % N == 0) && (((uint64_t)kSumBlock * D) % N == 0);
     const uint32_t R = (uint32_t)(kSmallD / D);
+    g_summary_last_form = summary_form(1, dense, S, R, ((uint64_t)per_slice + kSumBlock * R - 1) / (kSumBlock * R));
     hipLaunchKernelGGL(particle_summary_small_kernel<T>, dim3((unsigned)(B * S)), dim3(kSumBlock), 0, s,
                        static_cast<const T *>(log_w), v, sv, static_cast<T *>(out_log_ess),
                        static_cast<T *>(out_mean), static_cast<T *>(out_second), records, (uint32_t)K, cols, S,
                        dense ? 1 : 0, R);
-  } else if (vec)
+  } else if (vec) {
+    g_summary_last_form = summary_form(3, false, S, TX, ((uint64_t)cols + TX * kSumRegs - 1) / (TX * kSumRegs));
     hipLaunchKernelGGL((particle_summary_kernel<T, true>), dim3((unsigned)(B * S)), dim3(kSumBlock), lds, s,
                        static_cast<const T *>(log_w), v, sv, static_cast<T *>(out_log_ess),
                        static_cast<T *>(out_mean), static_cast<T *>(out_second), records, (uint32_t)K, cols, TX,
                        S);
-  else
+  } else {
+    g_summary_last_form =
+        summary_form(2, false, S, TX, cols == 0 ? 1 : ((uint64_t)cols + TX * kSumRegs - 1) / (TX * kSumRegs));
     hipLaunchKernelGGL((particle_summary_kernel<T, false>), dim3((unsigned)(B * S)), dim3(kSumBlock), lds, s,
                        static_cast<const T *>(log_w), v, sv, static_cast<T *>(out_log_ess),
                        static_cast<T *>(out_mean), static_cast<T *>(out_second), records, (uint32_t)K, cols, TX,
                        S);
+  }
   if (S > 1)
     hipLaunchKernelGGL(particle_summary_merge_kernel<T>, dim3((unsigned)B), dim3(kSumBlock), 0, s, records,
                        static_cast<T *>(out_log_ess), static_cast<T *>(out_mean),
@@ -452,6 +467,8 @@ static int launch_summary(const void *log_w, const aesmc_view3 *value, void *out
 }
 
 }  // namespace aesmc
+
+extern "C" int aesmc_test_last_particle_summary_form(void) { return aesmc::g_summary_last_form; }
 
 extern "C" size_t aesmc_particle_summary_workspace_bytes(int dtype, int64_t B, int64_t K, int64_t D) {
   if (B <= 0 || K <= 0 || D < 0) return 0;

@@ -132,6 +132,11 @@ int aesmc_logweight_accumulate(int dtype, const void *lp_a, const void *lp_b, co
  * K1 backward.  g[b,k] = grad_lw[b,k] + grad_lse[b] * exp(lw[b,k] - lse[b])   (either grad may be
  * NULL = zero).  Writes out_g (gradient w.r.t. lp_a and lp_b) and, if non-NULL, out_neg_g = -g
  * (gradient w.r.t. lp_c).  Replaces autograd of the ops listed under K1.
+ * Where lse[b] is not finite the kernel evaluates the expression as written: lse = -inf (a row of -inf) gives
+ * exp(-inf + inf) = NaN times grad_lse, lse = +inf gives exp(-inf) = 0 for finite lw and NaN where lw = +inf, a NaN lse
+ * gives NaN; with grad_lse NULL the term is dropped and g = grad_lw whatever lse holds.
+ * (Test hooks outside this header, like the other aesmc_test_*: aesmc_test_last_logweight_form reports the form the
+ * last K1 launch took, forward or backward, as 2 * TPR + VEC; aesmc_test_last_particle_summary_form does so for K7.)
  */
 int aesmc_logweight_lse_backward(int dtype, const void *lw, const void *lse, const void *grad_lw,
                                  const void *grad_lse, void *out_g, void *out_neg_g, int64_t B,
