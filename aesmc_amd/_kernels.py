@@ -2393,13 +2393,26 @@ class HipKernels:
                 raise ValueError("aesmc_amd: {} must be {} {} on {}".format(what, shape, dtype, device))
         return regime.contiguous(), mean.contiguous(), cov.contiguous()
 
-    def switching_kalman_step(self, model, state, index, uniforms, observation):
+    @staticmethod
+    def _switching_observed(observed, B, Dy, device):
+        """The mask of a masked step (K39, K40, K41), validated and dense: torch.bool [B,Dy] on the observation's device,
+        whose storage the entries read as uint8."""
+        if not torch.is_tensor(observed) or observed.dtype != torch.bool or tuple(observed.shape) != (B, Dy) or \
+                observed.device != device:
+            raise ValueError("aesmc_amd: observed must be None or a [{}, {}] torch.bool tensor on {}, got {}".format(
+                B, Dy, device, "{} {} on {}".format(tuple(observed.shape), observed.dtype, observed.device)
+                if torch.is_tensor(observed) else type(observed).__name__))
+        return observed.contiguous()
+
+    def switching_kalman_step(self, model, state, index, uniforms, observation, observed=None):
         """One step of the Rao-Blackwellised filter of a switching linear-Gaussian model (aesmc_switching_kalman_step, K31).
         model: a dict of dense float64 tensors cdf0 [M], cdf [M,M], m0 [D], s0 [D], A [M,D,D], b [M,D], q [M,D], C [M,Dy,D],
         d [M,Dy], r [M,Dy]; state: None (step 0) or (regime int32 [B,K], mean float64 [B,K,D], cov float64 [B,K,D(D+1)/2])
         — the STORED particles of the step before; index: int64 [B,K] or None (the identity); uniforms float64 [B,K];
         observation float32 / float64 [B,Dy].  Returns (regime, mean, cov, log_weight [B,K] float64), new tensors.  An index
-        outside [0, K) or a stored regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE."""
+        outside [0, K) or a stored regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE.
+        observed: None, or torch.bool [B,Dy] — the masked entry (aesmc_switching_kalman_masked_step, K39): row b's step is the
+        step of the model with the components deleted whose entry is False; y there is not used and may be NaN."""
         _require_hip(observation, "observation")
         tag = _tag(observation, "observation")
         _require_hip(uniforms, "regime uniforms")
@@ -2423,6 +2436,8 @@ class HipKernels:
         else:
             regime = mean = cov = index = None
         uniforms, observation = uniforms.contiguous(), observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
         out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
         out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
         out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
@@ -2431,6 +2446,16 @@ class HipKernels:
             return out_regime, out_mean, out_cov, log_weight
         per_particle = 8 + 2 * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) if state is not None else \
             8 + (4 + 8 * D + 8 * TD) + 8
+        if observed is not None:
+            self._launch(device, self._lib.aesmc_switching_kalman_masked_step,
+                         (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms), None,
+                          None, _ptr(observation), _ptr(observed), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov),
+                          _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
+                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
+                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                         (model, regime, mean, cov, index, uniforms, observation, observed, out_regime, out_mean, out_cov,
+                          log_weight, block), name="switching_kalman_masked_step")
+            return out_regime, out_mean, out_cov, log_weight
         self._launch(device, self._lib.aesmc_switching_kalman_step,
                      (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
                       _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_weight),
@@ -2442,13 +2467,13 @@ class HipKernels:
         return out_regime, out_mean, out_cov, log_weight
 
     # ---- K32, K33 ------------------------------------------------------------------------------
-    def switching_lookahead(self, model, log_prior, state, observation, num_particles=None):
+    def switching_lookahead(self, model, log_prior, state, observation, num_particles=None, observed=None):
         """The look-ahead of the fully adapted filter of a switching linear-Gaussian model (aesmc_switching_lookahead, K32):
         per stored particle one Kalman prediction per regime, the exact first-stage log-weight log p(y | history) and the
         cumulative row of the exact regime posterior.  model, state, observation as `switching_kalman_step`'s; log_prior:
         float64 [M,M] with a state (log Pi), [M] without one (log pi0; `num_particles` then gives K).  Returns (log_weight
         [B,K], cdf [B,K,M]) float64, new tensors.  A stored regime outside [0, M) gives NaN there and
-        FLAG_INDEX_OUT_OF_RANGE."""
+        FLAG_INDEX_OUT_OF_RANGE.  observed: as `switching_kalman_step`'s (aesmc_switching_masked_lookahead, K40)."""
         _require_hip(observation, "observation")
         tag = _tag(observation, "observation")
         device = observation.device
@@ -2474,12 +2499,24 @@ class HipKernels:
         log_prior = log_prior.contiguous()
         regime, mean, cov = (None, None, None) if state is None else self._switching_state(state, B, K, D, device)
         observation = observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
         log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
         cdf = torch.empty((B, K, M), dtype=torch.float64, device=device)
         if log_weight.numel() == 0:
             return log_weight, cdf
         TD = D * (D + 1) // 2
         per_particle = (4 + 8 * D + 8 * TD if state is not None else 0) + 8 + 8 * M
+        if observed is not None:
+            self._launch(device, self._lib.aesmc_switching_masked_lookahead,
+                         (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
+                          _ptr(observed), _ptr(log_weight), _ptr(cdf), _ptr(self.flags(device)), B, K,
+                          self._stream(observation)),
+                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
+                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                         (model, log_prior, regime, mean, cov, observation, observed, log_weight, cdf, block),
+                         name="switching_masked_lookahead")
+            return log_weight, cdf
         self._launch(device, self._lib.aesmc_switching_lookahead,
                      (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
                       _ptr(log_weight), _ptr(cdf), _ptr(self.flags(device)), B, K, self._stream(observation)),
@@ -2488,10 +2525,11 @@ class HipKernels:
                      (model, log_prior, regime, mean, cov, observation, log_weight, cdf, block), name="switching_lookahead")
         return log_weight, cdf
 
-    def switching_kalman_draw(self, model, state, index, uniforms, cdf, observation):
+    def switching_kalman_draw(self, model, state, index, uniforms, cdf, observation, observed=None):
         """`switching_kalman_step` with the regime drawn from a cumulative row per particle (aesmc_switching_kalman_draw,
         K33): cdf float64 [B,K,M], read at the ancestor's position (`switching_lookahead`'s).  Returns (regime, mean, cov,
-        log_likelihood [B,K] float64), new tensors; regimes, flags and NaNs as `switching_kalman_step`'s."""
+        log_likelihood [B,K] float64), new tensors; regimes, flags and NaNs as `switching_kalman_step`'s, and its
+        `observed` (K39 with particle_cdf)."""
         _require_hip(observation, "observation")
         tag = _tag(observation, "observation")
         _require_hip(uniforms, "regime uniforms")
@@ -2519,6 +2557,8 @@ class HipKernels:
         else:
             regime = mean = cov = index = None
         uniforms, observation = uniforms.contiguous(), observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
         out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
         out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
         out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
@@ -2527,6 +2567,16 @@ class HipKernels:
             return out_regime, out_mean, out_cov, log_likelihood
         per_particle = 8 + 8 * M + (2 if state is not None else 1) * (4 + 8 * D + 8 * TD) + 8 + \
             (8 if index is not None else 0)
+        if observed is not None:
+            self._launch(device, self._lib.aesmc_switching_kalman_masked_step,
+                         (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
+                          _ptr(cdf), None, _ptr(observation), _ptr(observed), _ptr(out_regime), _ptr(out_mean),
+                          _ptr(out_cov), _ptr(log_likelihood), _ptr(self.flags(device)), B, K, self._stream(observation)),
+                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
+                         8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
+                         (model, regime, mean, cov, index, uniforms, cdf, observation, observed, out_regime, out_mean,
+                          out_cov, log_likelihood, block), name="switching_kalman_masked_draw")
+            return out_regime, out_mean, out_cov, log_likelihood
         self._launch(device, self._lib.aesmc_switching_kalman_draw,
                      (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms), _ptr(cdf),
                       _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_likelihood),
@@ -2548,13 +2598,14 @@ class HipKernels:
             return False
         return observation.size(0) * num_trajectories * max(num_particles, 1) <= 0x7fffffff
 
-    def switching_information_step(self, model, regime_next, info, observation):
+    def switching_information_step(self, model, regime_next, info, observation, observed=None):
         """The information step of Rao-Blackwellised backward simulation (aesmc_switching_information_step, K34).  model as
         `switching_kalman_step`'s; regime_next int32 [B,N]: the trajectories' regimes at time t+1; info: None (the zeros of
         the last step) or (omega float64 [B,N,D(D+1)/2], lam float64 [B,N,D], c float64 [B,N]) of time t+1; observation
         float32 / float64 [B,Dy]: that of time t+1.  Returns (omega, lam, c, factor [B,N,D(D+1)/2]) of time t, new tensors;
         factor is the packed lower factor of omega, a pivot at or below 2^-40 of the largest diagonal entry giving a zero
-        column.  A regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE."""
+        column.  A regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE.  observed: as
+        `switching_kalman_step`'s (aesmc_switching_masked_information_step, K41)."""
         _require_hip(observation, "observation")
         tag = _tag(observation, "observation")
         _require_hip(regime_next, "regime_next")
@@ -2578,6 +2629,8 @@ class HipKernels:
                     raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
             omega, lam, c = omega.contiguous(), lam.contiguous(), c.contiguous()
         regime_next, observation = regime_next.contiguous(), observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
         out_omega = torch.empty((B, N, TD), dtype=torch.float64, device=device)
         out_lam = torch.empty((B, N, D), dtype=torch.float64, device=device)
         out_c = torch.empty((B, N), dtype=torch.float64, device=device)
@@ -2585,6 +2638,16 @@ class HipKernels:
         if out_c.numel() == 0:
             return out_omega, out_lam, out_c, factor
         per_trajectory = 4 + (2 if info is not None else 1) * 8 * (TD + D + 1) + 8 * TD
+        if observed is not None:
+            self._launch(device, self._lib.aesmc_switching_masked_information_step,
+                         (tag, ctypes.byref(block), _ptr(regime_next), _ptr(omega), _ptr(lam), _ptr(c), _ptr(observation),
+                          _ptr(observed), _ptr(out_omega), _ptr(out_lam), _ptr(out_c), _ptr(factor),
+                          _ptr(self.flags(device)), B, N, self._stream(observation)),
+                         lambda: B * N * per_trajectory + B * Dy * (observation.element_size() + 1) +
+                         8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
+                         (model, regime_next, omega, lam, c, observation, observed, out_omega, out_lam, out_c, factor, block),
+                         name="switching_masked_information_step")
+            return out_omega, out_lam, out_c, factor
         self._launch(device, self._lib.aesmc_switching_information_step,
                      (tag, ctypes.byref(block), _ptr(regime_next), _ptr(omega), _ptr(lam), _ptr(c), _ptr(observation),
                       _ptr(out_omega), _ptr(out_lam), _ptr(out_c), _ptr(factor), _ptr(self.flags(device)), B, N,
@@ -2643,14 +2706,17 @@ class HipKernels:
         return scores
 
     # ---- K36 -----------------------------------------------------------------------------------
-    def switching_smooth_combine(self, model, regime_next, filtered, factor, lam, omega_next=None, cov_next=None):
+    def switching_smooth_combine(self, model, regime_next, filtered, factor, lam, omega_next=None, cov_next=None,
+                                 observed_next=None):
         """The two-filter combination of the state smoother (aesmc_switching_smooth_combine, K36).  filtered: (mean float64
         [B,N,D], cov float64 [B,N,D(D+1)/2]), the conditional filter's of time t; factor [B,N,D(D+1)/2], lam [B,N,D]:
         `switching_information_step`'s of time t.  The lag-one cross-covariance is formed when cov_next (the smoothed packed
         covariance of time t+1) is given: model as `switching_kalman_step`'s, regime_next int32 [B,N] (the regimes at t+1),
         omega_next: `switching_information_step`'s omega of time t+1 or None (t+1 = T-1).  Without cov_next the model,
         regime_next and omega_next are not read (pass None).  Returns (mean [B,N,D], cov [B,N,D(D+1)/2], cross [B,N,D,D] or
-        None), new tensors.  With cov_next a regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE."""
+        None), new tensors.  With cov_next a regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE.
+        observed_next: None, or torch.bool [B,Dy], which components of y_{t+1} were observed — the masked entry
+        (aesmc_switching_masked_smooth_combine, K42), with cov_next only: the cross-covariance alone depends on it."""
         mean, cov = filtered
         _require_hip(mean, "mean")
         device = mean.device
@@ -2682,6 +2748,10 @@ class HipKernels:
                 raise ValueError("aesmc_amd: the model's latent has {} values, the mean {}".format(model_d, D))
             regime_next, cov_next = regime_next.contiguous(), cov_next.contiguous()
             omega_next = None if omega_next is None else omega_next.contiguous()
+            if observed_next is not None:
+                observed_next = self._switching_observed(observed_next, B, Dy, device)
+        elif observed_next is not None:
+            raise ValueError("aesmc_amd: switching_smooth_combine reads observed_next only with cov_next")
         if not (1 <= D <= max_d and M <= max_m and Dy <= max_dy and B * N <= 0x7fffffff // (max_d * max_d)):
             raise ValueError("aesmc_amd: switching_smooth_combine does not take these operands (see switching_covers)")
         mean, cov, factor, lam = mean.contiguous(), cov.contiguous(), factor.contiguous(), lam.contiguous()
@@ -2692,6 +2762,15 @@ class HipKernels:
             return out_mean, out_cov, out_cross
         per_trajectory = 8 * (2 * D + 3 * TD) + \
             ((4 + 8 * (TD + D * D) + (8 * TD if omega_next is not None else 0)) if cross else 0)
+        if observed_next is not None:
+            self._launch(device, self._lib.aesmc_switching_masked_smooth_combine,
+                         (ctypes.byref(block), _ptr(regime_next), _ptr(mean), _ptr(cov), _ptr(factor), _ptr(lam),
+                          _ptr(omega_next), _ptr(cov_next), _ptr(observed_next), _ptr(out_mean), _ptr(out_cov),
+                          _ptr(out_cross), _ptr(self.flags(device)), B, N, D, self._stream(mean)),
+                         lambda: B * N * per_trajectory + B * Dy + 8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
+                         (model, regime_next, mean, cov, factor, lam, omega_next, cov_next, observed_next, out_mean, out_cov,
+                          out_cross, block), name="switching_masked_smooth_combine")
+            return out_mean, out_cov, out_cross
         self._launch(device, self._lib.aesmc_switching_smooth_combine,
                      (None if block is None else ctypes.byref(block), _ptr(regime_next), _ptr(mean), _ptr(cov), _ptr(factor),
                       _ptr(lam), _ptr(omega_next), _ptr(cov_next), _ptr(out_mean), _ptr(out_cov), _ptr(out_cross),
@@ -2764,11 +2843,11 @@ class HipKernels:
                      name="switching_conditional_ancestor_index")
         return idx
 
-    def switching_kalman_conditional_step(self, model, state, index, uniforms, pinned_regime, observation):
+    def switching_kalman_conditional_step(self, model, state, index, uniforms, pinned_regime, observation, observed=None):
         """`switching_kalman_step` with the regime of slot K-1 pinned (aesmc_switching_kalman_conditional_step, K38):
         pinned_regime int32 [B], the regime particle (b, K-1) takes in place of its draw.  Returns (regime, mean, cov,
         log_weight [B,K] float64), new tensors; flags and NaNs as `switching_kalman_step`'s, a pinned regime outside [0, M)
-        as a stored one."""
+        as a stored one.  observed: as `switching_kalman_step`'s (K39 with pinned_regime)."""
         _require_hip(observation, "observation")
         tag = _tag(observation, "observation")
         _require_hip(uniforms, "regime uniforms")
@@ -2797,6 +2876,8 @@ class HipKernels:
         else:
             regime = mean = cov = index = None
         uniforms, observation = uniforms.contiguous(), observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
         out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
         out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
         out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
@@ -2805,6 +2886,16 @@ class HipKernels:
             return out_regime, out_mean, out_cov, log_weight
         per_particle = 8 + 2 * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) if state is not None else \
             8 + (4 + 8 * D + 8 * TD) + 8
+        if observed is not None:
+            self._launch(device, self._lib.aesmc_switching_kalman_masked_step,
+                         (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms), None,
+                          _ptr(pinned_regime), _ptr(observation), _ptr(observed), _ptr(out_regime), _ptr(out_mean),
+                          _ptr(out_cov), _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
+                         lambda: B * K * per_particle + 4 * B + B * Dy * (observation.element_size() + 1) +
+                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                         (model, regime, mean, cov, index, uniforms, pinned_regime, observation, observed, out_regime,
+                          out_mean, out_cov, log_weight, block), name="switching_kalman_masked_conditional_step")
+            return out_regime, out_mean, out_cov, log_weight
         self._launch(device, self._lib.aesmc_switching_kalman_conditional_step,
                      (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
                       _ptr(pinned_regime), _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov),

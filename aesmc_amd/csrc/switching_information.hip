@@ -26,6 +26,16 @@
 //   <8,2>       256     74        0             1
 //   <8,4>       256     76        0             1
 //   <8,8>       256     74        0             1
+// and of the masked instantiations (K41, aesmc_switching_masked_information_step):
+//   <2,2>        57      0        0             8
+//   <2,4>        72      0        0             7
+//   <2,8>       112      0        0             4
+//   <4,2>       108      0        0             4
+//   <4,4>       102      0        0             4
+//   <4,8>       158      0        0             3
+//   <8,2>       256     78        0             1
+//   <8,4>       256     74        0             1
+//   <8,8>       256     74        0             1
 // There are B N trajectories, not B N K pairs: this launch is a tenth of a step at N = 64, K = 1024 (profiles/
 // switching_smoother.txt).  The 8-wide instantiations keep Oh, L and X (36 + 36 + 64 float64) live at once and move through
 // the accumulation registers; none uses scratch, and they are not given K31's LDS layout.
@@ -38,6 +48,7 @@ struct InformationArgs {
   const int32_t *regime_next;                      // [B,N]
   const double *omega_in, *lambda_in, *c_in;       // all NULL: the zeros of the last step
   const void *y;                                   // [B,Dy]
+  const uint8_t *observed;                         // K41: [B,Dy], nonzero = observed; NULL in the unmasked instantiations
   double *omega_out, *lambda_out, *c_out, *factor_out;
   int32_t *flags;
   int64_t total;                                   // B N
@@ -45,7 +56,9 @@ struct InformationArgs {
   int M, D, Dy, y_is_float;
 };
 
-template <int DP, int DYP>
+// Masked (K41): a component whose byte of `observed` is zero adds no information — its e and its 1 / r^2 are SELECTED to 0
+// (its y is never read into a chain), its log r^2 is dropped, and the constant counts the observed components
+template <int DP, int DYP, bool Masked>
 __global__ __launch_bounds__(kSkBlock) void switching_information_kernel(const InformationArgs a) {
   extern __shared__ __attribute__((aligned(16))) double si_smem[];
   constexpr int kPer = sk_per_regime(DP, DYP);
@@ -95,14 +108,29 @@ __global__ __launch_bounds__(kSkBlock) void switching_information_kernel(const I
 #pragma unroll
     for (int i = 0; i < DYP; ++i) yv[i] = i < Dy ? yrow[i] : 0.0;
   }
+  bool seen[DYP];
+  int n_obs = Dy;
+  if constexpr (Masked) {
+    const uint8_t *orow = a.observed + b * Dy;
+    n_obs = 0;
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) {
+      seen[i] = i < Dy ? orow[i] != 0 : false;
+      n_obs += seen[i] ? 1 : 0;
+      yv[i] = seen[i] ? yv[i] : 0.0;      // (may be NaN or Inf where not observed)
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) seen[i] = true;
+  }
   double quad = 0.0, logr = 0.0;
 #pragma unroll
   for (int i = 0; i < DYP; ++i) {
     if (i) SK_REREAD_LDS();
-    const double e = yv[i] - dv[i];
-    const double rho = 1.0 / r2[i];
+    const double e = Masked && !seen[i] ? 0.0 : yv[i] - dv[i];
+    const double rho = Masked && !seen[i] ? 0.0 : 1.0 / r2[i];
     quad = __builtin_fma(e * rho, e, quad);
-    logr += ::log(r2[i]);
+    logr += Masked && !seen[i] ? 0.0 : ::log(r2[i]);
     double G[DP];
 #pragma unroll
     for (int l = 0; l < DP; ++l) G[l] = Cm[i * DP + l] * rho;
@@ -115,7 +143,7 @@ __global__ __launch_bounds__(kSkBlock) void switching_information_kernel(const I
   }
   double ch = __builtin_fma(-0.5, quad, c);
   ch = __builtin_fma(-0.5, logr, ch);
-  ch = ch - (double)Dy * kHalfLog2Pi;
+  ch = ch - (double)n_obs * kHalfLog2Pi;
 
   // ---- L = chol(I + Q^1/2 Oh Q^1/2) in place, column by column; inv[k] = 1 / L_kk -----------------------------------------------
   SK_REREAD_LDS();
@@ -249,25 +277,33 @@ __global__ __launch_bounds__(kSkBlock) void switching_information_kernel(const I
     if (e < TD) f_out[e] = F[e];
 }
 
-template <int DP, int DYP>
+template <int DP, int DYP, bool Masked>
 static void si_launch(dim3 grid, size_t lds, hipStream_t s, const InformationArgs &a) {
-  hipLaunchKernelGGL((switching_information_kernel<DP, DYP>), grid, dim3(kSkBlock), lds, s, a);
+  hipLaunchKernelGGL((switching_information_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
 }
 
-template <int DP>
+template <int DP, bool Masked>
 static void si_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const InformationArgs &a) {
-  if (dyp == 2) si_launch<DP, 2>(grid, lds, s, a);
-  else if (dyp == 4) si_launch<DP, 4>(grid, lds, s, a);
-  else si_launch<DP, 8>(grid, lds, s, a);
+  if (dyp == 2) si_launch<DP, 2, Masked>(grid, lds, s, a);
+  else if (dyp == 4) si_launch<DP, 4, Masked>(grid, lds, s, a);
+  else si_launch<DP, 8, Masked>(grid, lds, s, a);
 }
 
-}  // namespace aesmc
+template <bool Masked>
+static void si_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const InformationArgs &a) {
+  if (dp == 2) si_launch_dy<2, Masked>(dyp, grid, lds, s, a);
+  else if (dp == 4) si_launch_dy<4, Masked>(dyp, grid, lds, s, a);
+  else si_launch_dy<8, Masked>(dyp, grid, lds, s, a);
+}
 
-extern "C" int aesmc_switching_information_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_next,
-                                                const double *omega_in, const double *lambda_in, const double *c_in,
-                                                const void *y, double *omega_out, double *lambda_out, double *c_out,
-                                                double *factor_out, int32_t *flags, int64_t B, int64_t N, void *stream) {
-  using namespace aesmc;
+// K34, and K41 (`masked`: observed [B,Dy] given): one set of checks, one launch
+static int si_step(bool masked, const uint8_t *observed, int y_dtype, const aesmc_switching_model *model,
+                   const int32_t *regime_next, const double *omega_in, const double *lambda_in, const double *c_in,
+                   const void *y, double *omega_out, double *lambda_out, double *c_out, double *factor_out, int32_t *flags,
+                   int64_t B, int64_t N, void *stream) {
+  if (masked && (observed == nullptr || (const void *)observed == omega_out || (const void *)observed == lambda_out ||
+                 (const void *)observed == c_out || (const void *)observed == factor_out))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (model == nullptr || regime_next == nullptr || y == nullptr || omega_out == nullptr || lambda_out == nullptr ||
       c_out == nullptr || factor_out == nullptr || B < 0 || N < 0)
     return AESMC_ERR_INVALID_ARGUMENT;
@@ -298,6 +334,7 @@ extern "C" int aesmc_switching_information_step(int y_dtype, const aesmc_switchi
   a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
   a.regime_next = regime_next;
   a.omega_in = omega_in, a.lambda_in = lambda_in, a.c_in = c_in, a.y = y;
+  a.observed = masked ? observed : nullptr;
   a.omega_out = omega_out, a.lambda_out = lambda_out, a.c_out = c_out, a.factor_out = factor_out;
   a.flags = flags;
   a.total = B * N, a.N = (uint32_t)N;
@@ -307,8 +344,27 @@ extern "C" int aesmc_switching_information_step(int y_dtype, const aesmc_switchi
   const size_t lds = (size_t)a.M * sk_per_regime(dp, dyp) * sizeof(double);
   const dim3 grid((unsigned)((a.total + kSkBlock - 1) / kSkBlock));
   hipStream_t s = (hipStream_t)stream;
-  if (dp == 2) si_launch_dy<2>(dyp, grid, lds, s, a);
-  else if (dp == 4) si_launch_dy<4>(dyp, grid, lds, s, a);
-  else si_launch_dy<8>(dyp, grid, lds, s, a);
+  if (masked) si_launch_d<true>(dp, dyp, grid, lds, s, a);
+  else si_launch_d<false>(dp, dyp, grid, lds, s, a);
   return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+}
+
+}  // namespace aesmc
+
+extern "C" int aesmc_switching_information_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_next,
+                                                const double *omega_in, const double *lambda_in, const double *c_in,
+                                                const void *y, double *omega_out, double *lambda_out, double *c_out,
+                                                double *factor_out, int32_t *flags, int64_t B, int64_t N, void *stream) {
+  return aesmc::si_step(false, nullptr, y_dtype, model, regime_next, omega_in, lambda_in, c_in, y, omega_out, lambda_out,
+                        c_out, factor_out, flags, B, N, stream);
+}
+
+extern "C" int aesmc_switching_masked_information_step(int y_dtype, const aesmc_switching_model *model,
+                                                       const int32_t *regime_next, const double *omega_in,
+                                                       const double *lambda_in, const double *c_in, const void *y,
+                                                       const uint8_t *observed, double *omega_out, double *lambda_out,
+                                                       double *c_out, double *factor_out, int32_t *flags, int64_t B,
+                                                       int64_t N, void *stream) {
+  return aesmc::si_step(true, observed, y_dtype, model, regime_next, omega_in, lambda_in, c_in, y, omega_out, lambda_out,
+                        c_out, factor_out, flags, B, N, stream);
 }

@@ -9,6 +9,11 @@
 // pointer, `pinned_regime` [B], whose entry slot K-1 of the row takes as its regime in place of the draw — the reference
 // path's.  NULL for K31 and K33; everything after the regime is chosen is the same code for every slot.
 //
+// And aesmc_switching_kalman_masked_step (K39), any of the three under a mask of the observation's components: the kernel's
+// second instantiation per extent (`Masked`), in which a component that batch row b did not observe is deleted from the step
+// by three selections placed after the chains of the unmasked text — see the kernel's comment.  The unmasked instantiations
+// are compiled from the text they had before K39.
+//
 // Only the regimes are sampled.  Particle k of batch row b carries (s, m, P): its regime and the exact Kalman mean and
 // covariance of the continuous state given its regime history.  One launch, per particle: the gather through the ancestors,
 // the inverse-CDF regime draw, the Kalman predict, the Dy x Dy Cholesky factor of the innovation covariance, two triangular
@@ -37,6 +42,18 @@
 //   <8,2>       256      0        0             2       P- in LDS
 //   <8,4>       256      0        0             2       P- in LDS
 //   <8,8>       256    256      132             1       P- in LDS
+// and of the masked instantiations (K39, aesmc_switching_kalman_masked_step: `Masked` below):
+//   <2,2>        65      0        0             7
+//   <2,4>        95      0        0             5
+//   <2,8>       208      0        0             2
+//   <4,2>        90      0        0             5
+//   <4,4>       148      0        0             3
+//   <4,8>       256     54        0             1
+//   <8,2>       256      0        0             2       P- in LDS
+//   <8,4>       256      0        0             2       P- in LDS
+//   <8,8>       256    242        0             1       P- in LDS
+// (the masked <8,8> uses no scratch where the unmasked one takes 132 bytes: the register allocator's outcome on the text
+// with the selections in it, not something the kernel was shaped for; profiles/switching_missing.txt has both forms' times.)
 // With P- in registers <8,8> took 328 bytes of scratch per lane (its live set — V 128, S 72, P- 72 registers and the vectors —
 // exceeds the 256 architectural VGPRs; the accumulation registers are a spill space with a move per use), so the 8-wide
 // instantiations keep the packed P- in LDS in an [element][lane] layout (72 KB per workgroup).  <8,8> still spills 33
@@ -60,6 +77,7 @@ struct SwitchingArgs {
   const int64_t *idx;
   const double *uniforms;
   const void *y;
+  const uint8_t *observed;          // K39: [B,Dy], nonzero = observed; NULL in the unmasked instantiations
   int32_t *regime_out;
   double *mean_out, *cov_out, *log_weight;
   int32_t *flags;
@@ -70,7 +88,10 @@ struct SwitchingArgs {
 
 // LDS: [M * M] (or [M]) cumulative rows, then per regime kPer values: A [DP,DP], b [DP], q^2 [DP], C [DYP,DP], d [DYP],
 // r^2 [DYP]; then, for DP == 8, [TP][256] predicted covariances
-template <int DP, int DYP>
+// Masked (K39): a component whose byte of `observed` is zero is deleted from the step — its e, its row of U and its row and
+// column of S are SELECTED to 0, 0 and the identity's after their chains (its y is never read into one), so that its pivot is
+// 1 as a padded component's is; the constant counts the observed components
+template <int DP, int DYP, bool Masked>
 __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const SwitchingArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sk_smem[];
   constexpr int kPer = DP * DP + 2 * DP + DYP * DP + 2 * DYP;
@@ -180,6 +201,20 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
   // ---- innovation, U = C P-, S_ij = C_i . U_j + diag(r^2): row i of C alone serves e_i, U_i and S_i ---------------------------
   SK_REREAD_LDS();
   double e[DYP], U[DYP][DP], S[TY], yv[DYP];
+  bool ob[DYP];
+  int n_obs = Dy;
+  if constexpr (Masked) {
+    const uint8_t *orow = a.observed + b * Dy;
+    n_obs = 0;
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) {
+      ob[i] = i < Dy ? orow[i] != 0 : false;
+      n_obs += ob[i] ? 1 : 0;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) ob[i] = true;
+  }
   if (a.y_is_float) {
     const float *yrow = (const float *)a.y + b * Dy;
 #pragma unroll
@@ -189,26 +224,30 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
 #pragma unroll
     for (int i = 0; i < DYP; ++i) yv[i] = i < Dy ? yrow[i] : 0.0;
   }
+  if constexpr (Masked) {
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) yv[i] = ob[i] ? yv[i] : 0.0;      // (may be NaN or Inf where not observed)
+  }
 #pragma unroll
   for (int i = 0; i < DYP; ++i) {
     if (i) SK_REREAD_LDS();
     double acc = yv[i] - dv[i];
 #pragma unroll
     for (int l = 0; l < DP; ++l) acc = __builtin_fma(-Cm[i * DP + l], mp[l], acc);
-    e[i] = acc;
+    e[i] = Masked && !ob[i] ? 0.0 : acc;      // (a select: a non-finite y at an unobserved position ends here)
 #pragma unroll
     for (int l = 0; l < DP; ++l) {
       double w = 0.0;
 #pragma unroll
       for (int c = 0; c < DP; ++c) w = __builtin_fma(Cm[i * DP + c], Pm.get(sk_tri(c, l)), w);
-      U[i][l] = w;
+      U[i][l] = Masked && !ob[i] ? 0.0 : w;
     }
 #pragma unroll
     for (int j = 0; j <= i; ++j) {
       double w = i == j ? r2[i] : 0.0;
 #pragma unroll
       for (int l = 0; l < DP; ++l) w = __builtin_fma(Cm[i * DP + l], U[j][l], w);
-      S[sk_tri(i, j)] = w;
+      S[sk_tri(i, j)] = Masked && !(ob[i] && ob[j]) ? (i == j ? 1.0 : 0.0) : w;
     }
   }
 
@@ -262,7 +301,7 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
     for (int c = 0; c < TD; ++c) pout[c] = nan;
     return;
   }
-  a.log_weight[n] = (-0.5 * quad - log_det) - (double)Dy * kHalfLog2Pi;
+  a.log_weight[n] = (-0.5 * quad - log_det) - (double)n_obs * kHalfLog2Pi;
 #pragma unroll
   for (int l = 0; l < DP; ++l) {
     SK_REREAD_LDS();      // (row by row: neither the reads of P- nor the stores move across)
@@ -280,23 +319,30 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
   }
 }
 
-template <int DP, int DYP>
+template <int DP, int DYP, bool Masked>
 static bool sk_launch(dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
   // the 8-wide instantiations (72 KB of covariances beside the model) need the limit raised; on every launch — no state to
   // share between threads or devices, and the call is cheap beside the kernel
   if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_kalman_kernel<DP, DYP>),
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_kalman_kernel<DP, DYP, Masked>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return false;
-  hipLaunchKernelGGL((switching_kalman_kernel<DP, DYP>), grid, dim3(kSkBlock), lds, s, a);
+  hipLaunchKernelGGL((switching_kalman_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
   return true;
 }
 
-template <int DP>
+template <int DP, bool Masked>
 static bool sk_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
-  if (dyp == 2) return sk_launch<DP, 2>(grid, lds, s, a);
-  if (dyp == 4) return sk_launch<DP, 4>(grid, lds, s, a);
-  return sk_launch<DP, 8>(grid, lds, s, a);
+  if (dyp == 2) return sk_launch<DP, 2, Masked>(grid, lds, s, a);
+  if (dyp == 4) return sk_launch<DP, 4, Masked>(grid, lds, s, a);
+  return sk_launch<DP, 8, Masked>(grid, lds, s, a);
+}
+
+template <bool Masked>
+static bool sk_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
+  if (dp == 2) return sk_launch_dy<2, Masked>(dyp, grid, lds, s, a);
+  if (dp == 4) return sk_launch_dy<4, Masked>(dyp, grid, lds, s, a);
+  return sk_launch_dy<8, Masked>(dyp, grid, lds, s, a);
 }
 
 }  // namespace aesmc
@@ -308,14 +354,18 @@ extern "C" int64_t aesmc_switching_max_regimes(void) { return aesmc::kSkMaxRegim
 namespace aesmc {
 
 // K31 (particle_cdf NULL, `draw` false), K33 (`draw`: the regime from particle_cdf [B,K,M], the model's own cumulative
-// rows not read) and K38 (`pinned`: pinned_regime [B] given): one set of checks, one launch
-static int sk_step(bool draw, bool pinned, int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+// rows not read) and K38 (`pinned`: pinned_regime [B] given): one set of checks, one launch.  K39 (`masked`: observed [B,Dy]
+// given) is any of the three with the masked instantiation
+static int sk_step(bool draw, bool pinned, bool masked, const uint8_t *observed, int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
                    const double *mean_in, const double *cov_in, const int64_t *idx, const double *uniforms,
                    const double *particle_cdf, const int32_t *pinned_regime, const void *y, int32_t *regime_out,
                    double *mean_out, double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
                    void *stream) {
   if (draw && (particle_cdf == nullptr || !sk_aligned(particle_cdf, 8))) return AESMC_ERR_INVALID_ARGUMENT;
   if (pinned && (pinned_regime == nullptr || !sk_aligned(pinned_regime, 4) || pinned_regime == regime_out))
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (masked && (observed == nullptr || (const void *)observed == regime_out || (const void *)observed == mean_out ||
+                 (const void *)observed == cov_out || (const void *)observed == log_weight))
     return AESMC_ERR_INVALID_ARGUMENT;
   if (model == nullptr || uniforms == nullptr || y == nullptr || regime_out == nullptr || mean_out == nullptr ||
       cov_out == nullptr || log_weight == nullptr || B < 0 || K < 0)
@@ -348,6 +398,7 @@ static int sk_step(bool draw, bool pinned, int y_dtype, const aesmc_switching_mo
   a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
   a.regime_in = regime_in, a.mean_in = mean_in, a.cov_in = cov_in;
   a.idx = idx, a.uniforms = uniforms, a.y = y;
+  a.observed = masked ? observed : nullptr;
   a.regime_out = regime_out, a.mean_out = mean_out, a.cov_out = cov_out, a.log_weight = log_weight;
   a.flags = flags;
   a.N = B * K, a.K = (uint32_t)K;
@@ -359,8 +410,7 @@ static int sk_step(bool draw, bool pinned, int y_dtype, const aesmc_switching_mo
                      sizeof(double);
   const dim3 grid((unsigned)((a.N + kSkBlock - 1) / kSkBlock));
   hipStream_t s = (hipStream_t)stream;
-  const bool launched = dp == 2 ? sk_launch_dy<2>(dyp, grid, lds, s, a)
-                        : dp == 4 ? sk_launch_dy<4>(dyp, grid, lds, s, a) : sk_launch_dy<8>(dyp, grid, lds, s, a);
+  const bool launched = masked ? sk_launch_d<true>(dp, dyp, grid, lds, s, a) : sk_launch_d<false>(dp, dyp, grid, lds, s, a);
   return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
 }
 
@@ -371,7 +421,7 @@ extern "C" int aesmc_switching_kalman_step(int y_dtype, const aesmc_switching_mo
                                            const double *uniforms, const void *y, int32_t *regime_out, double *mean_out,
                                            double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
                                            void *stream) {
-  return aesmc::sk_step(false, false, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, nullptr, y,
+  return aesmc::sk_step(false, false, false, nullptr, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, nullptr, y,
                         regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
 }
 
@@ -380,7 +430,7 @@ extern "C" int aesmc_switching_kalman_draw(int y_dtype, const aesmc_switching_mo
                                            const double *uniforms, const double *particle_cdf, const void *y,
                                            int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
                                            int32_t *flags, int64_t B, int64_t K, void *stream) {
-  return aesmc::sk_step(true, false, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, particle_cdf, nullptr, y,
+  return aesmc::sk_step(true, false, false, nullptr, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, particle_cdf, nullptr, y,
                         regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
 }
 
@@ -390,6 +440,18 @@ extern "C" int aesmc_switching_kalman_conditional_step(int y_dtype, const aesmc_
                                                        const int32_t *pinned_regime, const void *y, int32_t *regime_out,
                                                        double *mean_out, double *cov_out, double *log_weight, int32_t *flags,
                                                        int64_t B, int64_t K, void *stream) {
-  return aesmc::sk_step(false, true, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, pinned_regime, y,
+  return aesmc::sk_step(false, true, false, nullptr, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, nullptr, pinned_regime, y,
                         regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
+}
+
+// K39: particle_cdf non-NULL is K33's form, pinned_regime non-NULL K38's, both NULL K31's
+extern "C" int aesmc_switching_kalman_masked_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                                  const double *mean_in, const double *cov_in, const int64_t *idx,
+                                                  const double *uniforms, const double *particle_cdf,
+                                                  const int32_t *pinned_regime, const void *y, const uint8_t *observed,
+                                                  int32_t *regime_out, double *mean_out, double *cov_out,
+                                                  double *log_weight, int32_t *flags, int64_t B, int64_t K, void *stream) {
+  return aesmc::sk_step(particle_cdf != nullptr, pinned_regime != nullptr, true, observed, y_dtype, model, regime_in, mean_in,
+                        cov_in, idx, uniforms, particle_cdf, pinned_regime, y, regime_out, mean_out, cov_out, log_weight,
+                        flags, B, K, stream);
 }

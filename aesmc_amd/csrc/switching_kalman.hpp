@@ -1,5 +1,5 @@
-// What the kernels of the switching linear-Gaussian filters share (switching_kalman.hip: K31 and K33; switching_lookahead.hip:
-// K32): the limits, the packed-triangle index, where a lane keeps its predicted covariance, and the model's staging into LDS.
+// What the kernels of the switching linear-Gaussian filters share (switching_kalman.hip: K31, K33 and their masked form K39;
+// switching_lookahead.hip: K32 and K40): the limits, the packed-triangle index, where a lane keeps its predicted covariance, and the model's staging into LDS.
 #pragma once
 #include "common.hpp"
 

@@ -28,6 +28,16 @@
 //   <8,2>       256     22        0             1       P- in LDS
 //   <8,4>       256     26        0             1       P- in LDS
 //   <8,8>       256     34        0             1       P- in LDS
+// and of the masked instantiations (K40, aesmc_switching_masked_lookahead: K39's selections per regime):
+//   <2,2>        69      0        0             7
+//   <2,4>        91      0        0             5
+//   <2,8>       163      0        0             3
+//   <4,2>       103      0        0             4
+//   <4,4>       124      0        0             4
+//   <4,8>       217      0        0             2
+//   <8,2>       256     22        0             1       P- in LDS
+//   <8,4>       256     26        0             1       P- in LDS
+//   <8,8>       256     82        0             1       P- in LDS
 // No instantiation spills: without V = Lam^-1 U and the downdate the live set of <8,8> (U 128, S 72 registers and the
 // vectors) fits, and the input covariance is read again per regime instead of being held across the loop.
 //
@@ -44,6 +54,7 @@ struct LookaheadArgs {
   const int32_t *regime_in;         // NULL: step 0
   const double *mean_in, *cov_in;
   const void *y;
+  const uint8_t *observed;          // K40: [B,Dy], nonzero = observed; NULL in the unmasked instantiations
   double *log_weight, *cdf;
   int32_t *flags;
   int64_t N;
@@ -53,7 +64,8 @@ struct LookaheadArgs {
 
 // LDS: [M * M] (or [M]) log-priors, the model (M blocks of sk_per_regime values), for DP == 8 [TP][256] predicted
 // covariances, then [M][256] scores
-template <int DP, int DYP>
+// Masked (K40): K39's three selections (switching_kalman.hip) for every regime; the constant counts the observed components
+template <int DP, int DYP, bool Masked>
 __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const LookaheadArgs a) {
   extern __shared__ __attribute__((aligned(16))) double la_smem[];
   constexpr int kPer = sk_per_regime(DP, DYP);
@@ -95,6 +107,21 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
     const double *yrow = (const double *)a.y + b * Dy;
 #pragma unroll
     for (int i = 0; i < DYP; ++i) yv[i] = i < Dy ? yrow[i] : 0.0;
+  }
+  bool ob[DYP];
+  int n_obs = Dy;
+  if constexpr (Masked) {
+    const uint8_t *orow = a.observed + b * Dy;
+    n_obs = 0;
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) {
+      ob[i] = i < Dy ? orow[i] != 0 : false;
+      n_obs += ob[i] ? 1 : 0;
+      yv[i] = ob[i] ? yv[i] : 0.0;      // (may be NaN or Inf where not observed)
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < DYP; ++i) ob[i] = true;
   }
 
   double mp[DP];
@@ -162,20 +189,20 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
       double acc = yv[i] - dv[i];
 #pragma unroll
       for (int l = 0; l < DP; ++l) acc = __builtin_fma(-Cm[i * DP + l], mp[l], acc);
-      e[i] = acc;
+      e[i] = Masked && !ob[i] ? 0.0 : acc;
 #pragma unroll
       for (int l = 0; l < DP; ++l) {
         double w = 0.0;
 #pragma unroll
         for (int c = 0; c < DP; ++c) w = __builtin_fma(Cm[i * DP + c], Pm.get(sk_tri(c, l)), w);
-        U[i][l] = w;
+        U[i][l] = Masked && !ob[i] ? 0.0 : w;
       }
 #pragma unroll
       for (int c = 0; c <= i; ++c) {
         double w = i == c ? r2[i] : 0.0;
 #pragma unroll
         for (int l = 0; l < DP; ++l) w = __builtin_fma(Cm[i * DP + l], U[c][l], w);
-        S[sk_tri(i, c)] = w;
+        S[sk_tri(i, c)] = Masked && !(ob[i] && ob[c]) ? (i == c ? 1.0 : 0.0) : w;
       }
     }
 
@@ -211,7 +238,7 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
       e[i] = acc * inv[i];
       quad = __builtin_fma(e[i], e[i], quad);
     }
-    const double ell = (-0.5 * quad - log_det) - (double)Dy * kHalfLog2Pi;
+    const double ell = (-0.5 * quad - log_det) - (double)n_obs * kHalfLog2Pi;
     const double lpj = prior[j];
     // a regime of prior probability 0 has the score -inf whatever its pivots are; elsewhere a pivot that is not positive is NaN
     scores[j * kSkBlock] = lpj == -inf ? -inf : positive ? lpj + ell : nan;
@@ -247,30 +274,37 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
   }
 }
 
-template <int DP, int DYP>
+template <int DP, int DYP, bool Masked>
 static bool la_launch(dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
   // more than the default 64 KB: the limit is raised on every launch, as K31's launcher does and for its reasons
   if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_lookahead_kernel<DP, DYP>),
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_lookahead_kernel<DP, DYP, Masked>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return false;
-  hipLaunchKernelGGL((switching_lookahead_kernel<DP, DYP>), grid, dim3(kSkBlock), lds, s, a);
+  hipLaunchKernelGGL((switching_lookahead_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
   return true;
 }
 
-template <int DP>
+template <int DP, bool Masked>
 static bool la_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
-  if (dyp == 2) return la_launch<DP, 2>(grid, lds, s, a);
-  if (dyp == 4) return la_launch<DP, 4>(grid, lds, s, a);
-  return la_launch<DP, 8>(grid, lds, s, a);
+  if (dyp == 2) return la_launch<DP, 2, Masked>(grid, lds, s, a);
+  if (dyp == 4) return la_launch<DP, 4, Masked>(grid, lds, s, a);
+  return la_launch<DP, 8, Masked>(grid, lds, s, a);
 }
 
-}  // namespace aesmc
+template <bool Masked>
+static bool la_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
+  if (dp == 2) return la_launch_dy<2, Masked>(dyp, grid, lds, s, a);
+  if (dp == 4) return la_launch_dy<4, Masked>(dyp, grid, lds, s, a);
+  return la_launch_dy<8, Masked>(dyp, grid, lds, s, a);
+}
 
-extern "C" int aesmc_switching_lookahead(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
-                                         const int32_t *regime_in, const double *mean_in, const double *cov_in, const void *y,
-                                         double *log_weight, double *cdf, int32_t *flags, int64_t B, int64_t K, void *stream) {
-  using namespace aesmc;
+// K32, and K40 (`masked`: observed [B,Dy] given): one set of checks, one launch
+static int la_step(bool masked, const uint8_t *observed, int y_dtype, const aesmc_switching_model *model,
+                   const double *log_prior, const int32_t *regime_in, const double *mean_in, const double *cov_in,
+                   const void *y, double *log_weight, double *cdf, int32_t *flags, int64_t B, int64_t K, void *stream) {
+  if (masked && (observed == nullptr || (const void *)observed == log_weight || (const void *)observed == cdf))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (model == nullptr || log_prior == nullptr || y == nullptr || log_weight == nullptr || cdf == nullptr || B < 0 || K < 0)
     return AESMC_ERR_INVALID_ARGUMENT;
   if (y_dtype != AESMC_F32 && y_dtype != AESMC_F64) return AESMC_ERR_INVALID_ARGUMENT;
@@ -295,6 +329,7 @@ extern "C" int aesmc_switching_lookahead(int y_dtype, const aesmc_switching_mode
   a.m0 = model->m0, a.s0 = model->s0;
   a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
   a.regime_in = regime_in, a.mean_in = mean_in, a.cov_in = cov_in, a.y = y;
+  a.observed = masked ? observed : nullptr;
   a.log_weight = log_weight, a.cdf = cdf, a.flags = flags;
   a.N = B * K, a.K = (uint32_t)K;
   a.M = (int)model->M, a.D = (int)model->D, a.Dy = (int)model->Dy;
@@ -304,7 +339,23 @@ extern "C" int aesmc_switching_lookahead(int y_dtype, const aesmc_switching_mode
                       (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0) + (size_t)a.M * kSkBlock) * sizeof(double);
   const dim3 grid((unsigned)((a.N + kSkBlock - 1) / kSkBlock));
   hipStream_t s = (hipStream_t)stream;
-  const bool launched = dp == 2 ? la_launch_dy<2>(dyp, grid, lds, s, a)
-                        : dp == 4 ? la_launch_dy<4>(dyp, grid, lds, s, a) : la_launch_dy<8>(dyp, grid, lds, s, a);
+  const bool launched = masked ? la_launch_d<true>(dp, dyp, grid, lds, s, a) : la_launch_d<false>(dp, dyp, grid, lds, s, a);
   return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+}
+
+}  // namespace aesmc
+
+extern "C" int aesmc_switching_lookahead(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
+                                         const int32_t *regime_in, const double *mean_in, const double *cov_in, const void *y,
+                                         double *log_weight, double *cdf, int32_t *flags, int64_t B, int64_t K, void *stream) {
+  return aesmc::la_step(false, nullptr, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, cdf, flags, B, K,
+                        stream);
+}
+
+extern "C" int aesmc_switching_masked_lookahead(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
+                                                const int32_t *regime_in, const double *mean_in, const double *cov_in,
+                                                const void *y, const uint8_t *observed, double *log_weight, double *cdf,
+                                                int32_t *flags, int64_t B, int64_t K, void *stream) {
+  return aesmc::la_step(true, observed, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, cdf, flags, B, K,
+                        stream);
 }

@@ -20,6 +20,10 @@
 //   chains    every value is ONE chain of float64 __builtin_fma in the header's order; the triangular sums skip the
 //             structural zeros of F, a padded term multiplies a zero by a zero.
 //
+// aesmc_switching_masked_smooth_combine (K42) is the kernel's second instantiation per extent (`Masked`): the observation of
+// time t+1 enters Oh only through the components batch row b observed — 1 / r_i^2 is SELECTED to 0 elsewhere, K41's rule
+// (switching_information.hip).  Nothing else of the combination knows about observations.
+//
 // Compiler's resource report (-Rpass-analysis=kernel-resource-usage, gfx950, 256 lanes per workgroup):
 //   <DP,DYP>  VGPRs  AGPRs  scratch B/lane  waves/SIMD
 //   <2,2>        54      0        0             8
@@ -30,6 +34,16 @@
 //   <4,8>       131      0        0             3
 //   <8,2>       256    138        0             1       P in LDS
 //   <8,4>       256    134        0             1       P in LDS
+//   <8,8>       256    134        0             1       P in LDS
+// and of the masked instantiations (K42):
+//   <2,2>        56      0        0             8
+//   <2,4>        56      0        0             8
+//   <2,8>        76      0        0             6
+//   <4,2>       133      0        0             3
+//   <4,4>       133      0        0             3
+//   <4,8>       146      0        0             3
+//   <8,2>       256    138        0             1       P in LDS
+//   <8,4>       256    136        0             1       P in LDS
 //   <8,8>       256    134        0             1       P in LDS
 // The 8-wide instantiations hold F, G and U (36 + 36 + 64 float64) at once in phase 1, K34's footprint; P beside them would
 // not fit, so they keep P in LDS in K31's [element][lane] layout (SkCov: 72 KB per workgroup beside the model's 20 KB at
@@ -48,10 +62,12 @@ struct SmoothArgs {
   int32_t *flags;
   int64_t total;                                   // B N
   int M, D, Dy;
+  uint32_t N;                                      // K42 only: the row of a trajectory
+  const uint8_t *observed_next;                    // K42: [B,Dy] of time t+1, nonzero = observed; NULL in the unmasked instantiations
 };
 
 // LDS: the staged model (with cross_out), then, for DP == 8, [TP][256] covariances
-template <int DP, int DYP>
+template <int DP, int DYP, bool Masked>
 __global__ __launch_bounds__(kSkBlock) void switching_smooth_kernel(const SmoothArgs a) {
   extern __shared__ __attribute__((aligned(16))) double ss_smem[];
   constexpr int kPer = sk_per_regime(DP, DYP);
@@ -191,7 +207,8 @@ __global__ __launch_bounds__(kSkBlock) void switching_smooth_kernel(const Smooth
 #pragma unroll
   for (int i = 0; i < DYP; ++i) {
     if (i) SK_REREAD_LDS();
-    const double rho = 1.0 / r2[i];
+    double rho = 1.0 / r2[i];
+    if constexpr (Masked) rho = (i < Dy && a.observed_next[(n / a.N) * Dy + i] != 0) ? rho : 0.0;
     double Gc[DP];
 #pragma unroll
     for (int l = 0; l < DP; ++l) Gc[l] = Cm[i * DP + l] * rho;
@@ -232,32 +249,39 @@ __global__ __launch_bounds__(kSkBlock) void switching_smooth_kernel(const Smooth
   }
 }
 
-template <int DP, int DYP>
+template <int DP, int DYP, bool Masked>
 static bool ss_launch(dim3 grid, size_t lds, hipStream_t s, const SmoothArgs &a) {
   // the 8-wide instantiations (72 KB of covariances beside the model) need the limit raised, as K31's
   if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_smooth_kernel<DP, DYP>),
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_smooth_kernel<DP, DYP, Masked>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return false;
-  hipLaunchKernelGGL((switching_smooth_kernel<DP, DYP>), grid, dim3(kSkBlock), lds, s, a);
+  hipLaunchKernelGGL((switching_smooth_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
   return true;
 }
 
-template <int DP>
+template <int DP, bool Masked>
 static bool ss_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const SmoothArgs &a) {
-  if (dyp == 2) return ss_launch<DP, 2>(grid, lds, s, a);
-  if (dyp == 4) return ss_launch<DP, 4>(grid, lds, s, a);
-  return ss_launch<DP, 8>(grid, lds, s, a);
+  if (dyp == 2) return ss_launch<DP, 2, Masked>(grid, lds, s, a);
+  if (dyp == 4) return ss_launch<DP, 4, Masked>(grid, lds, s, a);
+  return ss_launch<DP, 8, Masked>(grid, lds, s, a);
 }
 
-}  // namespace aesmc
+template <bool Masked>
+static bool ss_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const SmoothArgs &a) {
+  if (dp == 2) return ss_launch_dy<2, Masked>(dyp, grid, lds, s, a);
+  if (dp == 4) return ss_launch_dy<4, Masked>(dyp, grid, lds, s, a);
+  return ss_launch_dy<8, Masked>(dyp, grid, lds, s, a);
+}
 
-extern "C" int aesmc_switching_smooth_combine(const aesmc_switching_model *model, const int32_t *regime_next,
-                                              const double *mean, const double *cov, const double *factor,
-                                              const double *lambda, const double *omega_next, const double *cov_next,
-                                              double *mean_out, double *cov_out, double *cross_out, int32_t *flags,
-                                              int64_t B, int64_t N, int64_t D, void *stream) {
-  using namespace aesmc;
+// K36, and K42 (`masked`: observed_next [B,Dy] given, which only the cross-covariance reads): one set of checks, one launch
+static int ss_combine(bool masked, const uint8_t *observed_next, const aesmc_switching_model *model,
+                      const int32_t *regime_next, const double *mean, const double *cov, const double *factor,
+                      const double *lambda, const double *omega_next, const double *cov_next, double *mean_out,
+                      double *cov_out, double *cross_out, int32_t *flags, int64_t B, int64_t N, int64_t D, void *stream) {
+  if (masked && (observed_next == nullptr || cross_out == nullptr || (const void *)observed_next == mean_out ||
+                 (const void *)observed_next == cov_out || (const void *)observed_next == cross_out))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (mean == nullptr || cov == nullptr || factor == nullptr || lambda == nullptr || mean_out == nullptr ||
       cov_out == nullptr || B < 0 || N < 0 || D < 1)
     return AESMC_ERR_INVALID_ARGUMENT;
@@ -295,16 +319,37 @@ extern "C" int aesmc_switching_smooth_combine(const aesmc_switching_model *model
   }
   a.regime_next = regime_next;
   a.mean = mean, a.cov = cov, a.factor = factor, a.lambda = lambda, a.omega_next = omega_next, a.cov_next = cov_next;
+  a.observed_next = masked ? observed_next : nullptr;
   a.mean_out = mean_out, a.cov_out = cov_out, a.cross_out = cross_out;
   a.flags = flags;
-  a.total = B * N;
+  a.total = B * N, a.N = (uint32_t)N;
   a.D = (int)D;
   const int dp = sk_pad(D), dyp = cross ? sk_pad(model->Dy) : 2;      // (without cross_out nothing of extent Dy exists)
   const size_t lds = ((size_t)a.M * sk_per_regime(dp, dyp) + (sk_cov_in_lds(dp) ? (size_t)(dp * (dp + 1) / 2) * kSkBlock : 0)) *
                      sizeof(double);
   const dim3 grid((unsigned)((a.total + kSkBlock - 1) / kSkBlock));
   hipStream_t s = (hipStream_t)stream;
-  const bool launched = dp == 2 ? ss_launch_dy<2>(dyp, grid, lds, s, a)
-                                : dp == 4 ? ss_launch_dy<4>(dyp, grid, lds, s, a) : ss_launch_dy<8>(dyp, grid, lds, s, a);
+  const bool launched = masked ? ss_launch_d<true>(dp, dyp, grid, lds, s, a) : ss_launch_d<false>(dp, dyp, grid, lds, s, a);
   return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+}
+
+}  // namespace aesmc
+
+extern "C" int aesmc_switching_smooth_combine(const aesmc_switching_model *model, const int32_t *regime_next,
+                                              const double *mean, const double *cov, const double *factor,
+                                              const double *lambda, const double *omega_next, const double *cov_next,
+                                              double *mean_out, double *cov_out, double *cross_out, int32_t *flags,
+                                              int64_t B, int64_t N, int64_t D, void *stream) {
+  return aesmc::ss_combine(false, nullptr, model, regime_next, mean, cov, factor, lambda, omega_next, cov_next, mean_out,
+                           cov_out, cross_out, flags, B, N, D, stream);
+}
+
+extern "C" int aesmc_switching_masked_smooth_combine(const aesmc_switching_model *model, const int32_t *regime_next,
+                                                     const double *mean, const double *cov, const double *factor,
+                                                     const double *lambda, const double *omega_next, const double *cov_next,
+                                                     const uint8_t *observed_next, double *mean_out, double *cov_out,
+                                                     double *cross_out, int32_t *flags, int64_t B, int64_t N, int64_t D,
+                                                     void *stream) {
+  return aesmc::ss_combine(true, observed_next, model, regime_next, mean, cov, factor, lambda, omega_next, cov_next, mean_out,
+                           cov_out, cross_out, flags, B, N, D, stream);
 }

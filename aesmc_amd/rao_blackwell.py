@@ -57,6 +57,18 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                and K38 (`aesmc_switching_kalman_conditional_step`: K31 with that slot's regime pinned)
     switching_particle_gibbs   the chain of such sweeps; its paths are what `switching_state_smooth` takes
                                (examples/slds_gibbs.py: Gibbs over Pi with Dirichlet rows)
+    switching_forecast         the predictive distributions of the steps after the last observation, from either filter's
+                               last stored system: steps with nothing observed
+
+Missing observations: every function above takes `observed=`, per timestep None or a torch.bool [batch_size, Dy] mask.  For a
+batch row a step is then the step of the model with that row's unmeasured components deleted from C, d, r and y — exact, as
+a Kalman filter treats a gap: no innovation from an unmeasured component, the prediction where nothing was measured.  The
+three kernels that read y have a masked form each (K39 `aesmc_switching_kalman_masked_step`, K40
+`aesmc_switching_masked_lookahead`, K41 `aesmc_switching_masked_information_step`: the same bodies with the deleted rows of
+the innovation selected to those of the identity), and so has K36, which reads no y but adds the information C^T R^-1 C of
+y_{t+1} to its cross-covariance (K42 `aesmc_switching_masked_smooth_combine`: only the measured components add theirs).
+The value of y at an unmeasured position is never used and may be NaN.
+A NaN at a MEASURED position is still an error.  The contract is `aesmc_amd.testing.switching_missing`.
 
 The reference has no counterpart; this module adds to its interface and changes none of it.
 """
@@ -73,7 +85,8 @@ from . import statistics
 MAX_LATENT_DIM, MAX_OBSERVATION_DIM, MAX_REGIMES = 8, 8, 16      # aesmc_switching_max_*() of the library
 _COVERED = ("covered: switching linear-Gaussian models with at most {} regimes, a latent of at most {} values and an "
             "observation of at most {} values, constant in time; observations [batch_size, Dy] of float32 or float64 on "
-            "the HIP device".format(MAX_REGIMES, MAX_LATENT_DIM, MAX_OBSERVATION_DIM))
+            "the HIP device, with an optional torch.bool mask of the same shape per timestep (observed=) for components "
+            "that were not measured".format(MAX_REGIMES, MAX_LATENT_DIM, MAX_OBSERVATION_DIM))
 
 
 def _refuse(what):
@@ -84,7 +97,8 @@ class SwitchingLinearGaussian(torch.nn.Module):
     """A switching linear-Gaussian state-space model with M regimes, latent z in R^D and observation y in R^Dy.
 
     pi0 [M], Pi [M,M] (rows: from-regime); m0 [D], s0 (one value or D); A [M,D,D], b [M,D], q [M,D]; C [M,Dy,D], d [M,Dy],
-    r [M,Dy].  A leading extent of 1 in place of M means shared across regimes.  Everything is held as a float64 buffer
+    r [M,Dy].  A leading extent of 1 in place of M means shared across regimes.  Every component of y_t is part of the model;
+    which of them were measured at a step is the filters' `observed=`, not the model's.  Everything is held as a float64 buffer
     (`.to(device)` moves the model).  The filters are not differentiable and the buffers are no parameters: a model is
     learned by EM — `switching_smooth_states` gives the E-step's smoothed moments E[z_t z_t^T | y], E[z_{t+1} z_t^T | y] and
     regime trajectories, the M-step builds a new model from them (examples/slds_em.py)."""
@@ -243,6 +257,31 @@ def _check_observations(name, provider, observations, model, num_particles):
     return batch_size, device
 
 
+def _observed_steps(name, observed, observations):
+    """time -> the keywords of that step's provider calls: {} where the step is fully observed (today's entries and
+    results, bit for bit), {"observed": mask} where a mask is given (the masked entries K39, K40, K41).  observed: None, or
+    a length-T sequence whose entries are None or torch.bool tensors of the observation's shape on its device; ValueError
+    otherwise.  Called once the observations are validated; reads nothing from the device."""
+    if observed is None:
+        return lambda time: {}
+    try:
+        length = len(observed)
+    except TypeError:
+        length = -1
+    if length != len(observations):
+        raise ValueError("{}: observed must be None or hold one entry per timestep ({}), got {}".format(
+            name, len(observations), "{} entries".format(length) if length >= 0 else type(observed).__name__))
+    shape, device = tuple(observations[0].shape), observations[0].device
+    for time in range(length):
+        mask = observed[time]
+        if mask is not None and not (torch.is_tensor(mask) and mask.dtype == torch.bool and tuple(mask.shape) == shape and
+                                     mask.device == device):
+            raise ValueError("{}: observed[{}] must be None or {} torch.bool on {}, got {}".format(
+                name, time, shape, device, "{} {} on {}".format(tuple(mask.shape), mask.dtype, mask.device)
+                if torch.is_tensor(mask) else type(mask).__name__))
+    return lambda time: {} if observed[time] is None else {"observed": observed[time]}
+
+
 def _regime_draws(name, regime_uniforms, shape, device):
     """time -> the step's regime uniforms: fresh from torch's device generator, or the replayed tensor, validated."""
     def draw(time):
@@ -272,7 +311,7 @@ def _resampling_uniforms(feed, stratified, batch_size, num_particles, num_timest
 
 
 def switching_filter(observations, model, num_particles, resampling=None, regime_uniforms=None, return_moments=False,
-                     return_latents=False):
+                     return_latents=False, observed=None):
     """Runs the Rao-Blackwellised particle filter of a `SwitchingLinearGaussian`.
 
     observations: length-T sequence of [batch_size, Dy] tensors (float32 or float64) on the model's device.
@@ -287,6 +326,12 @@ def switching_filter(observations, model, num_particles, resampling=None, regime
     return_moments: also filtered_mean [T,batch_size,D], filtered_covariance [T,batch_size,D,D] (the mixture's: sum_k w_k
         (P_k + m_k m_k^T) - mean mean^T) and regime_probabilities [T,batch_size,M].
     return_latents: also `latents`: the regime genealogy (`inference.get_resampled_latents` of the stored regimes).
+    observed: None — every component of every y_t was measured; or a length-T sequence whose entries are None (that step
+        fully observed) or torch.bool [batch_size, Dy] tensors on the device, True where the component was measured.  For
+        batch row b a step is then the step of the model with that row's unmeasured components deleted from C, d, r and
+        y (the masked kernels K39 - K41): a component that was not measured contributes no innovation, a step with
+        nothing measured is the prediction (log-weight 0).  The value of y at an unmeasured position is never used and may
+        be NaN or Inf.  None, or only None entries, is today's path bit for bit.
 
     Returns a dict: log_marginal_likelihood [batch_size] float64 (unbiased for p(y_0..y_{T-1}); exact for M = 1); regimes (T
     int32 [batch_size, K]), means (T float64 [batch_size, K, D]), covariances (T float64 [batch_size, K, D(D+1)/2]: packed
@@ -306,6 +351,7 @@ def switching_filter(observations, model, num_particles, resampling=None, regime
             ops = model.operands()      # validation, expansion and the cumulative rows: once, before the loop
             M = model.num_regimes
             batch_size, device = _check_observations("switching_filter", provider, observations, model, num_particles)
+            mask = _observed_steps("switching_filter", observed, observations)
             draw = _regime_draws("switching_filter", regime_uniforms, (batch_size, num_particles), device)
             log_z = torch.zeros(batch_size, dtype=torch.float64, device=device)
             regimes, means, covariances, log_weights, ancestral = [], [], [], [], []
@@ -318,7 +364,7 @@ def switching_filter(observations, model, num_particles, resampling=None, regime
                     log_z = log_z + (lse.to(torch.float64) - math.log(num_particles))
                     ancestral.append(index)
                 regime, mean, cov, log_w = provider.switching_kalman_step(ops, state, index, draw(time),
-                                                                          observations[time])
+                                                                          observations[time], **mask(time))
                 state = (regime, mean, cov)
                 regimes.append(regime), means.append(mean), covariances.append(cov), log_weights.append(log_w)
             log_z = log_z + (_ops.row_logsumexp(log_weights[-1]).to(torch.float64) - math.log(num_particles))
@@ -340,12 +386,13 @@ def switching_filter(observations, model, num_particles, resampling=None, regime
 
 
 def adapted_switching_filter(observations, model, num_particles, resampling=None, regime_uniforms=None,
-                             return_moments=False, return_latents=False):
+                             return_moments=False, return_latents=False, observed=None):
     """Runs the fully adapted (look-ahead) Rao-Blackwellised filter of a `SwitchingLinearGaussian`: every step resamples on
     the exact first-stage weights p(y_t | history) and draws the regime from its exact posterior p(s_t | history, y_t).
 
     Arguments, validation, refusals and feeds as `switching_filter` (T - 1 blocks of resampling uniforms, T of regime
-    uniforms).
+    uniforms); `observed` as there too (K40 and K39 in place of K32 and K33): at a step where a row measured nothing its
+    first-stage weights are all equal and the regime is drawn from the transition's row.
 
     Returns a dict: log_marginal_likelihood [batch_size] float64 (unbiased for p(y_0..y_{T-1}); exact for M = 1 and, for any
     K, at T = 1); regimes (T int32 [batch_size, K]), means, covariances (packed, as `switching_filter`'s) — the T stored,
@@ -366,6 +413,7 @@ def adapted_switching_filter(observations, model, num_particles, resampling=None
             M = model.num_regimes
             batch_size, device = _check_observations("adapted_switching_filter", provider, observations, model,
                                                      num_particles)
+            mask = _observed_steps("adapted_switching_filter", observed, observations)
             draw = _regime_draws("adapted_switching_filter", regime_uniforms, (batch_size, num_particles), device)
             log_pi0, log_Pi = torch.log(ops["pi0"]), torch.log(ops["Pi"])      # (-inf where a probability is 0) once
             log_z = torch.zeros(batch_size, dtype=torch.float64, device=device)
@@ -374,7 +422,7 @@ def adapted_switching_filter(observations, model, num_particles, resampling=None
             for time in range(num_timesteps):
                 regime_u = draw(time)      # (a replayed tensor of the wrong shape is refused before the step's launches)
                 log_w, cdf = provider.switching_lookahead(ops, log_pi0 if time == 0 else log_Pi, state, observations[time],
-                                                          num_particles=num_particles)
+                                                          num_particles=num_particles, **mask(time))
                 if time == 0:
                     index, lse = None, _ops.row_logsumexp(log_w)
                 else:
@@ -383,7 +431,8 @@ def adapted_switching_filter(observations, model, num_particles, resampling=None
                     index = _kernels.as_index(index)
                     ancestral.append(index)
                 log_z = log_z + (lse.to(torch.float64) - math.log(num_particles))
-                regime, mean, cov, _ = provider.switching_kalman_draw(ops, state, index, regime_u, cdf, observations[time])
+                regime, mean, cov, _ = provider.switching_kalman_draw(ops, state, index, regime_u, cdf, observations[time],
+                                                                      **mask(time))
                 state = (regime, mean, cov)
                 regimes.append(regime), means.append(mean), covariances.append(cov), first_stage.append(log_w)
             out = {"log_marginal_likelihood": log_z, "regimes": regimes, "means": means, "covariances": covariances,
@@ -431,7 +480,8 @@ def _stored_systems(name, filtered, num_timesteps, batch_size, latent_dim, devic
     return regimes, means, covariances, log_weights, num_particles
 
 
-def switching_backward_simulate(filtered, model, observations, num_trajectories=None, uniforms=None, return_indices=False):
+def switching_backward_simulate(filtered, model, observations, num_trajectories=None, uniforms=None, return_indices=False,
+                                observed=None):
     """Rao-Blackwellised backward simulation over the stored systems of one run of `switching_filter` or
     `adapted_switching_filter`: regime trajectories from the joint smoothing distribution p(s_{0:T-1} | y_{0:T-1}).
 
@@ -445,6 +495,7 @@ def switching_backward_simulate(filtered, model, observations, num_trajectories=
         sequence of such blocks, `uniforms[t]` for the draw at time t (replay).  None inside `distributed.shard_scope`
         raises NotImplementedError for that function's reason.
     return_indices: also `indices`: which stored particle each trajectory passes through, T int64 [batch_size, N].
+    observed: `switching_filter`'s, and the one the filter ran with (K41 in place of K34).
 
     At t = T-1 a trajectory draws a stored particle by its weight (K21).  For t = T-2 .. 0 it takes the quadratic summary
     of its future observations one step back under its regime at t+1 (K34), every stored particle of step t is scored
@@ -477,6 +528,7 @@ def switching_backward_simulate(filtered, model, observations, num_trajectories=
             # (the observations first, for one particle: what the stored systems must match; their number is checked
             # with the number of trajectories below)
             batch_size, device = _check_observations(name, provider, observations, model, 1)
+            mask = _observed_steps(name, observed, observations)
             regimes, means, covariances, log_weights, num_particles = _stored_systems(
                 name, filtered, num_timesteps, batch_size, D, device)
             num_trajectories = num_particles if num_trajectories is None else int(num_trajectories)
@@ -522,7 +574,7 @@ def switching_backward_simulate(filtered, model, observations, num_trajectories=
             for time in range(last - 1, -1, -1):
                 u = block(time)      # (a replayed block of the wrong shape is refused before the step's launches)
                 omega, lam, c, factor = provider.switching_information_step(ops, drawn[time + 1], info,
-                                                                            observations[time + 1])
+                                                                            observations[time + 1], **mask(time + 1))
                 info = (omega, lam, c)
                 scores = provider.switching_backward_scores(log_Pi, drawn[time + 1], factor, lam,
                                                             (regimes[time], means[time], covariances[time]),
@@ -544,12 +596,13 @@ def switching_backward_simulate(filtered, model, observations, num_trajectories=
     return out
 
 
-def switching_smooth(observations, model, num_particles, num_trajectories=None, resampling=None, lookahead=False):
+def switching_smooth(observations, model, num_particles, num_trajectories=None, resampling=None, lookahead=False,
+                     observed=None):
     """Runs `switching_filter` (lookahead: `adapted_switching_filter`) and then `switching_backward_simulate` over what it
-    stored.  Returns (that function's dict, the filter's log_marginal_likelihood [batch_size])."""
+    stored, both with `observed`.  Returns (that function's dict, the filter's log_marginal_likelihood [batch_size])."""
     run = adapted_switching_filter if lookahead else switching_filter
-    filtered = run(observations, model, num_particles, resampling=resampling)
-    out = switching_backward_simulate(filtered, model, observations, num_trajectories=num_trajectories)
+    filtered = run(observations, model, num_particles, resampling=resampling, observed=observed)
+    out = switching_backward_simulate(filtered, model, observations, num_trajectories=num_trajectories, observed=observed)
     return out, filtered["log_marginal_likelihood"]
 
 
@@ -569,20 +622,20 @@ def _check_regimes(name, regimes, num_timesteps, batch_size, device):
     return shape[1]
 
 
-def _conditional_filter(provider, ops, observations, regimes, num_regimes):
+def _conditional_filter(provider, ops, observations, regimes, num_regimes, mask):
     """(means, covariances, log_likelihood, whether a regime was out of range: a device flag) of K31 forced along `regimes`
-    — `testing.rao_blackwell._forced`: every cumulative row (1/M, .., 1), the uniform (s + 1/2) / M, no ancestors.  Reads no
-    flags and nothing else from the device."""
+    — `testing.rao_blackwell._forced`: every cumulative row (1/M, .., 1), the uniform (s + 1/2) / M, no ancestors; `mask`:
+    `_observed_steps`'s.  Reads no flags and nothing else from the device."""
     device = regimes[0].device
     edges = (torch.arange(num_regimes, dtype=torch.float64, device=device) + 1.0) / num_regimes
     forced = dict(ops, cdf0=edges, cdf=edges.expand(num_regimes, num_regimes).contiguous())
     log_likelihood = torch.zeros(regimes[0].shape, dtype=torch.float64, device=device)
     outside = torch.zeros((), dtype=torch.bool, device=device)
     means, covariances, state = [], [], None
-    for regime, observation in zip(regimes, observations):
+    for time, (regime, observation) in enumerate(zip(regimes, observations)):
         outside = outside | ((regime < 0) | (regime >= num_regimes)).any()
         uniforms = (regime.to(torch.float64) + 0.5) / num_regimes
-        drawn, mean, cov, log_w = provider.switching_kalman_step(forced, state, None, uniforms, observation)
+        drawn, mean, cov, log_w = provider.switching_kalman_step(forced, state, None, uniforms, observation, **mask(time))
         state = (drawn, mean, cov)
         log_likelihood = log_likelihood + log_w
         means.append(mean), covariances.append(cov)
@@ -599,7 +652,7 @@ def _finish_conditional(name, provider, device, outside, log_likelihood):
         raise FloatingPointError("log_weight contains nan element(s)")
 
 
-def _prepare_conditional(name, provider, observations, model, regimes):
+def _prepare_conditional(name, provider, observations, model, regimes, observed):
     num_timesteps = len(observations)
     if num_timesteps == 0:
         raise ValueError("{}: observations must hold at least one timestep".format(name))
@@ -611,14 +664,14 @@ def _prepare_conditional(name, provider, observations, model, regimes):
     if batch_size * num_trajectories > 0x7fffffff // (MAX_LATENT_DIM * MAX_LATENT_DIM):
         _refuse("{} trajectories in {} batch rows (batch_size * num_trajectories * D^2 beyond 32-bit element arithmetic)"
                 .format(num_trajectories, batch_size))
-    return ops, num_timesteps, batch_size, num_trajectories, device
+    return ops, num_timesteps, batch_size, num_trajectories, device, _observed_steps(name, observed, observations)
 
 
-def conditional_kalman_filter(observations, model, regimes):
+def conditional_kalman_filter(observations, model, regimes, observed=None):
     """The exact Kalman filter of z given a regime path per trajectory: K31 with the regime FORCED (every cumulative row
     replaced by (1/M, .., 1) and the uniform by (s + 1/2) / M), no ancestors, one particle per trajectory.
 
-    observations, model: as `switching_filter`'s.  regimes: T int32 [batch_size, N] tensors on the device — what
+    observations, model, observed: as `switching_filter`'s.  regimes: T int32 [batch_size, N] tensors on the device — what
     `switching_backward_simulate` returns, or any paths of the caller's.
 
     Returns a dict: means (T float64 [batch_size, N, D]), covariances (T float64 [batch_size, N, D(D+1)/2], packed) — the
@@ -633,15 +686,15 @@ def conditional_kalman_filter(observations, model, regimes):
     provider = _kernels.get()
     try:
         with torch.no_grad(), _syncfree.scope():
-            ops, num_timesteps, batch_size, num_trajectories, device = _prepare_conditional(name, provider, observations,
-                                                                                            model, regimes)
+            ops, num_timesteps, batch_size, num_trajectories, device, mask = _prepare_conditional(
+                name, provider, observations, model, regimes, observed)
             D = model.latent_dim
             if num_trajectories == 0:
                 empty = lambda *tail: torch.empty((batch_size, 0) + tail, dtype=torch.float64, device=device)
                 return {"means": [empty(D) for _ in range(num_timesteps)],
                         "covariances": [empty(D * (D + 1) // 2) for _ in range(num_timesteps)], "log_likelihood": empty()}
             means, covariances, log_likelihood, outside = _conditional_filter(provider, ops, observations, regimes,
-                                                                              model.num_regimes)
+                                                                              model.num_regimes, mask)
             _finish_conditional(name, provider, device, outside, log_likelihood)
     except BaseException:
         inference._discard_pending_flags()
@@ -649,12 +702,13 @@ def conditional_kalman_filter(observations, model, regimes):
     return {"means": means, "covariances": covariances, "log_likelihood": log_likelihood}
 
 
-def switching_state_smooth(observations, model, regimes, return_cross_moments=False, return_trajectories=False):
+def switching_state_smooth(observations, model, regimes, return_cross_moments=False, return_trajectories=False,
+                           observed=None):
     """The smoothed continuous state of a `SwitchingLinearGaussian` from regime trajectories: along a trajectory the model is
     linear-Gaussian and its smoother exact, and the estimate is the average of those exact smoothers over the trajectories
     (Fong, Godsill, Doucet & West 2002; Lindsten, Bunch, Saerkkae, Schoen & Godsill 2016) — the regimes alone are sampled.
 
-    observations, model: as `switching_filter`'s.  regimes: T int32 [batch_size, N] on the device: equally weighted
+    observations, model, observed: as `switching_filter`'s.  regimes: T int32 [batch_size, N] on the device: equally weighted
     trajectories, `switching_backward_simulate`'s (or any paths: the result is then the exact smoother given them).
 
     `conditional_kalman_filter` runs forward; for t = T-2 .. 0 K34 takes the trajectory's information one step back under its
@@ -678,8 +732,8 @@ def switching_state_smooth(observations, model, regimes, return_cross_moments=Fa
     want_cross = bool(return_cross_moments or return_trajectories)
     try:
         with torch.no_grad(), _syncfree.scope():
-            ops, num_timesteps, batch_size, num_trajectories, device = _prepare_conditional(name, provider, observations,
-                                                                                            model, regimes)
+            ops, num_timesteps, batch_size, num_trajectories, device, mask = _prepare_conditional(
+                name, provider, observations, model, regimes, observed)
             D = model.latent_dim
             last = num_timesteps - 1
             if num_trajectories == 0:
@@ -695,19 +749,21 @@ def switching_state_smooth(observations, model, regimes, return_cross_moments=Fa
                                cross_covariances=[empty(D, D) for _ in range(last)])
                 return out
             filtered_means, filtered_covs, log_likelihood, outside = _conditional_filter(provider, ops, observations, regimes,
-                                                                                         model.num_regimes)
+                                                                                         model.num_regimes, mask)
             means, covs, crosses = [None] * num_timesteps, [None] * num_timesteps, [None] * last
             means[last], covs[last] = filtered_means[last], filtered_covs[last]
             info = None
             for time in range(last - 1, -1, -1):
                 omega_next = None if info is None else info[0]
                 omega, lam, c, factor = provider.switching_information_step(ops, regimes[time + 1], info,
-                                                                            observations[time + 1])
+                                                                            observations[time + 1], **mask(time + 1))
                 info = (omega, lam, c)
                 if want_cross:
+                    # (K36 adds the information of y_{t+1} to Om_{t+1}: under a mask only its observed components', K42)
+                    seen = {"observed_next": mask(time + 1)["observed"]} if mask(time + 1) else {}
                     means[time], covs[time], crosses[time] = provider.switching_smooth_combine(
                         ops, regimes[time + 1], (filtered_means[time], filtered_covs[time]), factor, lam, omega_next,
-                        covs[time + 1])
+                        covs[time + 1], **seen)
                 else:
                     means[time], covs[time], _ = provider.switching_smooth_combine(
                         None, None, (filtered_means[time], filtered_covs[time]), factor, lam)
@@ -731,23 +787,23 @@ def switching_state_smooth(observations, model, regimes, return_cross_moments=Fa
 
 
 def switching_smooth_states(observations, model, num_particles, num_trajectories=None, resampling=None, lookahead=False,
-                            return_trajectories=False):
+                            return_trajectories=False, observed=None):
     """Runs `switching_filter` (lookahead: `adapted_switching_filter`), `switching_backward_simulate` over what it stored and
     `switching_state_smooth` along the drawn trajectories with return_cross_moments (K34 runs once more along the drawn
     regimes: B N lanes, a tenth of a backward step).  Returns (a dict: `switching_backward_simulate`'s regimes and
     smoothed_regime_probabilities with `switching_state_smooth`'s smoothed_mean, smoothed_covariance, smoothed_cross_moment
     and log_likelihood — with return_trajectories its per-trajectory means, covariances and cross_covariances too —, the
-    filter's log_marginal_likelihood [batch_size])."""
+    filter's log_marginal_likelihood [batch_size]).  `observed` (`switching_filter`'s) goes to all three."""
     run = adapted_switching_filter if lookahead else switching_filter
-    filtered = run(observations, model, num_particles, resampling=resampling)
-    out = switching_backward_simulate(filtered, model, observations, num_trajectories=num_trajectories)
+    filtered = run(observations, model, num_particles, resampling=resampling, observed=observed)
+    out = switching_backward_simulate(filtered, model, observations, num_trajectories=num_trajectories, observed=observed)
     out.update(switching_state_smooth(observations, model, out["regimes"], return_cross_moments=True,
-                                      return_trajectories=return_trajectories))
+                                      return_trajectories=return_trajectories, observed=observed))
     return out, filtered["log_marginal_likelihood"]
 
 
 def conditional_switching_filter(observations, model, num_particles, reference, ancestor_sampling=True, uniforms=None,
-                                 regime_uniforms=None, return_particles=False):
+                                 regime_uniforms=None, return_particles=False, observed=None):
     """One sweep of particle Gibbs on the regimes of a `SwitchingLinearGaussian`: a Rao-Blackwellised conditional particle
     filter whose slot num_particles - 1 carries the regime path `reference`, then one draw of a path from the final weights
     along the ancestors.  The kernel leaves p(s_{0:T-1} | y_{0:T-1}) invariant for ANY number of particles (Andrieu, Doucet &
@@ -772,6 +828,7 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
     return_particles: also a dict with the stored systems — regimes (T int32 [batch_size, K], the reference in slot K-1),
         means, covariances (packed), log_weights — and ancestral_indices ((T-1) int64 [batch_size, K]) and indices (T int64
         [batch_size]: the slot the new path passes through).
+    observed: `switching_filter`'s (K41 along the reference, K39 with the pinned regime in place of K38).
 
     Returns T int32 [batch_size] tensors, the new path.  With return_particles: (path, particles).
 
@@ -812,6 +869,7 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
             ops = model.operands()
             M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
             batch_size, device = _check_observations(name, provider, observations, model, num_particles)
+            mask = _observed_steps(name, observed, observations)
             if not provider.switching_conditional_covers(observations[0], M, D, Dy, num_particles):
                 _refuse("num_particles = {} with a latent of {} values (conditional resampling keeps its running sums in "
                         "LDS: at most 8192 particles, 4096 for a latent of more than 4 values)".format(num_particles, D))
@@ -836,7 +894,7 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
                 info = None
                 for time in range(num_timesteps - 1, 0, -1):
                     omega, lam, c, factor = provider.switching_information_step(ops, reference[time].unsqueeze(1), info,
-                                                                                observations[time])
+                                                                                observations[time], **mask(time))
                     info = (omega, lam, c)
                     information[time] = (factor[:, 0], lam[:, 0])
             regimes, means, covariances, log_weights, ancestral = [], [], [], [], []
@@ -850,7 +908,8 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
                     # (a failed draw is position K: the step reads particle K-1 in its place, the flag raises at the end)
                     index = index.clamp(max=pinned)
                 regime, mean, cov, log_w = provider.switching_kalman_conditional_step(ops, state, index, draw(time),
-                                                                                      reference[time], observations[time])
+                                                                                      reference[time], observations[time],
+                                                                                      **mask(time))
                 state = (regime, mean, cov)
                 regimes.append(regime), means.append(mean), covariances.append(cov), log_weights.append(log_w)
             last, _ = provider.backward_sample(log_weights[-1], None, None, None, block(num_timesteps - 1))
@@ -873,7 +932,7 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
 
 
 def switching_particle_gibbs(observations, model, num_particles, num_sweeps, reference=None, ancestor_sampling=True,
-                             burn_in=0):
+                             burn_in=0, observed=None):
     """Runs `num_sweeps` sweeps of `conditional_switching_filter`, each from the path the one before returned: batch_size
     independent Markov chains on regime paths whose stationary law is p(s_{0:T-1} | y_{0:T-1}) for any num_particles; with
     ancestor sampling 8 .. 64 particles mix.
@@ -881,7 +940,7 @@ def switching_particle_gibbs(observations, model, num_particles, num_sweeps, ref
     reference: the first path, T int32 [batch_size] tensors; None — one trajectory of `switching_smooth` with num_particles
         particles (which consumes numpy's RandomState as `switching_filter` does; the sweeps draw from torch's generator).
     burn_in: the first `burn_in` sweeps are run and not returned.
-    The other arguments are `conditional_switching_filter`'s.
+    The other arguments, `observed` among them, are `conditional_switching_filter`'s.
 
     Returns a dict: regimes (T int32 [batch_size, num_sweeps - burn_in]: regimes[t][b, s] is s_t of chain b after sweep
     burn_in + s — the shape `switching_state_smooth` and `conditional_kalman_filter` take, successive sweeps of a chain being
@@ -891,11 +950,12 @@ def switching_particle_gibbs(observations, model, num_particles, num_sweeps, ref
         raise ValueError("switching_particle_gibbs: 0 <= burn_in < num_sweeps, got burn_in = {} and num_sweeps = {}".format(
             burn_in, num_sweeps))
     if reference is None:
-        drawn, _ = switching_smooth(observations, model, num_particles, num_trajectories=1)
+        drawn, _ = switching_smooth(observations, model, num_particles, num_trajectories=1, observed=observed)
         reference = [regime[:, 0].contiguous() for regime in drawn["regimes"]]
     path, kept = list(reference), []
     for sweep in range(num_sweeps):
-        path = conditional_switching_filter(observations, model, num_particles, path, ancestor_sampling=ancestor_sampling)
+        path = conditional_switching_filter(observations, model, num_particles, path, ancestor_sampling=ancestor_sampling,
+                                            observed=observed)
         if sweep >= burn_in:
             kept.append(path)
     M = model.num_regimes
@@ -905,6 +965,84 @@ def switching_particle_gibbs(observations, model, num_particles, num_sweeps, ref
             torch.nn.functional.one_hot(regime.to(torch.int64).clamp(0, M - 1), M).to(torch.float64).mean(dim=1)
             for regime in regimes])
     return {"regimes": regimes, "smoothed_regime_probabilities": probabilities}
+
+
+def switching_forecast(filtered, model, horizon, regime_uniforms=None):
+    """What comes next: the predictive distributions of steps T .. T + horizon - 1 from the last stored system of one run of
+    `switching_filter` or `adapted_switching_filter`.  A forecast step is the filter's step with nothing observed (K39 under
+    an all-False mask, the identity ancestor): every particle draws its next regime from the transition's row and takes
+    the Kalman prediction; its log-weight is 0, so the weights do not change and nothing is resampled.
+
+    filtered: the dict either filter returned (the last of regimes, means, covariances; with `log_weights` the system is
+        weighted by the last of them, without that key equally).
+    horizon: H >= 1.
+    regime_uniforms: None — torch.rand((batch_size, num_particles), float64) per step on the device; or a length-H sequence
+        of such tensors (replay).
+
+    Returns a dict: regimes (H int32 [batch_size, K]), means (H float64 [batch_size, K, D]), covariances (H float64
+    [batch_size, K, D(D+1)/2], packed) — the predicted particle systems; log_weight [batch_size, K] (the filter's last,
+    unchanged: zeros for an equally weighted system); regime_probabilities [H, batch_size, M], state_mean [H, batch_size, D],
+    state_covariance [H, batch_size, D, D] (`switching_filter`'s three moments of those systems); observation_mean [H,
+    batch_size, Dy] and observation_covariance [H, batch_size, Dy, Dy]: the moments of the mixture of N(C_s m + d_s, C_s P
+    C_s^T + diag(r_s^2)) over the particles (plain torch per particle, the weighted means by K7).
+
+    ValueError for an invalid model, a `filtered` without stored systems, horizon < 1 and regime_uniforms of the wrong length
+    or shape; refusals and flags as `switching_filter`'s, read once at the end.  No host synchronisation inside the loop.
+    Runs under torch.no_grad(): NOT differentiable."""
+    name = "switching_forecast"
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("{}: horizon must be at least 1, got {}".format(name, horizon))
+    if regime_uniforms is not None and len(regime_uniforms) != horizon:
+        raise ValueError("{}: regime_uniforms must hold one tensor per forecast step ({}), got {}".format(
+            name, horizon, len(regime_uniforms)))
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops = model.operands()
+            M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
+            stored = filtered.get("regimes") if isinstance(filtered, dict) else None
+            if not stored or not torch.is_tensor(stored[-1]) or stored[-1].dim() != 2:
+                raise ValueError("{}: filtered must be the dict of switching_filter or adapted_switching_filter".format(name))
+            batch_size, device = stored[-1].size(0), stored[-1].device
+            regimes, means, covariances, log_weights, num_particles = _stored_systems(
+                name, filtered, len(stored), batch_size, D, device)
+            log_weight = log_weights[-1] if log_weights is not None else \
+                torch.zeros((batch_size, num_particles), dtype=torch.float64, device=device)
+            nothing = torch.zeros((batch_size, Dy), dtype=torch.float64, device=device)      # (never read into a chain)
+            unobserved = torch.zeros((batch_size, Dy), dtype=torch.bool, device=device)
+            _check_observations(name, provider, [nothing], model, num_particles)
+            draw = _regime_draws(name, regime_uniforms, (batch_size, num_particles), device)
+            state = (regimes[-1], means[-1], covariances[-1])
+            out_regimes, out_means, out_covs = [], [], []
+            for step in range(horizon):
+                regime, mean, cov, _ = provider.switching_kalman_step(ops, state, None, draw(step), nothing,
+                                                                      observed=unobserved)
+                state = (regime, mean, cov)
+                out_regimes.append(regime), out_means.append(mean), out_covs.append(cov)
+            weights = [log_weight] * horizon
+            state_mean, state_cov, probabilities = _moments(out_regimes, out_means, out_covs, weights, M)
+            observation_mean, observation_cov = [], []
+            for regime, mean, cov in zip(out_regimes, out_means, out_covs):
+                s = regime.to(torch.int64).clamp(0, M - 1)
+                C = ops["C"][s]                                                            # [B,K,Dy,D]
+                center = torch.einsum("bkil,bkl->bki", C, mean) + ops["d"][s]
+                spread = C @ unpack_covariance(cov, D) @ C.transpose(-1, -2) + torch.diag_embed(ops["r"][s] ** 2)
+                second = spread + center.unsqueeze(-1) * center.unsqueeze(-2)
+                average = statistics.empirical_mean(center, log_weight)
+                second = statistics.empirical_mean(second.reshape(batch_size, num_particles, Dy * Dy),
+                                                   log_weight).reshape(-1, Dy, Dy)
+                observation_mean.append(average)
+                observation_cov.append(second - average.unsqueeze(-1) * average.unsqueeze(-2))
+            out = {"regimes": out_regimes, "means": out_means, "covariances": out_covs, "log_weight": log_weight,
+                   "regime_probabilities": probabilities, "state_mean": state_mean, "state_covariance": state_cov,
+                   "observation_mean": torch.stack(observation_mean),
+                   "observation_covariance": torch.stack(observation_cov)}
+            inference._raise_for_flags(provider.read_flags(device))
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
 
 
 class _ZeroFeed:
@@ -917,10 +1055,11 @@ class _ZeroFeed:
         return self.block
 
 
-def kalman_log_likelihood(observations, model):
+def kalman_log_likelihood(observations, model, observed=None):
     """The exact Kalman filter of a one-regime model on the device: `switching_filter` with M = 1 and one particle, where
     nothing is sampled.  Returns (log p(y_0..y_{T-1}) [batch_size] float64, filtered means [T,batch_size,D], filtered
-    covariances [T,batch_size,D,D]).  ValueError if the model has more than one regime."""
+    covariances [T,batch_size,D,D]).  observed: `switching_filter`'s — the Kalman filter with missing observations, still
+    exact.  ValueError if the model has more than one regime."""
     if model.num_regimes != 1:
         raise ValueError("kalman_log_likelihood: the model has {} regimes; the Kalman filter is the one-regime case".format(
             model.num_regimes))
@@ -929,7 +1068,7 @@ def kalman_log_likelihood(observations, model):
     shape = (observations[0].size(0), 1)
     zeros = [torch.zeros(shape, dtype=torch.float64, device=observations[0].device)] * len(observations)
     with inference.uniform_feed(_ZeroFeed(zeros[0][:, 0])):      # one particle: its own ancestor whatever the uniform
-        out = switching_filter(observations, model, 1, resampling="systematic", regime_uniforms=zeros)
+        out = switching_filter(observations, model, 1, resampling="systematic", regime_uniforms=zeros, observed=observed)
     D = model.latent_dim
     return (out["log_marginal_likelihood"], torch.stack([m[:, 0] for m in out["means"]]),
             torch.stack([unpack_covariance(c[:, 0], D) for c in out["covariances"]]))

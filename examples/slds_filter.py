@@ -3,7 +3,7 @@
 covariance of the continuous state given its regime history (kernel K31).
 
     python examples/slds_filter.py [--regimes 2] [--dim 2] [--particles 256] [--batch 8] [--timesteps 200] [--short 6]
-                                   [--lookahead] [--smooth]
+                                   [--lookahead] [--smooth] [--missing FRACTION] [--forecast H]
 
 Simulates a series whose regimes differ in their dynamics, filters it, and prints how often the most probable filtered
 regime is the true one and the error of the filtered mean; then, for a short series, log Z-hat beside the exact log p(y)
@@ -12,7 +12,11 @@ resamples on the exact p(y_t | history) and draws the regime from its exact post
 --smooth the stored systems are smoothed by Rao-Blackwellised backward simulation (`switching_backward_simulate`, kernels
 K34 and K35) and the accuracy of the most probable SMOOTHED regime, which has seen the whole series, is printed beside the
 filtered one; then the continuous state is smoothed along the drawn trajectories (`switching_state_smooth`, kernel K36) and
-the error of the smoothed state mean is printed beside the filtered one's.
+the error of the smoothed state mean is printed beside the filtered one's.  With --missing FRACTION every component of
+every observation is dropped with that probability (NaN is written over it) and the filter runs once more with
+`observed=` (the masked kernels K39 / K40): regime accuracy and state RMSE beside the fully observed run's.  With
+--forecast H the last H steps are held out, the filter runs on the rest and `switching_forecast` predicts them: the RMSE
+of the forecast's observation mean against the held-out observations, beside their own spread and the forecast's.
 """
 import argparse
 import os
@@ -50,6 +54,9 @@ def main():
     ap.add_argument("--lookahead", action="store_true", help="the fully adapted filter: regimes from their exact posterior")
     ap.add_argument("--smooth", action="store_true", help="also smooth: regime accuracy given the whole series")
     ap.add_argument("--trajectories", type=int, default=None, help="backward trajectories per series (default: --particles)")
+    ap.add_argument("--missing", type=float, default=0.0, metavar="FRACTION",
+                    help="also filter with every component dropped with this probability")
+    ap.add_argument("--forecast", type=int, default=0, metavar="H", help="also hold out the last H steps and forecast them")
     args = ap.parse_args()
 
     device = torch.device("cuda", 0)
@@ -73,6 +80,23 @@ def main():
         state = rao_blackwell.switching_state_smooth(observations, model, smoothed["regimes"])
         print("RMSE of the smoothed state mean {:.3f} (filtered: {:.3f})".format(
             (state["smoothed_mean"] - torch.stack(states)).pow(2).mean().sqrt().item(), error))
+    if args.missing > 0:
+        observed = [torch.rand(y.shape, device=device) >= args.missing for y in observations]
+        holes = [torch.where(seen, y, torch.full_like(y, float("nan"))) for y, seen in zip(observations, observed)]
+        gappy = run(holes, model, args.particles, return_moments=True, observed=observed)
+        guess = gappy["regime_probabilities"].argmax(dim=-1)
+        print("with {:.0%} of the components missing: filtered regime = true regime {:.1%} of the time (fully observed: {:.1%}); "
+              "RMSE of the filtered mean {:.3f} (fully observed: {:.3f})".format(
+                  1.0 - torch.stack(observed).double().mean().item(), (guess == torch.stack(regimes)).double().mean().item(),
+                  accuracy, (gappy["filtered_mean"] - torch.stack(states)).pow(2).mean().sqrt().item(), error))
+    if 0 < args.forecast < args.timesteps:
+        H = args.forecast
+        ahead = rao_blackwell.switching_forecast(run(observations[:-H], model, args.particles), model, H)
+        held = torch.stack(observations[-H:])
+        spread = torch.diagonal(ahead["observation_covariance"], dim1=-2, dim2=-1).mean().sqrt().item()
+        print("forecast of the last {} steps: RMSE of the observation mean {:.3f} (the held-out observations' own spread {:.3f}, "
+              "the forecast's standard deviation {:.3f})".format(
+                  H, (ahead["observation_mean"] - held).pow(2).mean().sqrt().item(), held.std().item(), spread))
     short = [y[:1] for y in observations[:args.short]]
     ops = {name: value.cpu().numpy() for name, value in model.operands().items()}
     exact = contract.exact_log_likelihood(ops, [y.cpu().numpy() for y in short])[0]

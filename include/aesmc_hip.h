@@ -86,7 +86,11 @@ extern "C" {
  *                state along a regime trajectory, from the conditional filter and K34 — the two-filter state smoother);
  *                aesmc_switching_conditional_ancestor_index with aesmc_switching_conditional_max_particles,
  *                aesmc_switching_kalman_conditional_step (K37, K38: conditional resampling with ancestor sampling against
- *                K34's information, and K31's step with one slot's regime pinned — particle Gibbs on the regimes).
+ *                K34's information, and K31's step with one slot's regime pinned — particle Gibbs on the regimes);
+ *                aesmc_switching_kalman_masked_step, aesmc_switching_masked_lookahead,
+ *                aesmc_switching_masked_information_step, aesmc_switching_masked_smooth_combine (K39, K40, K41, K42: K31 /
+ *                K33 / K38, K32, K34 and K36 with a per-row mask of the observation's components — missing observations,
+ *                and forecasts as steps with nothing observed).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -848,6 +852,48 @@ int aesmc_switching_kalman_conditional_step(int y_dtype, const aesmc_switching_m
                                             const double *uniforms, const int32_t *pinned_regime, const void *y,
                                             int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
                                             int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K39, K40, K41 — K31 (with its K33 and K38 forms), K32 and K34 under a mask of the observation's components.
+ *   observed: uint8 [B,Dy], nonzero = component i of y[b] was observed (the storage of a contiguous bool tensor).
+ * For batch row b the step is its sibling's on the model with that row's unobserved components deleted from C, d, r and y:
+ *   K39, K40   e_i = o_i ? e_i : 0,  U_i. = o_i ? U_i. : 0,  S_ij = (o_i and o_j) ? S_ij : (i == j ? 1 : 0)  — selections of the
+ *              sibling's chains, after which everything is the sibling's code: a deleted pivot is 1, its reciprocal 1, its
+ *              logarithm 0 (what a padded component's is), and the chains of the kept components gain only products with zeros
+ *   K41        e_i = o_i ? y_i - d_i : 0,  1 / r_i^2 -> o_i ? 1 / r_i^2 : 0,  log r_i^2 dropped where o_i is 0
+ *   constant   n_b = sum_i o[b,i] in place of Dy
+ * With nothing observed K39 is the prediction (log_weight 0, m = m-, P = P-), K40 gives log_weight = logsumexp of the
+ * log-priors' row and its cumulative row, K41 only the transition's part.  y at an unobserved position is never used in a
+ * chain: it may be NaN or Inf.
+ * aesmc_switching_kalman_masked_step: particle_cdf non-NULL is K33's form, pinned_regime non-NULL K38's, both NULL K31's.
+ * Checks, conventions and statuses are the siblings'; besides, observed is not NULL and is none of the outputs
+ * (AESMC_ERR_INVALID_ARGUMENT).  Every check runs before any launch. */
+int aesmc_switching_kalman_masked_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                       const double *mean_in, const double *cov_in, const int64_t *idx,
+                                       const double *uniforms, const double *particle_cdf, const int32_t *pinned_regime,
+                                       const void *y, const uint8_t *observed, int32_t *regime_out, double *mean_out,
+                                       double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
+                                       void *stream);
+int aesmc_switching_masked_lookahead(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
+                                     const int32_t *regime_in, const double *mean_in, const double *cov_in, const void *y,
+                                     const uint8_t *observed, double *log_weight, double *cdf, int32_t *flags, int64_t B,
+                                     int64_t K, void *stream);
+int aesmc_switching_masked_information_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_next,
+                                            const double *omega_in, const double *lambda_in, const double *c_in,
+                                            const void *y, const uint8_t *observed, double *omega_out, double *lambda_out,
+                                            double *c_out, double *factor_out, int32_t *flags, int64_t B, int64_t N,
+                                            void *stream);
+
+/* K42 — K36 under a mask of the observation of time t+1.  K36 reads no observation, but its cross-covariance adds the
+ * information of y_{t+1}, C^T R^-1 C, to Om_{t+1}: under the mask only the observed components add theirs,
+ *   Oh = Om_{t+1} + sum_i (o_i ? 1 / r_j[i]^2 : 0) C_j[i,:]^T C_j[i,:],      o = observed_next[b,:] (uint8 [B,Dy], time t+1)
+ * — K41's rule; the smoothed mean and covariance do not depend on it.  cross_out and observed_next are not optional here
+ * (without a cross-covariance the mask is not read: that is K36 itself), and observed_next is none of the outputs
+ * (AESMC_ERR_INVALID_ARGUMENT); everything else, the checks and statuses as K36's. */
+int aesmc_switching_masked_smooth_combine(const aesmc_switching_model *model, const int32_t *regime_next, const double *mean,
+                                          const double *cov, const double *factor, const double *lambda,
+                                          const double *omega_next, const double *cov_next, const uint8_t *observed_next,
+                                          double *mean_out, double *cov_out, double *cross_out, int32_t *flags, int64_t B,
+                                          int64_t N, int64_t D, void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *

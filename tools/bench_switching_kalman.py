@@ -6,7 +6,12 @@ that composition once more alone: they are what its time consists of.  Everythin
 the median per call is reported with the spread, K31 beside the bytes its launch moves and the fraction of the HBM peak
 they make.
     python tools/bench_switching_kalman.py [--out FILE] [B,K,M,D,Dy ...]
-(default: 1024,4096,4,4,4 and 1024,4096,4,8,8; the report goes to profiles/switching_kalman.txt)"""
+(default: 1024,4096,4,4,4 and 1024,4096,4,8,8; the report goes to profiles/switching_kalman.txt)
+    python tools/bench_switching_kalman.py --missing [--parent-report FILE] [--out FILE] [B,K,M,D,Dy ...]
+the masked step K39 (aesmc_switching_kalman_masked_step) beside K31 on the same inputs in the same run: under a mask that
+observes everything (K39 then computes what K31 does), one drawn with p = 0.6 per component, and one that observes nothing
+(the prediction).  --parent-report: a report this tool wrote on the commit before K39 in the same session, whose K31 lines
+are quoted beside.  A measurement, no threshold; the report goes to profiles/switching_missing.txt."""
 import os
 import sys
 
@@ -76,13 +81,68 @@ def composition(ops, regime, mean, full_cov, idx, u, y):
             log_w)
 
 
+def missing_leg(shapes, parent_report):
+    """The report of --missing: K31 and K39 under three masks, per shape."""
+    lines = ["tools/bench_switching_kalman.py --missing on one {} ({}), float64 state, float32 observations, HIP events, warm; "
+             "us per call: median (min .. max)".format(torch.cuda.get_device_name(0), k._lib.aesmc_target_arch().decode())]
+    for B, K, M, D, Dy in shapes:
+        model = contract.example_model(M, D, Dy, seed=1)
+        ops = {name: torch.from_numpy(np.array(value)).to(dev) for name, value in model.items()}
+        gen = torch.Generator(device=dev).manual_seed(1)
+        regime = torch.randint(0, M, (B, K), generator=gen, device=dev, dtype=torch.int32)
+        mean = torch.randn(B, K, D, generator=gen, device=dev, dtype=torch.float64)
+        factor = torch.randn(B, K, D, D, generator=gen, device=dev, dtype=torch.float64)
+        full = factor @ factor.transpose(-1, -2) / D + 0.1 * torch.eye(D, device=dev, dtype=torch.float64)
+        rows, cols = torch.tril_indices(D, D, device=dev)
+        packed = (0.5 * (full + full.transpose(-1, -2)))[..., rows, cols].contiguous()
+        del factor, full
+        idx = torch.sort(torch.randint(0, K, (B, K), generator=gen, device=dev), dim=1).values      # as a resampler's
+        u = torch.rand(B, K, generator=gen, device=dev, dtype=torch.float64)
+        y = torch.randn(B, Dy, generator=gen, device=dev, dtype=torch.float32)
+        masks = (("everything observed", torch.ones((B, Dy), dtype=torch.bool, device=dev)),
+                 ("p = 0.6 per component", torch.rand(B, Dy, generator=gen, device=dev) < 0.6),
+                 ("nothing observed", torch.zeros((B, Dy), dtype=torch.bool, device=dev)))
+        plain = k.switching_kalman_step(ops, (regime, mean, packed), idx, u, y)
+        same = all(torch.equal(a, b) for a, b in zip(plain, k.switching_kalman_step(ops, (regime, mean, packed), idx, u, y,
+                                                                                    observed=masks[0][1])))
+        lines.append("B={} K={} M={} D={} Dy={} (sorted ancestors; flags {}; K39 with everything observed equals K31 bit for "
+                     "bit: {})".format(B, K, M, D, Dy, k.read_flags(dev), same))
+        del plain
+        lines.append("  K31                                   {:10.1f} ({:.1f} .. {:.1f}) us".format(
+            *timed(lambda: k.switching_kalman_step(ops, (regime, mean, packed), idx, u, y), 3, 10, 8)))
+        for name, mask in masks:
+            lines.append("  K39, {:<32s} {:10.1f} ({:.1f} .. {:.1f}) us".format(name, *timed(
+                lambda: k.switching_kalman_step(ops, (regime, mean, packed), idx, u, y, observed=mask), 3, 10, 8)))
+        del packed, regime, mean, idx, u
+        torch.cuda.empty_cache()
+    if parent_report is not None:
+        lines.append("K31 on the commit before K39, this tool's own report from the same session:")
+        with open(parent_report) as handle:
+            lines += ["  " + line.rstrip() for line in handle if line.startswith("B=") or line.startswith("  K31")]
+    return lines
+
+
 def main(argv):
-    out_path = os.path.join(ROOT, "profiles", "switching_kalman.txt")
+    missing = "--missing" in argv
+    argv = [arg for arg in argv if arg != "--missing"]
+    parent_report = None
+    if "--parent-report" in argv:
+        at = argv.index("--parent-report")
+        parent_report = argv[at + 1]
+        argv = argv[:at] + argv[at + 2:]
+    out_path = os.path.join(ROOT, "profiles", "switching_missing.txt" if missing else "switching_kalman.txt")
     if "--out" in argv:
         at = argv.index("--out")
         out_path = argv[at + 1]
         argv = argv[:at] + argv[at + 2:]
     shapes = [tuple(int(x) for x in arg.split(",")) for arg in argv] or [(1024, 4096, 4, 4, 4), (1024, 4096, 4, 8, 8)]
+    if missing:
+        report = "\n".join(missing_leg(shapes, parent_report)) + "\n"
+        print(report, end="")
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as handle:
+            handle.write(report)
+        return
     lines = ["tools/bench_switching_kalman.py on one {} ({}), float64 state, float32 observations, HIP events, warm; us per "
              "call: median (min .. max); bytes the launch moves; fraction of the {:.0f} GB/s HBM peak".format(
                  torch.cuda.get_device_name(0), k._lib.aesmc_target_arch().decode(), PEAK_HBM / 1e9)]
