@@ -2525,6 +2525,112 @@ class HipKernels:
                      (model, log_prior, regime, mean, cov, observation, log_weight, cdf, block), name="switching_lookahead")
         return log_weight, cdf
 
+    # ---- K43, K44 ------------------------------------------------------------------------------
+    def switching_lookahead_scores(self, model, log_prior, state, observation, num_particles=None, observed=None):
+        """`switching_lookahead` with the scores themselves in place of the cumulative row (aesmc_switching_lookahead_scores,
+        K43; with `observed` aesmc_switching_masked_lookahead_scores): returns (scores [B,K,M], log_weight [B,K]) float64, new
+        tensors — scores[b,k,j] = g_j as K32 defines it (-inf under a log-prior of -inf, NaN where a pivot is not positive
+        under a finite one), log_weight K32's bit for bit.  Arguments, validation and flags as `switching_lookahead`'s."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        device = observation.device
+        block, M, D, Dy = self._switching_block(model, device)
+        if observation.dim() != 2 or observation.size(1) != Dy:
+            raise ValueError("aesmc_amd: observation must be [batch_size, {}], got {}".format(Dy, tuple(observation.shape)))
+        B = observation.size(0)
+        if state is None:
+            if num_particles is None or int(num_particles) < 0:
+                raise ValueError("aesmc_amd: switching_lookahead_scores without a state needs num_particles")
+            K = int(num_particles)
+        else:
+            K = state[0].size(1) if torch.is_tensor(state[0]) and state[0].dim() == 2 else -1
+            if num_particles is not None and int(num_particles) != K:
+                raise ValueError("aesmc_amd: num_particles ({}) disagrees with the state ({})".format(num_particles, K))
+        if not self.switching_covers(observation, M, D, Dy, K):
+            raise ValueError("aesmc_amd: switching_lookahead_scores does not take these operands (see switching_covers)")
+        _require_hip(log_prior, "log_prior")
+        want = (M,) if state is None else (M, M)
+        if tuple(log_prior.shape) != want or log_prior.dtype != torch.float64 or log_prior.device != device:
+            raise ValueError("aesmc_amd: log_prior must be {} float64 on {}, got {} {} on {}".format(
+                want, device, tuple(log_prior.shape), log_prior.dtype, log_prior.device))
+        log_prior = log_prior.contiguous()
+        regime, mean, cov = (None, None, None) if state is None else self._switching_state(state, B, K, D, device)
+        observation = observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
+        scores = torch.empty((B, K, M), dtype=torch.float64, device=device)
+        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
+        if log_weight.numel() == 0:
+            return scores, log_weight
+        TD = D * (D + 1) // 2
+        per_particle = (4 + 8 * D + 8 * TD if state is not None else 0) + 8 + 8 * M
+        if observed is not None:
+            self._launch(device, self._lib.aesmc_switching_masked_lookahead_scores,
+                         (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
+                          _ptr(observed), _ptr(scores), _ptr(log_weight), _ptr(self.flags(device)), B, K,
+                          self._stream(observation)),
+                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
+                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                         (model, log_prior, regime, mean, cov, observation, observed, scores, log_weight, block),
+                         name="switching_masked_lookahead_scores")
+            return scores, log_weight
+        self._launch(device, self._lib.aesmc_switching_lookahead_scores,
+                     (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
+                      _ptr(scores), _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
+                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
+                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
+                     (model, log_prior, regime, mean, cov, observation, scores, log_weight, block),
+                     name="switching_lookahead_scores")
+        return scores, log_weight
+
+    def switching_optimal_resample_max_candidates(self):
+        """The most candidates K_in * M `switching_optimal_resample` keeps in LDS, as the library exports it."""
+        return int(self._lib.aesmc_switching_optimal_resample_max_candidates())
+
+    def switching_optimal_resample_covers(self, num_in, num_regimes, num_out, batch_size):
+        """Whether `switching_optimal_resample` takes a step of K_in particles, M regimes and K_out slots in B rows."""
+        return num_in >= 0 and num_out >= 0 and 1 <= num_regimes <= self.switching_limits()[2] and \
+            num_in * num_regimes <= self.switching_optimal_resample_max_candidates() and batch_size * num_out <= 0x7fffffff
+
+    def switching_optimal_resample(self, log_w, scores, u, num_slots):
+        """Optimal resampling of a row's K_in * M candidates down to `num_slots` (aesmc_switching_optimal_resample, K44).
+        log_w: float64 [B,K_in] or None (zeros); scores: float64 [B,K_in,M] (`switching_lookahead_scores`'); u: float64 [B] in
+        [0, 1).  Returns (parent int64 [B,K_out], regime int32 [B,K_out], log_weight float64 [B,K_out] — normalised, -inf in
+        dead slots —, lse float64 [B], count int32 [B]), new tensors.  A NaN candidate or a row without a finite maximum:
+        every parent K_in, NaN weights and lse, count 0, and the flag.  K_in * M beyond
+        `switching_optimal_resample_max_candidates` raises (ask `switching_optimal_resample_covers`)."""
+        _require_hip(scores, "scores")
+        _require_hip(u, "uniforms")
+        device = scores.device
+        if scores.dim() != 3 or scores.dtype != torch.float64:
+            raise ValueError("aesmc_amd: scores must be [batch_size, num_particles, num_regimes] float64, got {} {}".format(
+                tuple(scores.shape), scores.dtype))
+        B, K_in, M = scores.shape
+        K_out = int(num_slots)
+        if K_out < 0:
+            raise ValueError("aesmc_amd: num_slots must not be negative")
+        if log_w is not None:
+            _require_hip(log_w, "log_weight")
+            if tuple(log_w.shape) != (B, K_in) or log_w.dtype != torch.float64 or log_w.device != device:
+                raise ValueError("aesmc_amd: log_weight must be None or [{}, {}] float64 on {}".format(B, K_in, device))
+            log_w = log_w.contiguous()
+        if u.numel() != B or u.dtype != torch.float64 or u.device != device:
+            raise ValueError("aesmc_amd: uniforms must be {} float64 values on {}".format(B, device))
+        scores, u = scores.contiguous(), u.contiguous()
+        parent = torch.empty((B, K_out), dtype=torch.int64, device=device)
+        regime = torch.empty((B, K_out), dtype=torch.int32, device=device)
+        log_weight = torch.empty((B, K_out), dtype=torch.float64, device=device)
+        lse = torch.empty((B,), dtype=torch.float64, device=device)
+        count = torch.empty((B,), dtype=torch.int32, device=device)
+        if B == 0 or K_out == 0 or K_in == 0 or M == 0:
+            return parent, regime, log_weight, lse.fill_(float("nan")), count.zero_()
+        self._launch(device, self._lib.aesmc_switching_optimal_resample,
+                     (_ptr(log_w), _ptr(scores), _ptr(u), _ptr(parent), _ptr(regime), _ptr(log_weight), _ptr(lse), _ptr(count),
+                      _ptr(self.flags(device)), B, K_in, M, K_out, self._stream(scores)),
+                     lambda: B * (K_in * (8 * M + (8 if log_w is not None else 0)) + 20 * K_out + 20),
+                     (log_w, scores, u, parent, regime, log_weight, lse, count), name="switching_optimal_resample")
+        return parent, regime, log_weight, lse, count
+
     def switching_kalman_draw(self, model, state, index, uniforms, cdf, observation, observed=None):
         """`switching_kalman_step` with the regime drawn from a cumulative row per particle (aesmc_switching_kalman_draw,
         K33): cdf float64 [B,K,M], read at the ancestor's position (`switching_lookahead`'s).  Returns (regime, mean, cov,

@@ -145,6 +145,10 @@ SIGNATURES = {
     "aesmc_switching_masked_lookahead": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 9 + [_i64, _i64, _vp]),
     "aesmc_switching_masked_information_step": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 11 + [_i64, _i64, _vp]),
     "aesmc_switching_masked_smooth_combine": (_i32, [ctypes.POINTER(SwitchingModel)] + [_vp] * 12 + [_i64] * 3 + [_vp]),
+    "aesmc_switching_lookahead_scores": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 8 + [_i64, _i64, _vp]),
+    "aesmc_switching_masked_lookahead_scores": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 9 + [_i64, _i64, _vp]),
+    "aesmc_switching_optimal_resample_max_candidates": (_i64, []),
+    "aesmc_switching_optimal_resample": (_i32, [_vp] * 9 + [_i64] * 4 + [_vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

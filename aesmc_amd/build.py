@@ -20,7 +20,7 @@ SOURCES = ["abi.hip", "logweight_lse.hip", "ancestor_index.hip", "ancestor_index
            "linear_gaussian_wide_generic_draw.hip", "linear_gaussian_wide_generic_emit.hip", "particle_mlp.hip",
            "linear_gaussian_initial.hip", "adapted_step.hip", "adapted_step_backward.hip",
            "switching_kalman.hip", "switching_lookahead.hip", "switching_information.hip", "switching_backward.hip",
-           "switching_smooth.hip", "switching_conditional.hip"]
+           "switching_smooth.hip", "switching_conditional.hip", "switching_optimal_resample.hip"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "ancestor_index.hpp"), os.path.join(CSRC, "pairwise_gaussian.hpp"),
            os.path.join(CSRC, "linear_gaussian.hpp"), os.path.join(CSRC, "adapted_step.hpp"),
            os.path.join(CSRC, "philox_normal.hpp"), os.path.join(CSRC, "linear_gaussian_fused.hpp"),

@@ -38,6 +38,18 @@
 //   <8,2>       256     22        0             1       P- in LDS
 //   <8,4>       256     26        0             1       P- in LDS
 //   <8,8>       256     82        0             1       P- in LDS
+// and of the scores instantiations (K43, aesmc_switching_lookahead_scores: g_j itself in place of the cumulative row — the body
+// up to log_w, then nothing), unmasked | masked:
+//   <2,2>        66      0        0             7       |     66      0        0             7
+//   <2,4>        88      0        0             5       |     89      0        0             5
+//   <2,8>       164      0        0             3       |    161      0        0             3
+//   <4,2>       102      0        0             4       |    101      0        0             4
+//   <4,4>       116      0        0             4       |    122      0        0             4
+//   <4,8>       204      0        0             2       |    215      0        0             2
+//   <8,2>       256     20        0             1       |    256     20        0             1       P- in LDS
+//   <8,4>       256     24        0             1       |    256     24        0             1       P- in LDS
+//   <8,8>       256     32        0             1       |    256     80        0             1       P- in LDS
+// (the K32 and K40 lines above are unchanged by the further template parameter).
 // No instantiation spills: without V = Lam^-1 U and the downdate the live set of <8,8> (U 128, S 72 registers and the
 // vectors) fits, and the input covariance is read again per regime instead of being held across the loop.
 //
@@ -65,7 +77,8 @@ struct LookaheadArgs {
 // LDS: [M * M] (or [M]) log-priors, the model (M blocks of sk_per_regime values), for DP == 8 [TP][256] predicted
 // covariances, then [M][256] scores
 // Masked (K40): K39's three selections (switching_kalman.hip) for every regime; the constant counts the observed components
-template <int DP, int DYP, bool Masked>
+// Scores (K43): the row that a.cdf points at receives g_j itself, as computed, and no cumulative row
+template <int DP, int DYP, bool Masked, bool Scores>
 __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const LookaheadArgs a) {
   extern __shared__ __attribute__((aligned(16))) double la_smem[];
   constexpr int kPer = sk_per_regime(DP, DYP);
@@ -241,7 +254,9 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
     const double ell = (-0.5 * quad - log_det) - (double)n_obs * kHalfLog2Pi;
     const double lpj = prior[j];
     // a regime of prior probability 0 has the score -inf whatever its pivots are; elsewhere a pivot that is not positive is NaN
-    scores[j * kSkBlock] = lpj == -inf ? -inf : positive ? lpj + ell : nan;
+    const double g = lpj == -inf ? -inf : positive ? lpj + ell : nan;
+    scores[j * kSkBlock] = g;
+    if constexpr (Scores) crow[j] = g;
   }
 
   // ---- log_w = logsumexp_j g_j; cdf_j = sum_{i <= j} exp(g_i - log_w), exactly 1 from the last positive term onwards -------------
@@ -254,13 +269,15 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
   }
   if (invalid || !(top > -inf)) {      // (no regime of positive prior: the host's validation excludes it)
     a.log_weight[n] = nan;
-    for (int j = 0; j < M; ++j) crow[j] = nan;
+    if constexpr (!Scores)
+      for (int j = 0; j < M; ++j) crow[j] = nan;
     return;
   }
   double sum = 0.0;
   for (int j = 0; j < M; ++j) sum += ::exp(scores[j * kSkBlock] - top);
   const double log_w = top + ::log(sum);
   a.log_weight[n] = log_w;
+  if constexpr (Scores) return;
   int last = 0;
   for (int j = 0; j < M; ++j) {
     const double p = ::exp(scores[j * kSkBlock] - log_w);
@@ -274,33 +291,33 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
   }
 }
 
-template <int DP, int DYP, bool Masked>
+template <int DP, int DYP, bool Masked, bool Scores>
 static bool la_launch(dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
   // more than the default 64 KB: the limit is raised on every launch, as K31's launcher does and for its reasons
   if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_lookahead_kernel<DP, DYP, Masked>),
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_lookahead_kernel<DP, DYP, Masked, Scores>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return false;
-  hipLaunchKernelGGL((switching_lookahead_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
+  hipLaunchKernelGGL((switching_lookahead_kernel<DP, DYP, Masked, Scores>), grid, dim3(kSkBlock), lds, s, a);
   return true;
 }
 
-template <int DP, bool Masked>
+template <int DP, bool Masked, bool Scores>
 static bool la_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
-  if (dyp == 2) return la_launch<DP, 2, Masked>(grid, lds, s, a);
-  if (dyp == 4) return la_launch<DP, 4, Masked>(grid, lds, s, a);
-  return la_launch<DP, 8, Masked>(grid, lds, s, a);
+  if (dyp == 2) return la_launch<DP, 2, Masked, Scores>(grid, lds, s, a);
+  if (dyp == 4) return la_launch<DP, 4, Masked, Scores>(grid, lds, s, a);
+  return la_launch<DP, 8, Masked, Scores>(grid, lds, s, a);
 }
 
-template <bool Masked>
+template <bool Masked, bool Scores>
 static bool la_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
-  if (dp == 2) return la_launch_dy<2, Masked>(dyp, grid, lds, s, a);
-  if (dp == 4) return la_launch_dy<4, Masked>(dyp, grid, lds, s, a);
-  return la_launch_dy<8, Masked>(dyp, grid, lds, s, a);
+  if (dp == 2) return la_launch_dy<2, Masked, Scores>(dyp, grid, lds, s, a);
+  if (dp == 4) return la_launch_dy<4, Masked, Scores>(dyp, grid, lds, s, a);
+  return la_launch_dy<8, Masked, Scores>(dyp, grid, lds, s, a);
 }
 
-// K32, and K40 (`masked`: observed [B,Dy] given): one set of checks, one launch
-static int la_step(bool masked, const uint8_t *observed, int y_dtype, const aesmc_switching_model *model,
+// K32, and K40 (`masked`: observed [B,Dy] given), and K43 (`scores`: `cdf` receives the scores): one set of checks, one launch
+static int la_step(bool scores, bool masked, const uint8_t *observed, int y_dtype, const aesmc_switching_model *model,
                    const double *log_prior, const int32_t *regime_in, const double *mean_in, const double *cov_in,
                    const void *y, double *log_weight, double *cdf, int32_t *flags, int64_t B, int64_t K, void *stream) {
   if (masked && (observed == nullptr || (const void *)observed == log_weight || (const void *)observed == cdf))
@@ -339,7 +356,10 @@ static int la_step(bool masked, const uint8_t *observed, int y_dtype, const aesm
                       (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0) + (size_t)a.M * kSkBlock) * sizeof(double);
   const dim3 grid((unsigned)((a.N + kSkBlock - 1) / kSkBlock));
   hipStream_t s = (hipStream_t)stream;
-  const bool launched = masked ? la_launch_d<true>(dp, dyp, grid, lds, s, a) : la_launch_d<false>(dp, dyp, grid, lds, s, a);
+  const bool launched = scores ? (masked ? la_launch_d<true, true>(dp, dyp, grid, lds, s, a)
+                                        : la_launch_d<false, true>(dp, dyp, grid, lds, s, a))
+                               : (masked ? la_launch_d<true, false>(dp, dyp, grid, lds, s, a)
+                                         : la_launch_d<false, false>(dp, dyp, grid, lds, s, a));
   return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
 }
 
@@ -348,7 +368,7 @@ static int la_step(bool masked, const uint8_t *observed, int y_dtype, const aesm
 extern "C" int aesmc_switching_lookahead(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
                                          const int32_t *regime_in, const double *mean_in, const double *cov_in, const void *y,
                                          double *log_weight, double *cdf, int32_t *flags, int64_t B, int64_t K, void *stream) {
-  return aesmc::la_step(false, nullptr, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, cdf, flags, B, K,
+  return aesmc::la_step(false, false, nullptr, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, cdf, flags, B, K,
                         stream);
 }
 
@@ -356,6 +376,23 @@ extern "C" int aesmc_switching_masked_lookahead(int y_dtype, const aesmc_switchi
                                                 const int32_t *regime_in, const double *mean_in, const double *cov_in,
                                                 const void *y, const uint8_t *observed, double *log_weight, double *cdf,
                                                 int32_t *flags, int64_t B, int64_t K, void *stream) {
-  return aesmc::la_step(true, observed, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, cdf, flags, B, K,
+  return aesmc::la_step(false, true, observed, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, cdf, flags, B, K,
                         stream);
+}
+
+extern "C" int aesmc_switching_lookahead_scores(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
+                                                const int32_t *regime_in, const double *mean_in, const double *cov_in,
+                                                const void *y, double *scores, double *log_weight, int32_t *flags, int64_t B,
+                                                int64_t K, void *stream) {
+  return aesmc::la_step(true, false, nullptr, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, scores, flags,
+                        B, K, stream);
+}
+
+extern "C" int aesmc_switching_masked_lookahead_scores(int y_dtype, const aesmc_switching_model *model,
+                                                       const double *log_prior, const int32_t *regime_in,
+                                                       const double *mean_in, const double *cov_in, const void *y,
+                                                       const uint8_t *observed, double *scores, double *log_weight,
+                                                       int32_t *flags, int64_t B, int64_t K, void *stream) {
+  return aesmc::la_step(true, true, observed, y_dtype, model, log_prior, regime_in, mean_in, cov_in, y, log_weight, scores, flags,
+                        B, K, stream);
 }

@@ -25,6 +25,13 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                from the ancestor's posterior row).  The weights after the draw are all equal; at T = 1 the
                                evidence is exact for any K, and a regime change is met in the step where it happens (Chen &
                                Liu 2000; Doucet, Gordon & Krishnamurthy 2001; Pitt & Shephard 1999)
+    discrete_switching_filter  the discrete particle filter (Fearnhead & Clifford 2003): no regime is drawn.  Every particle
+                               proposes all M successor regimes with their exact weights (K43,
+                               `aesmc_switching_lookahead_scores`: K32's scores themselves) and K of the K M candidates survive
+                               under optimal resampling (K44, `aesmc_switching_optimal_resample`: heavier than a threshold c as
+                               they are, the rest thinned by one stratified draw to the weight c), then K31 forced to the
+                               survivors' regimes.  No regime history appears twice, the evidence stays unbiased and is
+                               exact while M^T <= K
     kalman_log_likelihood      one regime: the exact log p(y)
     unpack_covariance          packed lower triangles -> symmetric matrices
     switching_backward_simulate   Rao-Blackwellised backward simulation (Fong, Godsill, Doucet & West 2002; Whiteley, Andrieu
@@ -445,6 +452,90 @@ def adapted_switching_filter(observations, model, num_particles, resampling=None
                 out["latents"] = inference.get_resampled_latents(regimes, ancestral)
             inference._raise_for_flags(provider.read_flags(device))
             # (step 0's first-stage weights meet no resampling launch: a NaN among them is reported here, after the one read)
+            if bool(torch.isnan(log_z).any()):
+                raise FloatingPointError("log_weight contains nan element(s)")
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
+
+
+def discrete_switching_filter(observations, model, num_particles, uniforms=None, return_moments=False,
+                              return_latents=False, observed=None):
+    """Runs the discrete particle filter (Fearnhead & Clifford 2003) of a `SwitchingLinearGaussian`: no regime is drawn.
+    Every particle proposes ALL M successor regimes with their exact weights (K43, `aesmc_switching_lookahead_scores`: K32's
+    scores, which that kernel computes and discards), and K of the K M candidates survive under optimal resampling (K44,
+    `aesmc_switching_optimal_resample`): every candidate heavier than a threshold c as it is, the rest thinned by one
+    stratified draw to the weight c each.  K31, with the regime forced and `idx = parent`, then gives the survivors their
+    Kalman moments.  With z integrated out two particles of one regime history are one particle; here no history appears
+    twice, the resampling is unbiased — so is the evidence — and while M^(t+1) <= K nothing is discarded: the filter is exact.
+
+    observations, model, num_particles, return_moments, return_latents, observed: as `switching_filter`'s (with `observed` the
+        masked kernels: K40's body for the scores and K39 for the step).
+    uniforms: None — torch.rand(batch_size, float64) per step on the device (seed with torch.manual_seed), ONE uniform per
+        batch row and step; or a length-T sequence of such tensors (replay).  None inside `distributed.shard_scope` raises
+        NotImplementedError, as `regime_uniforms` does there.
+
+    Returns a dict in `switching_filter`'s format — what `switching_backward_simulate` and `switching_forecast` take
+    unchanged (`switching_state_smooth` takes the trajectories drawn from it): log_marginal_likelihood [batch_size] float64 (the sum of K44's evidence increments;
+    unbiased, and exact while M^T <= K); regimes, means, covariances (T stored systems); log_weights (T float64
+    [batch_size, K], NORMALISED: their log-sum-exp is 0; -inf in a dead slot — with fewer than K live candidates the
+    remaining slots carry a copy of slot 0's state and weight zero); ancestral_indices (T-1 int64 [batch_size, K]: K44's
+    parents of steps 1 .. T-1); log_weight (the last of log_weights); num_live (T int32 [batch_size]: the slots that carry
+    weight).  With return_moments and return_latents, `switching_filter`'s additions.
+
+    ValueError for an invalid model, T == 0, K < 1 and uniforms of the wrong length or shape; NotImplementedError naming the
+    covered class for anything past the limits, and for K M above the candidates K44 keeps in LDS (16384).  A NaN score (an
+    innovation covariance that is not positive definite under a regime of positive prior probability) raises
+    FloatingPointError, a step without a candidate of positive weight RuntimeError — the flags are read once, at the end; an
+    exception on the way discards whatever was flagged.  No host synchronisation inside the step loop.  Runs under
+    torch.no_grad(): NOT differentiable."""
+    name = "discrete_switching_filter"
+    if uniforms is not None and len(uniforms) != len(observations):
+        raise ValueError("{}: uniforms must hold one tensor per timestep ({}), got {}".format(name, len(observations),
+                                                                                              len(uniforms)))
+    num_timesteps, num_particles, _ = _check_arguments(name, observations, num_particles, uniforms, None)
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops = model.operands()
+            M = model.num_regimes
+            batch_size, device = _check_observations(name, provider, observations, model, num_particles)
+            if not provider.switching_optimal_resample_covers(num_particles, M, num_particles, batch_size):
+                _refuse("{} particles of {} regimes ({} candidates per batch row; optimal resampling keeps at most {} in "
+                        "LDS)".format(num_particles, M, num_particles * M, provider.switching_optimal_resample_max_candidates()))
+            mask = _observed_steps(name, observed, observations)
+            draw = _regime_draws(name, uniforms, (batch_size,), device)
+            log_pi0, log_Pi = torch.log(ops["pi0"]), torch.log(ops["Pi"])      # (-inf where a probability is 0) once
+            edges = (torch.arange(M, dtype=torch.float64, device=device) + 1.0) / M
+            forced = dict(ops, cdf0=edges, cdf=edges.expand(M, M).contiguous())      # `_conditional_filter`'s forced draw
+            log_z = torch.zeros(batch_size, dtype=torch.float64, device=device)
+            regimes, means, covariances, log_weights, ancestral, num_live = [], [], [], [], [], []
+            state, log_w = None, None
+            for time in range(num_timesteps):
+                u = draw(time)      # (a replayed tensor of the wrong shape is refused before the step's launches)
+                scores, _ = provider.switching_lookahead_scores(ops, log_pi0 if time == 0 else log_Pi, state,
+                                                                observations[time], num_particles=1 if time == 0 else None,
+                                                                **mask(time))
+                parent, chosen, log_w, lse, count = provider.switching_optimal_resample(log_w, scores, u, num_particles)
+                log_z = log_z + lse
+                if time > 0:
+                    ancestral.append(parent)
+                regime, mean, cov, _ = provider.switching_kalman_step(
+                    forced, state, parent if time > 0 else None, (chosen.to(torch.float64) + 0.5) / M, observations[time],
+                    **mask(time))
+                state = (regime, mean, cov)
+                regimes.append(regime), means.append(mean), covariances.append(cov), log_weights.append(log_w)
+                num_live.append(count)
+            out = {"log_marginal_likelihood": log_z, "regimes": regimes, "means": means, "covariances": covariances,
+                   "log_weights": log_weights, "ancestral_indices": ancestral, "log_weight": log_weights[-1],
+                   "num_live": num_live}
+            if return_moments:
+                out["filtered_mean"], out["filtered_covariance"], out["regime_probabilities"] = _moments(
+                    regimes, means, covariances, log_weights, M)
+            if return_latents:
+                out["latents"] = inference.get_resampled_latents(regimes, ancestral)
+            inference._raise_for_flags(provider.read_flags(device))
             if bool(torch.isnan(log_z).any()):
                 raise FloatingPointError("log_weight contains nan element(s)")
     except BaseException:

@@ -3,12 +3,15 @@
 covariance of the continuous state given its regime history (kernel K31).
 
     python examples/slds_filter.py [--regimes 2] [--dim 2] [--particles 256] [--batch 8] [--timesteps 200] [--short 6]
-                                   [--lookahead] [--smooth] [--missing FRACTION] [--forecast H]
+                                   [--lookahead | --discrete] [--smooth] [--missing FRACTION] [--forecast H]
 
 Simulates a series whose regimes differ in their dynamics, filters it, and prints how often the most probable filtered
 regime is the true one and the error of the filtered mean; then, for a short series, log Z-hat beside the exact log p(y)
 from the enumeration of all M^T regime sequences.  With --lookahead the filter is `adapted_switching_filter`: every step
 resamples on the exact p(y_t | history) and draws the regime from its exact posterior (kernels K32 and K33).  With
+--discrete it is `discrete_switching_filter` (Fearnhead & Clifford 2003; kernels K43 and K44): no regime is drawn, every
+particle proposes all M successors and K of the K M candidates survive under optimal resampling — no regime history twice,
+and log Z-hat of the short series is exact once M^T <= K.  With
 --smooth the stored systems are smoothed by Rao-Blackwellised backward simulation (`switching_backward_simulate`, kernels
 K34 and K35) and the accuracy of the most probable SMOOTHED regime, which has seen the whole series, is printed beside the
 filtered one; then the continuous state is smoothed along the drawn trajectories (`switching_state_smooth`, kernel K36) and
@@ -52,19 +55,24 @@ def main():
     ap.add_argument("--short", type=int, default=6)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lookahead", action="store_true", help="the fully adapted filter: regimes from their exact posterior")
+    ap.add_argument("--discrete", action="store_true",
+                    help="the discrete particle filter: all successors proposed, optimal resampling, no history twice")
     ap.add_argument("--smooth", action="store_true", help="also smooth: regime accuracy given the whole series")
     ap.add_argument("--trajectories", type=int, default=None, help="backward trajectories per series (default: --particles)")
     ap.add_argument("--missing", type=float, default=0.0, metavar="FRACTION",
                     help="also filter with every component dropped with this probability")
     ap.add_argument("--forecast", type=int, default=0, metavar="H", help="also hold out the last H steps and forecast them")
     args = ap.parse_args()
+    if args.lookahead and args.discrete:
+        ap.error("--lookahead and --discrete name two filters: give one")
 
     device = torch.device("cuda", 0)
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     model = make_model(args.regimes, args.dim, args.seed).to(device)
     observations, regimes, states = model.simulate(args.timesteps, args.batch, seed=args.seed + 1, return_latents=True)
-    run = rao_blackwell.adapted_switching_filter if args.lookahead else rao_blackwell.switching_filter
+    run = rao_blackwell.adapted_switching_filter if args.lookahead else \
+        rao_blackwell.discrete_switching_filter if args.discrete else rao_blackwell.switching_filter
     out = run(observations, model, args.particles, return_moments=True)
     guess = out["regime_probabilities"].argmax(dim=-1)
     accuracy = (guess == torch.stack(regimes)).double().mean().item()

@@ -90,7 +90,10 @@ extern "C" {
  *                aesmc_switching_kalman_masked_step, aesmc_switching_masked_lookahead,
  *                aesmc_switching_masked_information_step, aesmc_switching_masked_smooth_combine (K39, K40, K41, K42: K31 /
  *                K33 / K38, K32, K34 and K36 with a per-row mask of the observation's components — missing observations,
- *                and forecasts as steps with nothing observed).
+ *                and forecasts as steps with nothing observed);
+ *                aesmc_switching_lookahead_scores, aesmc_switching_masked_lookahead_scores,
+ *                aesmc_switching_optimal_resample with aesmc_switching_optimal_resample_max_candidates (K43, K44: the
+ *                look-ahead's scores and optimal resampling over all successor regimes — the discrete particle filter).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -894,6 +897,54 @@ int aesmc_switching_masked_smooth_combine(const aesmc_switching_model *model, co
                                           const double *omega_next, const double *cov_next, const uint8_t *observed_next,
                                           double *mean_out, double *cov_out, double *cross_out, int32_t *flags, int64_t B,
                                           int64_t N, int64_t D, void *stream);
+
+/* K43 — K32's scores themselves, for the discrete particle filter of the same model (Fearnhead & Clifford 2003): K32's kernel
+ * body as a further instantiation, which writes
+ *   scores[b,k,j]   = g_j exactly as K32 defines it: -inf where the log-prior is -inf, NaN where the log-prior is finite and a
+ *                     pivot is not positive (and NaN for every j where the stored regime is outside [0, M))
+ *   log_weight[b,k] = K32's, bit for bit (the same chains in the same order)
+ * and no cumulative row.  scores float64 [B,K,M] takes the place of K32's cdf in every check; the masked form is K40's body
+ * in the same way.  Conventions, flags and statuses are K32's (K40's). */
+int aesmc_switching_lookahead_scores(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
+                                     const int32_t *regime_in, const double *mean_in, const double *cov_in, const void *y,
+                                     double *scores, double *log_weight, int32_t *flags, int64_t B, int64_t K, void *stream);
+int aesmc_switching_masked_lookahead_scores(int y_dtype, const aesmc_switching_model *model, const double *log_prior,
+                                            const int32_t *regime_in, const double *mean_in, const double *cov_in,
+                                            const void *y, const uint8_t *observed, double *scores, double *log_weight,
+                                            int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K44 — optimal resampling (Fearnhead & Clifford 2003) of the K_in M candidates of a batch row down to K_out slots, in float64,
+ * one launch.  Candidate i = k M + j (particle k, successor regime j):
+ *   log_w   float64 [B,K_in] or NULL (zeros)     scores  float64 [B,K_in,M] (K43's)     u  float64 [B] in [0, 1)
+ *   a_i     = log_w[b,k] + scores[b,k,j]  (one rounded addition);  top = max_i a_i
+ *   e_i     = exp(a_i - top), and 0 where a_i - top < log(2^-1022) (a result below the normal range is flushed: whether a
+ *             candidate lives does not hang on how an exponential rounds a subnormal);  live: e_i > 0;  E = sum_i e_i
+ *   lse[b]  = top + log E  (the step's evidence increment; the outgoing weights are normalised: no - log K_out)
+ * With at most K_out live candidates the survivors are the live candidates in ascending i, log_weight = a_i - lse; the
+ * remaining slots are dead: log_weight -inf, parent and regime copies of slot 0's (a valid state of weight zero); count[b] is
+ * the number of live candidates.  Otherwise, with w_i = e_i / E:
+ *   c       solves sum_i min(1, w_i / c) = K_out: with the candidates by descending weight, L is the smallest number for which
+ *           e_(L+1) (K_out - L) < S_L, S_L the sum of e over all but the L heaviest; L is at most K_out - 1 (where the test
+ *           fails even there — the mass outside the K_out - 1 heaviest does not register next to the next one — L is
+ *           K_out - 1; equal weights are then kept in ascending i); c E = S_L / (K_out - L)
+ *   kept    the L heaviest, in ascending i, in slots 0 .. L-1 with log_weight = a_i - lse
+ *   thinned with R = K_out - L, Q_i the inclusive running sum of e over the candidates not kept in ascending i and
+ *           t_i = R (Q_i / Q_last): slot L + n, n = 0 .. R-1, takes the first candidate not kept with t_i > n + u (n + u
+ *           rounded once; the last live one where none is), log_weight = (top + log(Q_last / R)) - lse.  A candidate of
+ *           weight 0 is never taken; no candidate is taken twice
+ *   parent int64 [B,K_out] (k; `infer`'s ancestor convention), regime int32 [B,K_out] (j), log_weight float64 [B,K_out],
+ *   lse float64 [B], count int32 [B] (K_out here)
+ * The sums may be added in any order: two evaluations differ only where a w_i lies within rounding of c or an n + u within
+ * rounding of a t_i.  A NaN candidate raises AESMC_FLAG_NAN_LOG_WEIGHT, a maximum that is not finite
+ * AESMC_FLAG_DEGENERATE_ROW: every parent of the row is K_in (K2's out-of-range marker), every regime 0, log_weight and lse
+ * NaN, count 0.  The row's candidates live in LDS: K_in M above aesmc_switching_optimal_resample_max_candidates() (16384), M
+ * above the limit of K31 or B K_out beyond 32-bit element arithmetic return AESMC_ERR_UNSUPPORTED.  NULL (but log_w, flags) or
+ * misaligned pointers, negative sizes, M below 1 and an output that is an input, another output or flags return
+ * AESMC_ERR_INVALID_ARGUMENT; B == 0, K_in == 0 or K_out == 0 is a no-op.  No workspace.  Every check runs before any launch. */
+int64_t aesmc_switching_optimal_resample_max_candidates(void);
+int aesmc_switching_optimal_resample(const double *log_w, const double *scores, const double *u, int64_t *out_parent,
+                                     int32_t *out_regime, double *out_log_weight, double *out_lse, int32_t *out_count,
+                                     int32_t *flags, int64_t B, int64_t K_in, int64_t M, int64_t K_out, void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *

@@ -11,7 +11,12 @@ they make.
 the masked step K39 (aesmc_switching_kalman_masked_step) beside K31 on the same inputs in the same run: under a mask that
 observes everything (K39 then computes what K31 does), one drawn with p = 0.6 per component, and one that observes nothing
 (the prediction).  --parent-report: a report this tool wrote on the commit before K39 in the same session, whose K31 lines
-are quoted beside.  A measurement, no threshold; the report goes to profiles/switching_missing.txt."""
+are quoted beside.  A measurement, no threshold; the report goes to profiles/switching_missing.txt.
+    python tools/bench_switching_kalman.py --discrete [--out FILE] [B,K,M,D,Dy ...]
+a step of the discrete particle filter (K43 aesmc_switching_lookahead_scores + K44 aesmc_switching_optimal_resample + K31
+forced through the parents) beside a step of the fully adapted filter (K32 + K2 + K33) on the same stored system in the same
+run, each launch alone and the three together (default: 1024,1024,4,4,4 and 1024,1024,4,8,8).  A measurement, no
+threshold; the report goes to profiles/discrete_filter.txt."""
 import os
 import sys
 
@@ -122,7 +127,85 @@ def missing_leg(shapes, parent_report):
     return lines
 
 
+def discrete_leg(shapes):
+    """The report of --discrete: the launches of a discrete step and of an adapted step, alone and together, per shape."""
+    from aesmc_amd import _ops
+    lines = ["tools/bench_switching_kalman.py --discrete on one {} ({}), float64 state, float32 observations, HIP events, warm; "
+             "us per call: median (min .. max)".format(torch.cuda.get_device_name(0), k._lib.aesmc_target_arch().decode())]
+    for B, K, M, D, Dy in shapes:
+        model = contract.example_model(M, D, Dy, seed=1)
+        ops = {name: torch.from_numpy(np.array(value)).to(dev) for name, value in model.items()}
+        edges = (torch.arange(M, dtype=torch.float64, device=dev) + 1.0) / M
+        forced = dict(ops, cdf0=edges, cdf=edges.expand(M, M).contiguous())
+        log_Pi = torch.log(ops["Pi"])
+        gen = torch.Generator(device=dev).manual_seed(1)
+        regime = torch.randint(0, M, (B, K), generator=gen, device=dev, dtype=torch.int32)
+        mean = torch.randn(B, K, D, generator=gen, device=dev, dtype=torch.float64)
+        factor = torch.randn(B, K, D, D, generator=gen, device=dev, dtype=torch.float64)
+        full = factor @ factor.transpose(-1, -2) / D + 0.1 * torch.eye(D, device=dev, dtype=torch.float64)
+        rows, cols = torch.tril_indices(D, D, device=dev)
+        packed = (0.5 * (full + full.transpose(-1, -2)))[..., rows, cols].contiguous()
+        del factor, full
+        state = (regime, mean, packed)
+        stored = torch.log_softmax(torch.randn(B, K, generator=gen, device=dev, dtype=torch.float64), dim=1)
+        row_u = torch.rand(B, generator=gen, device=dev, dtype=torch.float64)
+        u = torch.rand(B, K, generator=gen, device=dev, dtype=torch.float64)
+        y = torch.randn(B, Dy, generator=gen, device=dev, dtype=torch.float32)
+        scores, _ = k.switching_lookahead_scores(ops, log_Pi, state, y)
+        parent, chosen, _, _, count = k.switching_optimal_resample(stored, scores, row_u, K)
+        forced_u = (chosen.to(torch.float64) + 0.5) / M
+        log_w, cdf = k.switching_lookahead(ops, log_Pi, state, y)
+        index = _kernels.as_index(_ops.resample_step(log_w, row_u, None, want_lse=True)[0])
+        kept = int((torch.sort(parent, dim=1).values.diff(dim=1) != 0).sum().item()) + B
+        lines.append("B={} K={} M={} D={} Dy={} ({} candidates per row; flags {}; live slots {}; distinct parents per row: "
+                     "discrete {:.0f}, adapted {:.0f})".format(
+                         B, K, M, D, Dy, K * M, k.read_flags(dev), int(count.min().item()), kept / B,
+                         (int((index.diff(dim=1) != 0).sum().item()) + B) / B))
+
+        def discrete_step():
+            s, _ = k.switching_lookahead_scores(ops, log_Pi, state, y)
+            p, c, _, _, _ = k.switching_optimal_resample(stored, s, row_u, K)
+            return k.switching_kalman_step(forced, state, p, (c.to(torch.float64) + 0.5) / M, y)
+
+        def adapted_step():
+            w, rows_ = k.switching_lookahead(ops, log_Pi, state, y)
+            i = _kernels.as_index(_ops.resample_step(w, row_u, None, want_lse=True)[0])
+            return k.switching_kalman_draw(ops, state, i, u, rows_, y)
+
+        legs = (("K43 scores", lambda: k.switching_lookahead_scores(ops, log_Pi, state, y)),
+                ("K44 optimal resampling", lambda: k.switching_optimal_resample(stored, scores, row_u, K)),
+                ("K31 forced, idx = parent", lambda: k.switching_kalman_step(forced, state, parent, forced_u, y)),
+                ("discrete step (K43 + K44 + K31)", discrete_step),
+                ("K32 look-ahead", lambda: k.switching_lookahead(ops, log_Pi, state, y)),
+                ("K2 resampling", lambda: _ops.resample_step(log_w, row_u, None, want_lse=True)),
+                ("K33 draw", lambda: k.switching_kalman_draw(ops, state, index, u, cdf, y)),
+                ("adapted step (K32 + K2 + K33)", adapted_step))
+        medians = {}
+        for name, fn in legs:
+            result = timed(fn, 3, 10, 8)
+            medians[name] = result[0]
+            lines.append("  {:<36s} {:10.1f} ({:.1f} .. {:.1f}) us".format(name, *result))
+        lines.append("  discrete / adapted = {:.2f}x".format(medians[legs[3][0]] / medians[legs[7][0]]))
+        del packed, regime, mean, state, scores, cdf
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv):
+    if "--discrete" in argv:
+        argv = [arg for arg in argv if arg != "--discrete"]
+        out_path = os.path.join(ROOT, "profiles", "discrete_filter.txt")
+        if "--out" in argv:
+            at = argv.index("--out")
+            out_path = argv[at + 1]
+            argv = argv[:at] + argv[at + 2:]
+        shapes = [tuple(int(x) for x in arg.split(",")) for arg in argv] or [(1024, 1024, 4, 4, 4), (1024, 1024, 4, 8, 8)]
+        report = "\n".join(discrete_leg(shapes)) + "\n"
+        print(report, end="")
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as handle:
+            handle.write(report)
+        return
     missing = "--missing" in argv
     argv = [arg for arg in argv if arg != "--missing"]
     parent_report = None
