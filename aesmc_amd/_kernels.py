@@ -2404,15 +2404,18 @@ class HipKernels:
                 if torch.is_tensor(observed) else type(observed).__name__))
         return observed.contiguous()
 
-    def switching_kalman_step(self, model, state, index, uniforms, observation, observed=None):
-        """One step of the Rao-Blackwellised filter of a switching linear-Gaussian model (aesmc_switching_kalman_step, K31).
-        model: a dict of dense float64 tensors cdf0 [M], cdf [M,M], m0 [D], s0 [D], A [M,D,D], b [M,D], q [M,D], C [M,Dy,D],
-        d [M,Dy], r [M,Dy]; state: None (step 0) or (regime int32 [B,K], mean float64 [B,K,D], cov float64 [B,K,D(D+1)/2])
-        — the STORED particles of the step before; index: int64 [B,K] or None (the identity); uniforms float64 [B,K];
-        observation float32 / float64 [B,Dy].  Returns (regime, mean, cov, log_weight [B,K] float64), new tensors.  An index
-        outside [0, K) or a stored regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE.
-        observed: None, or torch.bool [B,Dy] — the masked entry (aesmc_switching_kalman_masked_step, K39): row b's step is the
-        step of the model with the components deleted whose entry is False; y there is not used and may be NaN."""
+    @staticmethod
+    def _switching_model_bytes(M, D, Dy, rows=True):
+        """The algorithmic traffic of a switching model's operands: per regime A, b, q, C, d, r and, with `rows`, its row of the
+        chain (a launch that draws from per-particle rows, or that draws nothing, does not read them)."""
+        return 8 * M * ((M if rows else 0) + D * D + 2 * D + Dy * D + 2 * Dy)
+
+    def _switching_kalman(self, name, entry, masked_name, model, state, index, uniforms, observation, observed, cdf=None,
+                          pinned_regime=None, draw=False, pinned=False):
+        """`switching_kalman_step`, `switching_kalman_draw` (`draw`: with `cdf`) and `switching_kalman_conditional_step`
+        (`pinned`: with `pinned_regime`), called as `name`, which messages and the timer's entries carry.  Without `observed`
+        the launch is the caller's own C `entry` (and so its unmasked kernel); with it, the masked entry, which takes both
+        operands as nullable, recorded as `masked_name`."""
         _require_hip(observation, "observation")
         tag = _tag(observation, "observation")
         _require_hip(uniforms, "regime uniforms")
@@ -2425,7 +2428,17 @@ class HipKernels:
         if tuple(observation.shape) != (B, Dy):
             raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
         if not self.switching_covers(observation, M, D, Dy, K):
-            raise ValueError("aesmc_amd: switching_kalman_step does not take these operands (see switching_covers)")
+            raise ValueError("aesmc_amd: {} does not take these operands (see switching_covers)".format(name))
+        if draw:
+            _require_hip(cdf, "cdf")
+            if tuple(cdf.shape) != (B, K, M) or cdf.dtype != torch.float64 or cdf.device != device:
+                raise ValueError("aesmc_amd: cdf must be {} float64 on {}".format((B, K, M), device))
+            cdf = cdf.contiguous()
+        if pinned:
+            _require_hip(pinned_regime, "pinned_regime")
+            if tuple(pinned_regime.shape) != (B,) or pinned_regime.dtype != torch.int32 or pinned_regime.device != device:
+                raise ValueError("aesmc_amd: pinned_regime must be [{}] int32 on {}".format(B, device))
+            pinned_regime = pinned_regime.contiguous()
         if state is not None:
             regime, mean, cov = self._switching_state(state, B, K, D, device)
             if index is not None:
@@ -2442,31 +2455,90 @@ class HipKernels:
         out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
         out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
         log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
+        outputs = (out_regime, out_mean, out_cov, log_weight)
         if log_weight.numel() == 0:
-            return out_regime, out_mean, out_cov, log_weight
-        per_particle = 8 + 2 * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) if state is not None else \
-            8 + (4 + 8 * D + 8 * TD) + 8
-        if observed is not None:
-            self._launch(device, self._lib.aesmc_switching_kalman_masked_step,
-                         (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms), None,
-                          None, _ptr(observation), _ptr(observed), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov),
-                          _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
-                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
-                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                         (model, regime, mean, cov, index, uniforms, observation, observed, out_regime, out_mean, out_cov,
-                          log_weight, block), name="switching_kalman_masked_step")
-            return out_regime, out_mean, out_cov, log_weight
-        self._launch(device, self._lib.aesmc_switching_kalman_step,
-                     (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
-                      _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_weight),
-                      _ptr(self.flags(device)), B, K, self._stream(observation)),
-                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
-                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                     (model, regime, mean, cov, index, uniforms, observation, out_regime, out_mean, out_cov, log_weight,
-                      block), name="switching_kalman_step")
-        return out_regime, out_mean, out_cov, log_weight
+            return outputs
+        # per particle: the uniform, the state written and (later steps) read, the weight, the index, the drawn-from row
+        per_particle = 8 + (2 if state is not None else 1) * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) + \
+            (8 * M if draw else 0)
+        head = (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms))
+        tail = (_ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_weight), _ptr(self.flags(device)), B, K,
+                self._stream(observation))
+        if observed is None:
+            middle = (_ptr(cdf), _ptr(observation)) if draw else (_ptr(pinned_regime), _ptr(observation)) if pinned else \
+                (_ptr(observation),)
+        else:
+            entry, name = self._lib.aesmc_switching_kalman_masked_step, masked_name
+            middle = (_ptr(cdf), _ptr(pinned_regime), _ptr(observation), _ptr(observed))
+        self._launch(device, entry, head + middle + tail,
+                     lambda: B * K * per_particle + (4 * B if pinned else 0) +
+                     B * Dy * (observation.element_size() + (0 if observed is None else 1)) +
+                     self._switching_model_bytes(M, D, Dy, rows=not draw),
+                     (model, regime, mean, cov, index, uniforms, cdf, pinned_regime, observation, observed, out_regime, out_mean,
+                      out_cov, log_weight, block), name=name)
+        return outputs
+
+    def switching_kalman_step(self, model, state, index, uniforms, observation, observed=None):
+        """One step of the Rao-Blackwellised filter of a switching linear-Gaussian model (aesmc_switching_kalman_step, K31).
+        model: a dict of dense float64 tensors cdf0 [M], cdf [M,M], m0 [D], s0 [D], A [M,D,D], b [M,D], q [M,D], C [M,Dy,D],
+        d [M,Dy], r [M,Dy]; state: None (step 0) or (regime int32 [B,K], mean float64 [B,K,D], cov float64 [B,K,D(D+1)/2])
+        — the STORED particles of the step before; index: int64 [B,K] or None (the identity); uniforms float64 [B,K];
+        observation float32 / float64 [B,Dy].  Returns (regime, mean, cov, log_weight [B,K] float64), new tensors.  An index
+        outside [0, K) or a stored regime outside [0, M) gives NaN there and FLAG_INDEX_OUT_OF_RANGE.
+        observed: None, or torch.bool [B,Dy] — the masked entry (aesmc_switching_kalman_masked_step, K39): row b's step is the
+        step of the model with the components deleted whose entry is False; y there is not used and may be NaN."""
+        return self._switching_kalman("switching_kalman_step", self._lib.aesmc_switching_kalman_step,
+                                      "switching_kalman_masked_step", model, state, index, uniforms, observation, observed)
 
     # ---- K32, K33 ------------------------------------------------------------------------------
+    def _switching_lookahead(self, name, entry, masked_entry, scores, model, log_prior, state, observation, num_particles,
+                             observed):
+        """`switching_lookahead` and `switching_lookahead_scores` (`scores`), called as `name`: one validation, the caller's C
+        `entry` (with `observed` its `masked_entry`), and the outputs in the order the entry takes them, which is the order
+        returned: (log_weight, cdf), or (scores, log_weight)."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        device = observation.device
+        block, M, D, Dy = self._switching_block(model, device)
+        if observation.dim() != 2 or observation.size(1) != Dy:
+            raise ValueError("aesmc_amd: observation must be [batch_size, {}], got {}".format(Dy, tuple(observation.shape)))
+        B = observation.size(0)
+        if state is None:
+            if num_particles is None or int(num_particles) < 0:
+                raise ValueError("aesmc_amd: {} without a state needs num_particles".format(name))
+            K = int(num_particles)
+        else:
+            K = state[0].size(1) if torch.is_tensor(state[0]) and state[0].dim() == 2 else -1
+            if num_particles is not None and int(num_particles) != K:
+                raise ValueError("aesmc_amd: num_particles ({}) disagrees with the state ({})".format(num_particles, K))
+        if not self.switching_covers(observation, M, D, Dy, K):
+            raise ValueError("aesmc_amd: {} does not take these operands (see switching_covers)".format(name))
+        _require_hip(log_prior, "log_prior")
+        want = (M,) if state is None else (M, M)
+        if tuple(log_prior.shape) != want or log_prior.dtype != torch.float64 or log_prior.device != device:
+            raise ValueError("aesmc_amd: log_prior must be {} float64 on {}, got {} {} on {}".format(
+                want, device, tuple(log_prior.shape), log_prior.dtype, log_prior.device))
+        log_prior = log_prior.contiguous()
+        regime, mean, cov = (None, None, None) if state is None else self._switching_state(state, B, K, D, device)
+        observation = observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
+        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
+        rows = torch.empty((B, K, M), dtype=torch.float64, device=device)      # the cumulative rows, or the scores
+        outputs = (rows, log_weight) if scores else (log_weight, rows)
+        if log_weight.numel() == 0:
+            return outputs
+        TD = D * (D + 1) // 2
+        per_particle = (4 + 8 * D + 8 * TD if state is not None else 0) + 8 + 8 * M
+        head = (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation))
+        tail = (_ptr(outputs[0]), _ptr(outputs[1]), _ptr(self.flags(device)), B, K, self._stream(observation))
+        self._launch(device, entry if observed is None else masked_entry,
+                     head + tail if observed is None else head + (_ptr(observed),) + tail,
+                     lambda: B * K * per_particle + B * Dy * (observation.element_size() + (0 if observed is None else 1)) +
+                     self._switching_model_bytes(M, D, Dy),
+                     (model, log_prior, regime, mean, cov, observation, observed, log_weight, rows, block))
+        return outputs
+
     def switching_lookahead(self, model, log_prior, state, observation, num_particles=None, observed=None):
         """The look-ahead of the fully adapted filter of a switching linear-Gaussian model (aesmc_switching_lookahead, K32):
         per stored particle one Kalman prediction per regime, the exact first-stage log-weight log p(y | history) and the
@@ -2474,56 +2546,9 @@ class HipKernels:
         float64 [M,M] with a state (log Pi), [M] without one (log pi0; `num_particles` then gives K).  Returns (log_weight
         [B,K], cdf [B,K,M]) float64, new tensors.  A stored regime outside [0, M) gives NaN there and
         FLAG_INDEX_OUT_OF_RANGE.  observed: as `switching_kalman_step`'s (aesmc_switching_masked_lookahead, K40)."""
-        _require_hip(observation, "observation")
-        tag = _tag(observation, "observation")
-        device = observation.device
-        block, M, D, Dy = self._switching_block(model, device)
-        if observation.dim() != 2 or observation.size(1) != Dy:
-            raise ValueError("aesmc_amd: observation must be [batch_size, {}], got {}".format(Dy, tuple(observation.shape)))
-        B = observation.size(0)
-        if state is None:
-            if num_particles is None or int(num_particles) < 0:
-                raise ValueError("aesmc_amd: switching_lookahead without a state needs num_particles")
-            K = int(num_particles)
-        else:
-            K = state[0].size(1) if torch.is_tensor(state[0]) and state[0].dim() == 2 else -1
-            if num_particles is not None and int(num_particles) != K:
-                raise ValueError("aesmc_amd: num_particles ({}) disagrees with the state ({})".format(num_particles, K))
-        if not self.switching_covers(observation, M, D, Dy, K):
-            raise ValueError("aesmc_amd: switching_lookahead does not take these operands (see switching_covers)")
-        _require_hip(log_prior, "log_prior")
-        want = (M,) if state is None else (M, M)
-        if tuple(log_prior.shape) != want or log_prior.dtype != torch.float64 or log_prior.device != device:
-            raise ValueError("aesmc_amd: log_prior must be {} float64 on {}, got {} {} on {}".format(
-                want, device, tuple(log_prior.shape), log_prior.dtype, log_prior.device))
-        log_prior = log_prior.contiguous()
-        regime, mean, cov = (None, None, None) if state is None else self._switching_state(state, B, K, D, device)
-        observation = observation.contiguous()
-        if observed is not None:
-            observed = self._switching_observed(observed, B, Dy, device)
-        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
-        cdf = torch.empty((B, K, M), dtype=torch.float64, device=device)
-        if log_weight.numel() == 0:
-            return log_weight, cdf
-        TD = D * (D + 1) // 2
-        per_particle = (4 + 8 * D + 8 * TD if state is not None else 0) + 8 + 8 * M
-        if observed is not None:
-            self._launch(device, self._lib.aesmc_switching_masked_lookahead,
-                         (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
-                          _ptr(observed), _ptr(log_weight), _ptr(cdf), _ptr(self.flags(device)), B, K,
-                          self._stream(observation)),
-                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
-                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                         (model, log_prior, regime, mean, cov, observation, observed, log_weight, cdf, block),
-                         name="switching_masked_lookahead")
-            return log_weight, cdf
-        self._launch(device, self._lib.aesmc_switching_lookahead,
-                     (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
-                      _ptr(log_weight), _ptr(cdf), _ptr(self.flags(device)), B, K, self._stream(observation)),
-                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
-                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                     (model, log_prior, regime, mean, cov, observation, log_weight, cdf, block), name="switching_lookahead")
-        return log_weight, cdf
+        return self._switching_lookahead("switching_lookahead", self._lib.aesmc_switching_lookahead,
+                                         self._lib.aesmc_switching_masked_lookahead, False, model, log_prior, state, observation,
+                                         num_particles, observed)
 
     # ---- K43, K44 ------------------------------------------------------------------------------
     def switching_lookahead_scores(self, model, log_prior, state, observation, num_particles=None, observed=None):
@@ -2531,57 +2556,9 @@ class HipKernels:
         K43; with `observed` aesmc_switching_masked_lookahead_scores): returns (scores [B,K,M], log_weight [B,K]) float64, new
         tensors — scores[b,k,j] = g_j as K32 defines it (-inf under a log-prior of -inf, NaN where a pivot is not positive
         under a finite one), log_weight K32's bit for bit.  Arguments, validation and flags as `switching_lookahead`'s."""
-        _require_hip(observation, "observation")
-        tag = _tag(observation, "observation")
-        device = observation.device
-        block, M, D, Dy = self._switching_block(model, device)
-        if observation.dim() != 2 or observation.size(1) != Dy:
-            raise ValueError("aesmc_amd: observation must be [batch_size, {}], got {}".format(Dy, tuple(observation.shape)))
-        B = observation.size(0)
-        if state is None:
-            if num_particles is None or int(num_particles) < 0:
-                raise ValueError("aesmc_amd: switching_lookahead_scores without a state needs num_particles")
-            K = int(num_particles)
-        else:
-            K = state[0].size(1) if torch.is_tensor(state[0]) and state[0].dim() == 2 else -1
-            if num_particles is not None and int(num_particles) != K:
-                raise ValueError("aesmc_amd: num_particles ({}) disagrees with the state ({})".format(num_particles, K))
-        if not self.switching_covers(observation, M, D, Dy, K):
-            raise ValueError("aesmc_amd: switching_lookahead_scores does not take these operands (see switching_covers)")
-        _require_hip(log_prior, "log_prior")
-        want = (M,) if state is None else (M, M)
-        if tuple(log_prior.shape) != want or log_prior.dtype != torch.float64 or log_prior.device != device:
-            raise ValueError("aesmc_amd: log_prior must be {} float64 on {}, got {} {} on {}".format(
-                want, device, tuple(log_prior.shape), log_prior.dtype, log_prior.device))
-        log_prior = log_prior.contiguous()
-        regime, mean, cov = (None, None, None) if state is None else self._switching_state(state, B, K, D, device)
-        observation = observation.contiguous()
-        if observed is not None:
-            observed = self._switching_observed(observed, B, Dy, device)
-        scores = torch.empty((B, K, M), dtype=torch.float64, device=device)
-        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
-        if log_weight.numel() == 0:
-            return scores, log_weight
-        TD = D * (D + 1) // 2
-        per_particle = (4 + 8 * D + 8 * TD if state is not None else 0) + 8 + 8 * M
-        if observed is not None:
-            self._launch(device, self._lib.aesmc_switching_masked_lookahead_scores,
-                         (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
-                          _ptr(observed), _ptr(scores), _ptr(log_weight), _ptr(self.flags(device)), B, K,
-                          self._stream(observation)),
-                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
-                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                         (model, log_prior, regime, mean, cov, observation, observed, scores, log_weight, block),
-                         name="switching_masked_lookahead_scores")
-            return scores, log_weight
-        self._launch(device, self._lib.aesmc_switching_lookahead_scores,
-                     (tag, ctypes.byref(block), _ptr(log_prior), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation),
-                      _ptr(scores), _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
-                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
-                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                     (model, log_prior, regime, mean, cov, observation, scores, log_weight, block),
-                     name="switching_lookahead_scores")
-        return scores, log_weight
+        return self._switching_lookahead("switching_lookahead_scores", self._lib.aesmc_switching_lookahead_scores,
+                                         self._lib.aesmc_switching_masked_lookahead_scores, True, model, log_prior, state,
+                                         observation, num_particles, observed)
 
     def switching_optimal_resample_max_candidates(self):
         """The most candidates K_in * M `switching_optimal_resample` keeps in LDS, as the library exports it."""
@@ -2636,62 +2613,9 @@ class HipKernels:
         K33): cdf float64 [B,K,M], read at the ancestor's position (`switching_lookahead`'s).  Returns (regime, mean, cov,
         log_likelihood [B,K] float64), new tensors; regimes, flags and NaNs as `switching_kalman_step`'s, and its
         `observed` (K39 with particle_cdf)."""
-        _require_hip(observation, "observation")
-        tag = _tag(observation, "observation")
-        _require_hip(uniforms, "regime uniforms")
-        device = observation.device
-        if uniforms.dim() != 2 or uniforms.dtype != torch.float64 or uniforms.device != device:
-            raise ValueError("aesmc_amd: regime uniforms must be [batch_size, num_particles] float64 on {}".format(device))
-        B, K = uniforms.shape
-        block, M, D, Dy = self._switching_block(model, device)
-        TD = D * (D + 1) // 2
-        if tuple(observation.shape) != (B, Dy):
-            raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
-        if not self.switching_covers(observation, M, D, Dy, K):
-            raise ValueError("aesmc_amd: switching_kalman_draw does not take these operands (see switching_covers)")
-        _require_hip(cdf, "cdf")
-        if tuple(cdf.shape) != (B, K, M) or cdf.dtype != torch.float64 or cdf.device != device:
-            raise ValueError("aesmc_amd: cdf must be {} float64 on {}".format((B, K, M), device))
-        cdf = cdf.contiguous()
-        if state is not None:
-            regime, mean, cov = self._switching_state(state, B, K, D, device)
-            if index is not None:
-                index = as_index(index)
-                if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != device:
-                    raise ValueError("aesmc_amd: index must be [{}, {}] int64 on {}".format(B, K, device))
-                index = index.contiguous()
-        else:
-            regime = mean = cov = index = None
-        uniforms, observation = uniforms.contiguous(), observation.contiguous()
-        if observed is not None:
-            observed = self._switching_observed(observed, B, Dy, device)
-        out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
-        out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
-        out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
-        log_likelihood = torch.empty((B, K), dtype=torch.float64, device=device)
-        if log_likelihood.numel() == 0:
-            return out_regime, out_mean, out_cov, log_likelihood
-        per_particle = 8 + 8 * M + (2 if state is not None else 1) * (4 + 8 * D + 8 * TD) + 8 + \
-            (8 if index is not None else 0)
-        if observed is not None:
-            self._launch(device, self._lib.aesmc_switching_kalman_masked_step,
-                         (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
-                          _ptr(cdf), None, _ptr(observation), _ptr(observed), _ptr(out_regime), _ptr(out_mean),
-                          _ptr(out_cov), _ptr(log_likelihood), _ptr(self.flags(device)), B, K, self._stream(observation)),
-                         lambda: B * K * per_particle + B * Dy * (observation.element_size() + 1) +
-                         8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
-                         (model, regime, mean, cov, index, uniforms, cdf, observation, observed, out_regime, out_mean,
-                          out_cov, log_likelihood, block), name="switching_kalman_masked_draw")
-            return out_regime, out_mean, out_cov, log_likelihood
-        self._launch(device, self._lib.aesmc_switching_kalman_draw,
-                     (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms), _ptr(cdf),
-                      _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_likelihood),
-                      _ptr(self.flags(device)), B, K, self._stream(observation)),
-                     lambda: B * K * per_particle + B * Dy * observation.element_size() +
-                     8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
-                     (model, regime, mean, cov, index, uniforms, cdf, observation, out_regime, out_mean, out_cov,
-                      log_likelihood, block), name="switching_kalman_draw")
-        return out_regime, out_mean, out_cov, log_likelihood
+        return self._switching_kalman("switching_kalman_draw", self._lib.aesmc_switching_kalman_draw,
+                                      "switching_kalman_masked_draw", model, state, index, uniforms, observation, observed,
+                                      cdf=cdf, draw=True)
 
     # ---- K34, K35 ------------------------------------------------------------------------------
     def switching_backward_covers(self, observation, num_regimes, latent_dim, observation_dim, num_particles,
@@ -2744,24 +2668,15 @@ class HipKernels:
         if out_c.numel() == 0:
             return out_omega, out_lam, out_c, factor
         per_trajectory = 4 + (2 if info is not None else 1) * 8 * (TD + D + 1) + 8 * TD
-        if observed is not None:
-            self._launch(device, self._lib.aesmc_switching_masked_information_step,
-                         (tag, ctypes.byref(block), _ptr(regime_next), _ptr(omega), _ptr(lam), _ptr(c), _ptr(observation),
-                          _ptr(observed), _ptr(out_omega), _ptr(out_lam), _ptr(out_c), _ptr(factor),
-                          _ptr(self.flags(device)), B, N, self._stream(observation)),
-                         lambda: B * N * per_trajectory + B * Dy * (observation.element_size() + 1) +
-                         8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
-                         (model, regime_next, omega, lam, c, observation, observed, out_omega, out_lam, out_c, factor, block),
-                         name="switching_masked_information_step")
-            return out_omega, out_lam, out_c, factor
-        self._launch(device, self._lib.aesmc_switching_information_step,
-                     (tag, ctypes.byref(block), _ptr(regime_next), _ptr(omega), _ptr(lam), _ptr(c), _ptr(observation),
-                      _ptr(out_omega), _ptr(out_lam), _ptr(out_c), _ptr(factor), _ptr(self.flags(device)), B, N,
-                      self._stream(observation)),
-                     lambda: B * N * per_trajectory + B * Dy * observation.element_size() +
-                     8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
-                     (model, regime_next, omega, lam, c, observation, out_omega, out_lam, out_c, factor, block),
-                     name="switching_information_step")
+        head = (tag, ctypes.byref(block), _ptr(regime_next), _ptr(omega), _ptr(lam), _ptr(c), _ptr(observation))
+        tail = (_ptr(out_omega), _ptr(out_lam), _ptr(out_c), _ptr(factor), _ptr(self.flags(device)), B, N,
+                self._stream(observation))
+        self._launch(device, self._lib.aesmc_switching_information_step if observed is None else
+                     self._lib.aesmc_switching_masked_information_step,
+                     head + tail if observed is None else head + (_ptr(observed),) + tail,
+                     lambda: B * N * per_trajectory + B * Dy * (observation.element_size() + (0 if observed is None else 1)) +
+                     self._switching_model_bytes(M, D, Dy, rows=False),
+                     (model, regime_next, omega, lam, c, observation, observed, out_omega, out_lam, out_c, factor, block))
         return out_omega, out_lam, out_c, factor
 
     def switching_backward_scores(self, log_Pi, regime_next, factor, lam, state, log_w=None):
@@ -2868,22 +2783,16 @@ class HipKernels:
             return out_mean, out_cov, out_cross
         per_trajectory = 8 * (2 * D + 3 * TD) + \
             ((4 + 8 * (TD + D * D) + (8 * TD if omega_next is not None else 0)) if cross else 0)
-        if observed_next is not None:
-            self._launch(device, self._lib.aesmc_switching_masked_smooth_combine,
-                         (ctypes.byref(block), _ptr(regime_next), _ptr(mean), _ptr(cov), _ptr(factor), _ptr(lam),
-                          _ptr(omega_next), _ptr(cov_next), _ptr(observed_next), _ptr(out_mean), _ptr(out_cov),
-                          _ptr(out_cross), _ptr(self.flags(device)), B, N, D, self._stream(mean)),
-                         lambda: B * N * per_trajectory + B * Dy + 8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
-                         (model, regime_next, mean, cov, factor, lam, omega_next, cov_next, observed_next, out_mean, out_cov,
-                          out_cross, block), name="switching_masked_smooth_combine")
-            return out_mean, out_cov, out_cross
-        self._launch(device, self._lib.aesmc_switching_smooth_combine,
-                     (None if block is None else ctypes.byref(block), _ptr(regime_next), _ptr(mean), _ptr(cov), _ptr(factor),
-                      _ptr(lam), _ptr(omega_next), _ptr(cov_next), _ptr(out_mean), _ptr(out_cov), _ptr(out_cross),
-                      _ptr(self.flags(device)), B, N, D, self._stream(mean)),
-                     lambda: B * N * per_trajectory + 8 * M * (D * D + 2 * D + Dy * D + 2 * Dy),
-                     (model, regime_next, mean, cov, factor, lam, omega_next, cov_next, out_mean, out_cov, out_cross, block),
-                     name="switching_smooth_combine")
+        head = (None if block is None else ctypes.byref(block), _ptr(regime_next), _ptr(mean), _ptr(cov), _ptr(factor),
+                _ptr(lam), _ptr(omega_next), _ptr(cov_next))
+        tail = (_ptr(out_mean), _ptr(out_cov), _ptr(out_cross), _ptr(self.flags(device)), B, N, D, self._stream(mean))
+        self._launch(device, self._lib.aesmc_switching_smooth_combine if observed_next is None else
+                     self._lib.aesmc_switching_masked_smooth_combine,
+                     head + tail if observed_next is None else head + (_ptr(observed_next),) + tail,
+                     lambda: B * N * per_trajectory + (0 if observed_next is None else B * Dy) +
+                     self._switching_model_bytes(M, D, Dy, rows=False),
+                     (model, regime_next, mean, cov, factor, lam, omega_next, cov_next, observed_next, out_mean, out_cov, out_cross,
+                      block))
         return out_mean, out_cov, out_cross
 
     # ---- K37, K38 ------------------------------------------------------------------------------
@@ -2954,63 +2863,9 @@ class HipKernels:
         pinned_regime int32 [B], the regime particle (b, K-1) takes in place of its draw.  Returns (regime, mean, cov,
         log_weight [B,K] float64), new tensors; flags and NaNs as `switching_kalman_step`'s, a pinned regime outside [0, M)
         as a stored one.  observed: as `switching_kalman_step`'s (K39 with pinned_regime)."""
-        _require_hip(observation, "observation")
-        tag = _tag(observation, "observation")
-        _require_hip(uniforms, "regime uniforms")
-        device = observation.device
-        if uniforms.dim() != 2 or uniforms.dtype != torch.float64 or uniforms.device != device:
-            raise ValueError("aesmc_amd: regime uniforms must be [batch_size, num_particles] float64 on {}".format(device))
-        B, K = uniforms.shape
-        block, M, D, Dy = self._switching_block(model, device)
-        TD = D * (D + 1) // 2
-        if tuple(observation.shape) != (B, Dy):
-            raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
-        if not self.switching_covers(observation, M, D, Dy, K):
-            raise ValueError("aesmc_amd: switching_kalman_conditional_step does not take these operands (see "
-                             "switching_covers)")
-        _require_hip(pinned_regime, "pinned_regime")
-        if tuple(pinned_regime.shape) != (B,) or pinned_regime.dtype != torch.int32 or pinned_regime.device != device:
-            raise ValueError("aesmc_amd: pinned_regime must be [{}] int32 on {}".format(B, device))
-        pinned_regime = pinned_regime.contiguous()
-        if state is not None:
-            regime, mean, cov = self._switching_state(state, B, K, D, device)
-            if index is not None:
-                index = as_index(index)
-                if tuple(index.shape) != (B, K) or index.dtype != torch.int64 or index.device != device:
-                    raise ValueError("aesmc_amd: index must be [{}, {}] int64 on {}".format(B, K, device))
-                index = index.contiguous()
-        else:
-            regime = mean = cov = index = None
-        uniforms, observation = uniforms.contiguous(), observation.contiguous()
-        if observed is not None:
-            observed = self._switching_observed(observed, B, Dy, device)
-        out_regime = torch.empty((B, K), dtype=torch.int32, device=device)
-        out_mean = torch.empty((B, K, D), dtype=torch.float64, device=device)
-        out_cov = torch.empty((B, K, TD), dtype=torch.float64, device=device)
-        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
-        if log_weight.numel() == 0:
-            return out_regime, out_mean, out_cov, log_weight
-        per_particle = 8 + 2 * (4 + 8 * D + 8 * TD) + 8 + (8 if index is not None else 0) if state is not None else \
-            8 + (4 + 8 * D + 8 * TD) + 8
-        if observed is not None:
-            self._launch(device, self._lib.aesmc_switching_kalman_masked_step,
-                         (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms), None,
-                          _ptr(pinned_regime), _ptr(observation), _ptr(observed), _ptr(out_regime), _ptr(out_mean),
-                          _ptr(out_cov), _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
-                         lambda: B * K * per_particle + 4 * B + B * Dy * (observation.element_size() + 1) +
-                         8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                         (model, regime, mean, cov, index, uniforms, pinned_regime, observation, observed, out_regime,
-                          out_mean, out_cov, log_weight, block), name="switching_kalman_masked_conditional_step")
-            return out_regime, out_mean, out_cov, log_weight
-        self._launch(device, self._lib.aesmc_switching_kalman_conditional_step,
-                     (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(index), _ptr(uniforms),
-                      _ptr(pinned_regime), _ptr(observation), _ptr(out_regime), _ptr(out_mean), _ptr(out_cov),
-                      _ptr(log_weight), _ptr(self.flags(device)), B, K, self._stream(observation)),
-                     lambda: B * K * per_particle + 4 * B + B * Dy * observation.element_size() +
-                     8 * M * (M + D * D + 2 * D + Dy * D + 2 * Dy),
-                     (model, regime, mean, cov, index, uniforms, pinned_regime, observation, out_regime, out_mean, out_cov,
-                      log_weight, block), name="switching_kalman_conditional_step")
-        return out_regime, out_mean, out_cov, log_weight
+        return self._switching_kalman("switching_kalman_conditional_step", self._lib.aesmc_switching_kalman_conditional_step,
+                                      "switching_kalman_masked_conditional_step", model, state, index, uniforms, observation,
+                                      observed, pinned_regime=pinned_regime, pinned=True)
 
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256

@@ -21,13 +21,7 @@ SOURCES = ["abi.hip", "logweight_lse.hip", "ancestor_index.hip", "ancestor_index
            "linear_gaussian_initial.hip", "adapted_step.hip", "adapted_step_backward.hip",
            "switching_kalman.hip", "switching_lookahead.hip", "switching_information.hip", "switching_backward.hip",
            "switching_smooth.hip", "switching_conditional.hip", "switching_optimal_resample.hip"]
-HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "ancestor_index.hpp"), os.path.join(CSRC, "pairwise_gaussian.hpp"),
-           os.path.join(CSRC, "linear_gaussian.hpp"), os.path.join(CSRC, "adapted_step.hpp"),
-           os.path.join(CSRC, "philox_normal.hpp"), os.path.join(CSRC, "linear_gaussian_fused.hpp"),
-           os.path.join(CSRC, "linear_gaussian_backward.hpp"), os.path.join(CSRC, "linear_gaussian_wide_generic.hpp"),
-           os.path.join(CSRC, "switching_kalman.hpp"), os.path.join(CSRC, "switching_score.hpp"),
-           os.path.join(CSRC, "conditional_cdf.hpp"),
-           os.path.join(os.path.dirname(HERE), "include", "aesmc_hip.h")]
+HEADER = os.path.join(os.path.dirname(HERE), "include", "aesmc_hip.h")      # the C ABI (csrc/common.hpp includes it)
 ARCH = "gfx950"
 # per translation unit: the generic matrix-core step's product loops are 96 - 128 operand groups of eight v_mfma each, written
 # as ONE loop that must be unrolled in full (the accumulator tiles are register arrays indexed by the loop counter); the
@@ -63,7 +57,9 @@ def needs_build():
     if not os.path.exists(LIB_PATH):
         return True
     built = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS
+    deps = {HEADER}
+    for source in SOURCES:      # every source and whatever it includes, as the per-object check below
+        _depends_on(os.path.join(CSRC, source), deps)
     return any(os.path.getmtime(d) > built for d in deps)
 
 

@@ -26,6 +26,7 @@
 //   <8>     200      0        0             2       P in LDS
 // (the score itself is switching_pair_score of switching_score.hpp, which K37 calls too)
 // Measured (profiles/switching_smoother.txt, B = 64, K = 1024, N = 64: 4.2 million pairs): 98 us at D = 4, 342 us at D = 8.
+#include "switching_host.hpp"
 #include "switching_score.hpp"
 
 namespace aesmc {
@@ -110,17 +111,6 @@ __global__ __launch_bounds__(kSkBlock) void switching_backward_kernel(const Back
   }
 }
 
-template <int DP>
-static bool sb_launch(dim3 grid, size_t lds, hipStream_t s, const BackwardScoreArgs &a) {
-  // the 8-wide instantiation (72 KB of covariances beside the tile) needs the limit raised, as K31's
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_backward_kernel<DP>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return false;
-  hipLaunchKernelGGL((switching_backward_kernel<DP>), grid, dim3(kSkBlock), lds, s, a);
-  return true;
-}
-
 }  // namespace aesmc
 
 extern "C" int aesmc_switching_backward_scores(const double *log_Pi, const int32_t *regime_next, const double *factor,
@@ -129,20 +119,17 @@ extern "C" int aesmc_switching_backward_scores(const double *log_Pi, const int32
                                                int64_t B, int64_t K, int64_t N, int64_t M, int64_t D, void *stream) {
   using namespace aesmc;
   if (log_Pi == nullptr || regime_next == nullptr || factor == nullptr || lambda == nullptr || regime == nullptr ||
-      mean == nullptr || cov == nullptr || scores == nullptr || B < 0 || K < 0 || N < 0 || M < 1 || D < 1)
+      mean == nullptr || cov == nullptr || scores == nullptr || B < 0 || K < 0 || N < 0 || !sk_extents_positive(M, D, 1))
     return AESMC_ERR_INVALID_ARGUMENT;
   if (!sk_aligned(log_Pi, 8) || !sk_aligned(regime_next, 4) || !sk_aligned(factor, 8) || !sk_aligned(lambda, 8) ||
       !sk_aligned(regime, 4) || !sk_aligned(mean, 8) || !sk_aligned(cov, 8) || !sk_aligned(log_w, 8) ||
       !sk_aligned(scores, 8) || !sk_aligned(flags, 4))
     return AESMC_ERR_INVALID_ARGUMENT;
-  const void *inputs[] = {log_Pi, regime_next, factor, lambda, regime, mean, cov, log_w};
-  for (const void *in : inputs)
-    if (in == scores) return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_outputs_distinct({scores}, {log_Pi, regime_next, factor, lambda, regime, mean, cov, log_w}))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (B == 0 || N == 0 || K == 0) return AESMC_OK;
-  if (D > kSkMaxDim || M > kSkMaxRegimes) return AESMC_ERR_UNSUPPORTED;
-  constexpr int64_t kLimit = 0x7fffffffLL;
-  constexpr int64_t kTri = kSkMaxDim * (kSkMaxDim + 1) / 2;
-  if (B > kLimit || K > kLimit || N > kLimit || B * K > kLimit / kTri || B * N > kLimit / kTri || B * N > kLimit / K)
+  if (!sk_extents_supported(M, D, 1) || !sk_fits_32bit(B, K, kSkTriMax) || !sk_fits_32bit(B, N, kSkTriMax) ||
+      !sk_fits_32bit(B, N, K))      // (the last: B N K scores)
     return AESMC_ERR_UNSUPPORTED;
   BackwardScoreArgs a;
   a.log_Pi = log_Pi, a.regime_next = regime_next, a.factor = factor, a.lambda = lambda;
@@ -155,8 +142,7 @@ extern "C" int aesmc_switching_backward_scores(const double *log_Pi, const int32
   const int tp = dp * (dp + 1) / 2;
   const size_t lds = ((size_t)kSbTile * (tp + dp + a.M) + (sk_cov_in_lds(dp) ? (size_t)tp * kSkBlock : 0)) * sizeof(double);
   const dim3 grid((unsigned)(B * a.n_tiles * a.k_tiles));      // (at most B N K workgroups: within 32 bits by the check above)
-  hipStream_t s = (hipStream_t)stream;
-  const bool launched = dp == 2 ? sb_launch<2>(grid, lds, s, a) : dp == 4 ? sb_launch<4>(grid, lds, s, a)
-                                                                          : sb_launch<8>(grid, lds, s, a);
-  return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+  return sk_for_extent(dp, [&](auto d) {
+    return sk_launch(&switching_backward_kernel<decltype(d)::value>, grid, dim3(kSkBlock), lds, (hipStream_t)stream, a);
+  });
 }

@@ -33,6 +33,7 @@
 // D = 8, against 43 us and 327 us for the four launches it replaces.
 #include "ancestor_index.hpp"
 #include "conditional_cdf.hpp"
+#include "switching_host.hpp"
 #include "switching_score.hpp"
 
 namespace aesmc {
@@ -192,15 +193,12 @@ __global__ __launch_bounds__(NT) void switching_conditional_kernel(const Switchi
   }
 }
 
+// (not sk_launch: this kernel's limit is raised once per device, as the resampling kernels' is)
 template <int DP, int NT> static int sc_launch(int64_t B, size_t lds, hipStream_t s, const SwitchingConditionalArgs &a) {
   const int raised = raise_dynamic_lds_cap<switching_conditional_kernel<DP, NT>>();
   if (raised != AESMC_OK) return raised;
   hipLaunchKernelGGL((switching_conditional_kernel<DP, NT>), dim3((unsigned)B), dim3(NT), lds, s, a);
   return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
-}
-
-template <int DP> static int sc_launch_lanes(int lanes, int64_t B, size_t lds, hipStream_t s, const SwitchingConditionalArgs &a) {
-  return lanes == kWave ? sc_launch<DP, kWave>(B, lds, s, a) : sc_launch<DP, kSkBlock>(B, lds, s, a);
 }
 
 }  // namespace aesmc
@@ -215,7 +213,7 @@ extern "C" int aesmc_switching_conditional_ancestor_index(const double *log_w, c
                                                           const double *cov, int64_t *out_idx, int32_t *flags, int64_t B,
                                                           int64_t K, int64_t M, int64_t D, void *stream) {
   using namespace aesmc;
-  if (log_w == nullptr || u == nullptr || out_idx == nullptr || B < 0 || K < 0 || M < 1 || D < 1)
+  if (log_w == nullptr || u == nullptr || out_idx == nullptr || B < 0 || K < 0 || !sk_extents_positive(M, D, 1))
     return AESMC_ERR_INVALID_ARGUMENT;
   const bool pinned = factor != nullptr;
   if (pinned != (lambda != nullptr)) return AESMC_ERR_INVALID_ARGUMENT;
@@ -225,13 +223,10 @@ extern "C" int aesmc_switching_conditional_ancestor_index(const double *log_w, c
       !sk_aligned(factor, 8) || !sk_aligned(lambda, 8) || !sk_aligned(regime, 4) || !sk_aligned(mean, 8) ||
       !sk_aligned(cov, 8) || !sk_aligned(out_idx, 8) || !sk_aligned(flags, 4))
     return AESMC_ERR_INVALID_ARGUMENT;
-  const void *inputs[] = {log_w, u, log_Pi, regime_next, factor, lambda, regime, mean, cov};
-  for (const void *in : inputs)
-    if (in == out_idx) return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_outputs_distinct({out_idx}, {log_w, u, log_Pi, regime_next, factor, lambda, regime, mean, cov}))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (B == 0 || K == 0) return AESMC_OK;
-  if (D > kSkMaxDim || M > kSkMaxRegimes || K > sc_max_particles(D) || B > 0x7fffffffLL ||
-      B * K > 0x7fffffffLL / (kSkMaxDim * (kSkMaxDim + 1) / 2))
-    return AESMC_ERR_UNSUPPORTED;
+  if (!sk_extents_supported(M, D, 1) || K > sc_max_particles(D) || !sk_fits_32bit(B, K, kSkTriMax)) return AESMC_ERR_UNSUPPORTED;
   SwitchingConditionalArgs a;
   a.log_w = log_w, a.u = u, a.log_Pi = log_Pi, a.regime_next = regime_next;
   a.factor = factor, a.lambda = lambda, a.regime = regime, a.mean = mean, a.cov = cov;
@@ -242,6 +237,8 @@ extern "C" int aesmc_switching_conditional_ancestor_index(const double *log_w, c
   const int lanes = K <= kWave ? kWave : kSkBlock;
   const size_t lds = sc_lds_bytes(K, dp, lanes, pinned);
   hipStream_t s = (hipStream_t)stream;
-  return dp == 2 ? sc_launch_lanes<2>(lanes, B, lds, s, a)
-                 : dp == 4 ? sc_launch_lanes<4>(lanes, B, lds, s, a) : sc_launch_lanes<8>(lanes, B, lds, s, a);
+  return sk_for_extent(dp, [&](auto d) {
+    constexpr int DP = decltype(d)::value;
+    return lanes == kWave ? sc_launch<DP, kWave>(B, lds, s, a) : sc_launch<DP, kSkBlock>(B, lds, s, a);
+  });
 }

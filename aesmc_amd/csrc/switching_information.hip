@@ -39,7 +39,7 @@
 // There are B N trajectories, not B N K pairs: this launch is a tenth of a step at N = 64, K = 1024 (profiles/
 // switching_smoother.txt).  The 8-wide instantiations keep Oh, L and X (36 + 36 + 64 float64) live at once and move through
 // the accumulation registers; none uses scratch, and they are not given K31's LDS layout.
-#include "switching_kalman.hpp"
+#include "switching_host.hpp"
 
 namespace aesmc {
 
@@ -277,76 +277,44 @@ __global__ __launch_bounds__(kSkBlock) void switching_information_kernel(const I
     if (e < TD) f_out[e] = F[e];
 }
 
-template <int DP, int DYP, bool Masked>
-static void si_launch(dim3 grid, size_t lds, hipStream_t s, const InformationArgs &a) {
-  hipLaunchKernelGGL((switching_information_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
-}
-
-template <int DP, bool Masked>
-static void si_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const InformationArgs &a) {
-  if (dyp == 2) si_launch<DP, 2, Masked>(grid, lds, s, a);
-  else if (dyp == 4) si_launch<DP, 4, Masked>(grid, lds, s, a);
-  else si_launch<DP, 8, Masked>(grid, lds, s, a);
-}
-
-template <bool Masked>
-static void si_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const InformationArgs &a) {
-  if (dp == 2) si_launch_dy<2, Masked>(dyp, grid, lds, s, a);
-  else if (dp == 4) si_launch_dy<4, Masked>(dyp, grid, lds, s, a);
-  else si_launch_dy<8, Masked>(dyp, grid, lds, s, a);
-}
-
 // K34, and K41 (`masked`: observed [B,Dy] given): one set of checks, one launch
 static int si_step(bool masked, const uint8_t *observed, int y_dtype, const aesmc_switching_model *model,
                    const int32_t *regime_next, const double *omega_in, const double *lambda_in, const double *c_in,
                    const void *y, double *omega_out, double *lambda_out, double *c_out, double *factor_out, int32_t *flags,
                    int64_t B, int64_t N, void *stream) {
-  if (masked && (observed == nullptr || (const void *)observed == omega_out || (const void *)observed == lambda_out ||
-                 (const void *)observed == c_out || (const void *)observed == factor_out))
+  if (masked && observed == nullptr) return AESMC_ERR_INVALID_ARGUMENT;
+  if (model == nullptr || regime_next == nullptr || omega_out == nullptr || lambda_out == nullptr || c_out == nullptr ||
+      factor_out == nullptr || B < 0 || N < 0)
     return AESMC_ERR_INVALID_ARGUMENT;
-  if (model == nullptr || regime_next == nullptr || y == nullptr || omega_out == nullptr || lambda_out == nullptr ||
-      c_out == nullptr || factor_out == nullptr || B < 0 || N < 0)
-    return AESMC_ERR_INVALID_ARGUMENT;
-  if (y_dtype != AESMC_F32 && y_dtype != AESMC_F64) return AESMC_ERR_INVALID_ARGUMENT;
   const bool later = omega_in != nullptr;
   if (later != (lambda_in != nullptr) || later != (c_in != nullptr)) return AESMC_ERR_INVALID_ARGUMENT;
-  if (model->M < 1 || model->D < 1 || model->Dy < 1) return AESMC_ERR_INVALID_ARGUMENT;
-  const double *operands[] = {model->A, model->b, model->q, model->C, model->d, model->r};
-  for (const double *p : operands)
-    if (p == nullptr || !sk_aligned(p, 8)) return AESMC_ERR_INVALID_ARGUMENT;
-  if (!sk_aligned(regime_next, 4) || !sk_aligned(omega_in, 8) || !sk_aligned(lambda_in, 8) || !sk_aligned(c_in, 8) ||
-      !sk_aligned(y, y_dtype == AESMC_F32 ? 4 : 8) || !sk_aligned(omega_out, 8) || !sk_aligned(lambda_out, 8) ||
-      !sk_aligned(c_out, 8) || !sk_aligned(factor_out, 8) || !sk_aligned(flags, 4))
+  if (!sk_observation(y, y_dtype) || !sk_extents_positive(model->M, model->D, model->Dy) || !sk_model_operands(model, false))
     return AESMC_ERR_INVALID_ARGUMENT;
-  const void *outputs[] = {omega_out, lambda_out, c_out, factor_out};
-  const void *inputs[] = {regime_next, omega_in, lambda_in, c_in, y};
-  for (int i = 0; i < 4; ++i) {
-    for (const void *in : inputs)
-      if (outputs[i] == in) return AESMC_ERR_INVALID_ARGUMENT;
-    for (int o = 0; o < i; ++o)
-      if (outputs[i] == outputs[o]) return AESMC_ERR_INVALID_ARGUMENT;
-  }
+  if (!sk_aligned(regime_next, 4) || !sk_aligned(omega_in, 8) || !sk_aligned(lambda_in, 8) || !sk_aligned(c_in, 8) ||
+      !sk_aligned(omega_out, 8) || !sk_aligned(lambda_out, 8) || !sk_aligned(c_out, 8) || !sk_aligned(factor_out, 8) ||
+      !sk_aligned(flags, 4))
+    return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_outputs_distinct({omega_out, lambda_out, c_out, factor_out}, {regime_next, omega_in, lambda_in, c_in, y, observed}))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (B == 0 || N == 0) return AESMC_OK;
-  if (model->D > kSkMaxDim || model->Dy > kSkMaxDim || model->M > kSkMaxRegimes) return AESMC_ERR_UNSUPPORTED;
-  if (B > 0x7fffffffLL || N > 0x7fffffffLL || B * N > 0x7fffffffLL / (kSkMaxDim * (kSkMaxDim + 1) / 2))
-    return AESMC_ERR_UNSUPPORTED;
+  if (!sk_extents_supported(model->M, model->D, model->Dy) || !sk_fits_32bit(B, N, kSkTriMax)) return AESMC_ERR_UNSUPPORTED;
   InformationArgs a;
-  a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
+  sk_fill_model(a, model);
   a.regime_next = regime_next;
   a.omega_in = omega_in, a.lambda_in = lambda_in, a.c_in = c_in, a.y = y;
   a.observed = masked ? observed : nullptr;
   a.omega_out = omega_out, a.lambda_out = lambda_out, a.c_out = c_out, a.factor_out = factor_out;
   a.flags = flags;
   a.total = B * N, a.N = (uint32_t)N;
-  a.M = (int)model->M, a.D = (int)model->D, a.Dy = (int)model->Dy;
   a.y_is_float = y_dtype == AESMC_F32;
   const int dp = sk_pad(model->D), dyp = sk_pad(model->Dy);
-  const size_t lds = (size_t)a.M * sk_per_regime(dp, dyp) * sizeof(double);
-  const dim3 grid((unsigned)((a.total + kSkBlock - 1) / kSkBlock));
-  hipStream_t s = (hipStream_t)stream;
-  if (masked) si_launch_d<true>(dp, dyp, grid, lds, s, a);
-  else si_launch_d<false>(dp, dyp, grid, lds, s, a);
-  return hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+  const size_t lds = (size_t)a.M * sk_per_regime(dp, dyp) * sizeof(double);      // (at most 20 KB: the limit is never raised)
+  return sk_for_extents(dp, dyp, [&](auto d, auto dy) {
+    return sk_for_flag(masked, [&](auto m) {
+      return sk_launch(&switching_information_kernel<decltype(d)::value, decltype(dy)::value, decltype(m)::value>,
+                       sk_grid(a.total), dim3(kSkBlock), lds, (hipStream_t)stream, a);
+    });
+  });
 }
 
 }  // namespace aesmc

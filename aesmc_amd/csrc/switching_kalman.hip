@@ -62,7 +62,7 @@
 //
 // Traffic per particle at D = Dy = 4: 8 (ancestor) + 8 (uniform) + 2 (4 + 32 + 80) (state in and out) + 8 (log-weight) =
 // 256 bytes; at D = 8: 736 bytes.
-#include "switching_kalman.hpp"
+#include "switching_host.hpp"
 
 namespace aesmc {
 
@@ -319,32 +319,6 @@ __global__ __launch_bounds__(kSkBlock) void switching_kalman_kernel(const Switch
   }
 }
 
-template <int DP, int DYP, bool Masked>
-static bool sk_launch(dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
-  // the 8-wide instantiations (72 KB of covariances beside the model) need the limit raised; on every launch — no state to
-  // share between threads or devices, and the call is cheap beside the kernel
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_kalman_kernel<DP, DYP, Masked>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return false;
-  hipLaunchKernelGGL((switching_kalman_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
-  return true;
-}
-
-template <int DP, bool Masked>
-static bool sk_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
-  if (dyp == 2) return sk_launch<DP, 2, Masked>(grid, lds, s, a);
-  if (dyp == 4) return sk_launch<DP, 4, Masked>(grid, lds, s, a);
-  return sk_launch<DP, 8, Masked>(grid, lds, s, a);
-}
-
-template <bool Masked>
-static bool sk_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const SwitchingArgs &a) {
-  if (dp == 2) return sk_launch_dy<2, Masked>(dyp, grid, lds, s, a);
-  if (dp == 4) return sk_launch_dy<4, Masked>(dyp, grid, lds, s, a);
-  return sk_launch_dy<8, Masked>(dyp, grid, lds, s, a);
-}
-
 }  // namespace aesmc
 
 extern "C" int64_t aesmc_switching_max_latent_dim(void) { return aesmc::kSkMaxDim; }
@@ -361,57 +335,51 @@ static int sk_step(bool draw, bool pinned, bool masked, const uint8_t *observed,
                    const double *particle_cdf, const int32_t *pinned_regime, const void *y, int32_t *regime_out,
                    double *mean_out, double *cov_out, double *log_weight, int32_t *flags, int64_t B, int64_t K,
                    void *stream) {
-  if (draw && (particle_cdf == nullptr || !sk_aligned(particle_cdf, 8))) return AESMC_ERR_INVALID_ARGUMENT;
+  if (draw && (particle_cdf == nullptr || !sk_aligned(particle_cdf, 8) ||
+               sk_among(particle_cdf, {mean_out, cov_out, log_weight})))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (pinned && (pinned_regime == nullptr || !sk_aligned(pinned_regime, 4) || pinned_regime == regime_out))
     return AESMC_ERR_INVALID_ARGUMENT;
-  if (masked && (observed == nullptr || (const void *)observed == regime_out || (const void *)observed == mean_out ||
-                 (const void *)observed == cov_out || (const void *)observed == log_weight))
+  if (masked && (observed == nullptr || sk_among(observed, {regime_out, mean_out, cov_out, log_weight})))
     return AESMC_ERR_INVALID_ARGUMENT;
-  if (model == nullptr || uniforms == nullptr || y == nullptr || regime_out == nullptr || mean_out == nullptr ||
-      cov_out == nullptr || log_weight == nullptr || B < 0 || K < 0)
+  if (model == nullptr || uniforms == nullptr || regime_out == nullptr || mean_out == nullptr || cov_out == nullptr ||
+      log_weight == nullptr || B < 0 || K < 0)
     return AESMC_ERR_INVALID_ARGUMENT;
-  if (y_dtype != AESMC_F32 && y_dtype != AESMC_F64) return AESMC_ERR_INVALID_ARGUMENT;
   const bool later = regime_in != nullptr;
   if (later != (mean_in != nullptr) || later != (cov_in != nullptr)) return AESMC_ERR_INVALID_ARGUMENT;
-  if (model->M < 1 || model->D < 1 || model->Dy < 1) return AESMC_ERR_INVALID_ARGUMENT;
   const double *rows = later ? model->cdf : model->cdf0;
   if (!draw && (rows == nullptr || !sk_aligned(rows, 8))) return AESMC_ERR_INVALID_ARGUMENT;
-  const double *operands[] = {model->m0, model->s0, model->A, model->b, model->q, model->C, model->d, model->r};
-  for (const double *p : operands)
-    if (p == nullptr || !sk_aligned(p, 8)) return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_observation(y, y_dtype) || !sk_extents_positive(model->M, model->D, model->Dy) || !sk_model_operands(model, true))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (!sk_aligned(regime_in, 4) || !sk_aligned(mean_in, 8) || !sk_aligned(cov_in, 8) || !sk_aligned(idx, 8) ||
-      !sk_aligned(uniforms, 8) || !sk_aligned(y, y_dtype == AESMC_F32 ? 4 : 8) || !sk_aligned(regime_out, 4) ||
-      !sk_aligned(mean_out, 8) || !sk_aligned(cov_out, 8) || !sk_aligned(log_weight, 8) || !sk_aligned(flags, 4))
+      !sk_aligned(uniforms, 8) || !sk_aligned(regime_out, 4) || !sk_aligned(mean_out, 8) || !sk_aligned(cov_out, 8) ||
+      !sk_aligned(log_weight, 8) || !sk_aligned(flags, 4))
     return AESMC_ERR_INVALID_ARGUMENT;
   if (later && (regime_out == regime_in || mean_out == mean_in || cov_out == cov_in)) return AESMC_ERR_INVALID_ARGUMENT;
-  if (draw && (particle_cdf == mean_out || particle_cdf == cov_out || particle_cdf == log_weight))
-    return AESMC_ERR_INVALID_ARGUMENT;
   if (B == 0 || K == 0) return AESMC_OK;
-  if (model->D > kSkMaxDim || model->Dy > kSkMaxDim || model->M > kSkMaxRegimes) return AESMC_ERR_UNSUPPORTED;
-  if (B > 0x7fffffffLL || K > 0x7fffffffLL || B * K > 0x7fffffffLL / (kSkMaxDim * (kSkMaxDim + 1) / 2))
-    return AESMC_ERR_UNSUPPORTED;
+  if (!sk_extents_supported(model->M, model->D, model->Dy) || !sk_fits_32bit(B, K, kSkTriMax)) return AESMC_ERR_UNSUPPORTED;
   SwitchingArgs a;
-  a.cdf = draw ? nullptr : later ? model->cdf : model->cdf0;
+  sk_fill_model(a, model);
+  a.cdf = draw ? nullptr : rows;
   a.particle_cdf = draw ? particle_cdf : nullptr;
   a.pinned_regime = pinned ? pinned_regime : nullptr;
   a.m0 = model->m0, a.s0 = model->s0;
-  a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
   a.regime_in = regime_in, a.mean_in = mean_in, a.cov_in = cov_in;
   a.idx = idx, a.uniforms = uniforms, a.y = y;
   a.observed = masked ? observed : nullptr;
   a.regime_out = regime_out, a.mean_out = mean_out, a.cov_out = cov_out, a.log_weight = log_weight;
   a.flags = flags;
   a.N = B * K, a.K = (uint32_t)K;
-  a.M = (int)model->M, a.D = (int)model->D, a.Dy = (int)model->Dy;
   a.y_is_float = y_dtype == AESMC_F32;
   const int dp = sk_pad(model->D), dyp = sk_pad(model->Dy);
-  const size_t per = (size_t)dp * dp + 2 * dp + (size_t)dyp * dp + 2 * dyp;
-  const size_t lds = ((draw ? 0 : later ? (size_t)a.M * a.M : (size_t)a.M) + (size_t)a.M * per + (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0)) *
-                     sizeof(double);
-  const dim3 grid((unsigned)((a.N + kSkBlock - 1) / kSkBlock));
-  hipStream_t s = (hipStream_t)stream;
-  const bool launched = masked ? sk_launch_d<true>(dp, dyp, grid, lds, s, a) : sk_launch_d<false>(dp, dyp, grid, lds, s, a);
-  return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+  const size_t lds = ((draw ? 0 : later ? (size_t)a.M * a.M : (size_t)a.M) + (size_t)a.M * sk_per_regime(dp, dyp) +
+                      (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0)) * sizeof(double);
+  return sk_for_extents(dp, dyp, [&](auto d, auto dy) {
+    return sk_for_flag(masked, [&](auto m) {
+      return sk_launch(&switching_kalman_kernel<decltype(d)::value, decltype(dy)::value, decltype(m)::value>, sk_grid(a.N),
+                       dim3(kSkBlock), lds, (hipStream_t)stream, a);
+    });
+  });
 }
 
 }  // namespace aesmc

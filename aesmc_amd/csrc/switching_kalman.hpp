@@ -1,5 +1,6 @@
 // What the kernels of the switching linear-Gaussian filters share (switching_kalman.hip: K31, K33 and their masked form K39;
 // switching_lookahead.hip: K32 and K40): the limits, the packed-triangle index, where a lane keeps its predicted covariance, and the model's staging into LDS.
+// What their C entries share on the host (checks, dispatch, launch) is switching_host.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -67,8 +68,5 @@ __device__ __forceinline__ void sk_stage_model(double *mdl, int M, int D, int Dy
     mdl[e] = v;
   }
 }
-
-static inline bool sk_aligned(const void *p, size_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-static inline int sk_pad(int64_t d) { return d <= 2 ? 2 : d <= 4 ? 4 : 8; }
 
 }  // namespace aesmc

@@ -55,7 +55,7 @@
 //
 // Traffic per particle at D = Dy = 4, M = 4: 4 + 32 + 80 (state) + 8 (log-weight) + 32 (CDF row) = 156 bytes; at D = 8:
 // 4 + 64 + 288 + 8 + 32 = 396 bytes (the state's re-reads per regime are served by the caches).
-#include "switching_kalman.hpp"
+#include "switching_host.hpp"
 
 namespace aesmc {
 
@@ -291,76 +291,43 @@ __global__ __launch_bounds__(kSkBlock) void switching_lookahead_kernel(const Loo
   }
 }
 
-template <int DP, int DYP, bool Masked, bool Scores>
-static bool la_launch(dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
-  // more than the default 64 KB: the limit is raised on every launch, as K31's launcher does and for its reasons
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_lookahead_kernel<DP, DYP, Masked, Scores>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return false;
-  hipLaunchKernelGGL((switching_lookahead_kernel<DP, DYP, Masked, Scores>), grid, dim3(kSkBlock), lds, s, a);
-  return true;
-}
-
-template <int DP, bool Masked, bool Scores>
-static bool la_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
-  if (dyp == 2) return la_launch<DP, 2, Masked, Scores>(grid, lds, s, a);
-  if (dyp == 4) return la_launch<DP, 4, Masked, Scores>(grid, lds, s, a);
-  return la_launch<DP, 8, Masked, Scores>(grid, lds, s, a);
-}
-
-template <bool Masked, bool Scores>
-static bool la_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const LookaheadArgs &a) {
-  if (dp == 2) return la_launch_dy<2, Masked, Scores>(dyp, grid, lds, s, a);
-  if (dp == 4) return la_launch_dy<4, Masked, Scores>(dyp, grid, lds, s, a);
-  return la_launch_dy<8, Masked, Scores>(dyp, grid, lds, s, a);
-}
-
 // K32, and K40 (`masked`: observed [B,Dy] given), and K43 (`scores`: `cdf` receives the scores): one set of checks, one launch
 static int la_step(bool scores, bool masked, const uint8_t *observed, int y_dtype, const aesmc_switching_model *model,
                    const double *log_prior, const int32_t *regime_in, const double *mean_in, const double *cov_in,
                    const void *y, double *log_weight, double *cdf, int32_t *flags, int64_t B, int64_t K, void *stream) {
-  if (masked && (observed == nullptr || (const void *)observed == log_weight || (const void *)observed == cdf))
+  if (masked && observed == nullptr) return AESMC_ERR_INVALID_ARGUMENT;
+  if (model == nullptr || log_prior == nullptr || log_weight == nullptr || cdf == nullptr || B < 0 || K < 0)
     return AESMC_ERR_INVALID_ARGUMENT;
-  if (model == nullptr || log_prior == nullptr || y == nullptr || log_weight == nullptr || cdf == nullptr || B < 0 || K < 0)
-    return AESMC_ERR_INVALID_ARGUMENT;
-  if (y_dtype != AESMC_F32 && y_dtype != AESMC_F64) return AESMC_ERR_INVALID_ARGUMENT;
   const bool later = regime_in != nullptr;
   if (later != (mean_in != nullptr) || later != (cov_in != nullptr)) return AESMC_ERR_INVALID_ARGUMENT;
-  if (model->M < 1 || model->D < 1 || model->Dy < 1) return AESMC_ERR_INVALID_ARGUMENT;
-  const double *operands[] = {model->m0, model->s0, model->A, model->b, model->q, model->C, model->d, model->r};
-  for (const double *p : operands)
-    if (p == nullptr || !sk_aligned(p, 8)) return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_observation(y, y_dtype) || !sk_extents_positive(model->M, model->D, model->Dy) || !sk_model_operands(model, true))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (!sk_aligned(log_prior, 8) || !sk_aligned(regime_in, 4) || !sk_aligned(mean_in, 8) || !sk_aligned(cov_in, 8) ||
-      !sk_aligned(y, y_dtype == AESMC_F32 ? 4 : 8) || !sk_aligned(log_weight, 8) || !sk_aligned(cdf, 8) ||
-      !sk_aligned(flags, 4))
+      !sk_aligned(log_weight, 8) || !sk_aligned(cdf, 8) || !sk_aligned(flags, 4))
     return AESMC_ERR_INVALID_ARGUMENT;
-  if (log_weight == cdf || (later && (log_weight == mean_in || log_weight == cov_in || cdf == mean_in || cdf == cov_in)))
-    return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_outputs_distinct({log_weight, cdf}, {mean_in, cov_in, observed})) return AESMC_ERR_INVALID_ARGUMENT;
   if (B == 0 || K == 0) return AESMC_OK;
-  if (model->D > kSkMaxDim || model->Dy > kSkMaxDim || model->M > kSkMaxRegimes) return AESMC_ERR_UNSUPPORTED;
-  if (B > 0x7fffffffLL || K > 0x7fffffffLL || B * K > 0x7fffffffLL / (kSkMaxDim * (kSkMaxDim + 1) / 2))
-    return AESMC_ERR_UNSUPPORTED;
+  if (!sk_extents_supported(model->M, model->D, model->Dy) || !sk_fits_32bit(B, K, kSkTriMax)) return AESMC_ERR_UNSUPPORTED;
   LookaheadArgs a;
+  sk_fill_model(a, model);
   a.log_prior = log_prior;
   a.m0 = model->m0, a.s0 = model->s0;
-  a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
   a.regime_in = regime_in, a.mean_in = mean_in, a.cov_in = cov_in, a.y = y;
   a.observed = masked ? observed : nullptr;
   a.log_weight = log_weight, a.cdf = cdf, a.flags = flags;
   a.N = B * K, a.K = (uint32_t)K;
-  a.M = (int)model->M, a.D = (int)model->D, a.Dy = (int)model->Dy;
   a.y_is_float = y_dtype == AESMC_F32;
   const int dp = sk_pad(model->D), dyp = sk_pad(model->Dy);
   const size_t lds = ((later ? (size_t)a.M * a.M : (size_t)a.M) + (size_t)a.M * sk_per_regime(dp, dyp) +
                       (sk_cov_in_lds(dp) ? dp * (dp + 1) / 2 * kSkBlock : 0) + (size_t)a.M * kSkBlock) * sizeof(double);
-  const dim3 grid((unsigned)((a.N + kSkBlock - 1) / kSkBlock));
-  hipStream_t s = (hipStream_t)stream;
-  const bool launched = scores ? (masked ? la_launch_d<true, true>(dp, dyp, grid, lds, s, a)
-                                        : la_launch_d<false, true>(dp, dyp, grid, lds, s, a))
-                               : (masked ? la_launch_d<true, false>(dp, dyp, grid, lds, s, a)
-                                         : la_launch_d<false, false>(dp, dyp, grid, lds, s, a));
-  return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+  return sk_for_extents(dp, dyp, [&](auto d, auto dy) {
+    return sk_for_flag(masked, [&](auto m) {
+      return sk_for_flag(scores, [&](auto sc) {
+        return sk_launch(&switching_lookahead_kernel<decltype(d)::value, decltype(dy)::value, decltype(m)::value, decltype(sc)::value>,
+                         sk_grid(a.N), dim3(kSkBlock), lds, (hipStream_t)stream, a);
+      });
+    });
+  });
 }
 
 }  // namespace aesmc

@@ -34,7 +34,7 @@
 //   <256>       54      0        0             7
 //   <1024>      93      0        0             5       (16 wavefronts of a workgroup: 4 per SIMD)
 #include "ancestor_index.hpp"
-#include "switching_kalman.hpp"
+#include "switching_host.hpp"
 
 namespace aesmc {
 
@@ -309,13 +309,10 @@ extern "C" int aesmc_switching_optimal_resample(const double *log_w, const doubl
       !sk_aligned(out_regime, 4) || !sk_aligned(out_log_weight, 8) || !sk_aligned(out_lse, 8) || !sk_aligned(out_count, 4) ||
       !sk_aligned(flags, 4))
     return AESMC_ERR_INVALID_ARGUMENT;
-  const void *operands[] = {log_w, scores, u, out_parent, out_regime, out_log_weight, out_lse, out_count, flags};
-  for (int first = 3; first < 8; ++first)      // an output that is an input, another output or the flags
-    for (int other = 0; other < 9; ++other)
-      if (other != first && operands[other] == operands[first]) return AESMC_ERR_INVALID_ARGUMENT;
+  if (!sk_outputs_distinct({out_parent, out_regime, out_log_weight, out_lse, out_count}, {log_w, scores, u, flags}))
+    return AESMC_ERR_INVALID_ARGUMENT;      // an output that is an input, another output or the flags
   if (B == 0 || K_in == 0 || K_out == 0) return AESMC_OK;
-  if (M > kSkMaxRegimes || K_in > kOrMaxCandidates || K_in * M > kOrMaxCandidates || B > 0x7fffffffLL ||
-      K_out > 0x7fffffffLL || B * K_out > 0x7fffffffLL)
+  if (M > kSkMaxRegimes || K_in > kOrMaxCandidates || K_in * M > kOrMaxCandidates || !sk_fits_32bit(B, K_out, 1))
     return AESMC_ERR_UNSUPPORTED;
   OptimalResampleArgs a;
   a.log_w = log_w, a.scores = scores, a.u = u;

@@ -49,7 +49,7 @@
 // not fit, so they keep P in LDS in K31's [element][lane] layout (SkCov: 72 KB per workgroup beside the model's 20 KB at
 // most) — the layout the siblings already use, chosen over a second kernel for the cross-covariance because phase 2 needs
 // the same P again and is the lighter phase.  No instantiation uses scratch.
-#include "switching_kalman.hpp"
+#include "switching_host.hpp"
 
 namespace aesmc {
 
@@ -249,49 +249,20 @@ __global__ __launch_bounds__(kSkBlock) void switching_smooth_kernel(const Smooth
   }
 }
 
-template <int DP, int DYP, bool Masked>
-static bool ss_launch(dim3 grid, size_t lds, hipStream_t s, const SmoothArgs &a) {
-  // the 8-wide instantiations (72 KB of covariances beside the model) need the limit raised, as K31's
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&switching_smooth_kernel<DP, DYP, Masked>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return false;
-  hipLaunchKernelGGL((switching_smooth_kernel<DP, DYP, Masked>), grid, dim3(kSkBlock), lds, s, a);
-  return true;
-}
-
-template <int DP, bool Masked>
-static bool ss_launch_dy(int dyp, dim3 grid, size_t lds, hipStream_t s, const SmoothArgs &a) {
-  if (dyp == 2) return ss_launch<DP, 2, Masked>(grid, lds, s, a);
-  if (dyp == 4) return ss_launch<DP, 4, Masked>(grid, lds, s, a);
-  return ss_launch<DP, 8, Masked>(grid, lds, s, a);
-}
-
-template <bool Masked>
-static bool ss_launch_d(int dp, int dyp, dim3 grid, size_t lds, hipStream_t s, const SmoothArgs &a) {
-  if (dp == 2) return ss_launch_dy<2, Masked>(dyp, grid, lds, s, a);
-  if (dp == 4) return ss_launch_dy<4, Masked>(dyp, grid, lds, s, a);
-  return ss_launch_dy<8, Masked>(dyp, grid, lds, s, a);
-}
-
 // K36, and K42 (`masked`: observed_next [B,Dy] given, which only the cross-covariance reads): one set of checks, one launch
 static int ss_combine(bool masked, const uint8_t *observed_next, const aesmc_switching_model *model,
                       const int32_t *regime_next, const double *mean, const double *cov, const double *factor,
                       const double *lambda, const double *omega_next, const double *cov_next, double *mean_out,
                       double *cov_out, double *cross_out, int32_t *flags, int64_t B, int64_t N, int64_t D, void *stream) {
-  if (masked && (observed_next == nullptr || cross_out == nullptr || (const void *)observed_next == mean_out ||
-                 (const void *)observed_next == cov_out || (const void *)observed_next == cross_out))
-    return AESMC_ERR_INVALID_ARGUMENT;
+  if (masked && (observed_next == nullptr || cross_out == nullptr)) return AESMC_ERR_INVALID_ARGUMENT;
   if (mean == nullptr || cov == nullptr || factor == nullptr || lambda == nullptr || mean_out == nullptr ||
       cov_out == nullptr || B < 0 || N < 0 || D < 1)
     return AESMC_ERR_INVALID_ARGUMENT;
   const bool cross = cross_out != nullptr;
   if (cross) {
     if (model == nullptr || regime_next == nullptr || cov_next == nullptr) return AESMC_ERR_INVALID_ARGUMENT;
-    if (model->M < 1 || model->Dy < 1 || model->D != D) return AESMC_ERR_INVALID_ARGUMENT;
-    const double *operands[] = {model->A, model->b, model->q, model->C, model->d, model->r};
-    for (const double *p : operands)
-      if (p == nullptr || !sk_aligned(p, 8)) return AESMC_ERR_INVALID_ARGUMENT;
+    if (model->D != D || !sk_extents_positive(model->M, D, model->Dy) || !sk_model_operands(model, false))
+      return AESMC_ERR_INVALID_ARGUMENT;
   } else if (model != nullptr || regime_next != nullptr || omega_next != nullptr || cov_next != nullptr) {
     return AESMC_ERR_INVALID_ARGUMENT;      // (what only the cross-covariance reads, given without asking for it)
   }
@@ -299,38 +270,31 @@ static int ss_combine(bool masked, const uint8_t *observed_next, const aesmc_swi
       !sk_aligned(lambda, 8) || !sk_aligned(omega_next, 8) || !sk_aligned(cov_next, 8) || !sk_aligned(mean_out, 8) ||
       !sk_aligned(cov_out, 8) || !sk_aligned(cross_out, 8) || !sk_aligned(flags, 4))
     return AESMC_ERR_INVALID_ARGUMENT;
-  const void *outputs[] = {mean_out, cov_out, cross_out};
-  const void *inputs[] = {regime_next, mean, cov, factor, lambda, omega_next, cov_next};
-  for (int i = 0; i < (cross ? 3 : 2); ++i) {
-    for (const void *in : inputs)
-      if (outputs[i] == in) return AESMC_ERR_INVALID_ARGUMENT;
-    for (int o = 0; o < i; ++o)
-      if (outputs[i] == outputs[o]) return AESMC_ERR_INVALID_ARGUMENT;
-  }
+  if (!sk_outputs_distinct({mean_out, cov_out, cross_out},
+                           {regime_next, mean, cov, factor, lambda, omega_next, cov_next, observed_next}))
+    return AESMC_ERR_INVALID_ARGUMENT;
   if (B == 0 || N == 0) return AESMC_OK;
-  if (D > kSkMaxDim || (cross && (model->Dy > kSkMaxDim || model->M > kSkMaxRegimes))) return AESMC_ERR_UNSUPPORTED;
-  if (B > 0x7fffffffLL || N > 0x7fffffffLL || B * N > 0x7fffffffLL / (kSkMaxDim * kSkMaxDim)) return AESMC_ERR_UNSUPPORTED;
+  if (!sk_extents_supported(cross ? model->M : 0, D, cross ? model->Dy : 0) || !sk_fits_32bit(B, N, kSkMaxDim * kSkMaxDim))
+    return AESMC_ERR_UNSUPPORTED;
   SmoothArgs a;
   a.A = a.b = a.q = a.C = a.d = a.r = nullptr;
-  a.M = 0, a.Dy = 0;
-  if (cross) {
-    a.A = model->A, a.b = model->b, a.q = model->q, a.C = model->C, a.d = model->d, a.r = model->r;
-    a.M = (int)model->M, a.Dy = (int)model->Dy;
-  }
+  a.M = 0, a.Dy = 0, a.D = (int)D;
+  if (cross) sk_fill_model(a, model);
   a.regime_next = regime_next;
   a.mean = mean, a.cov = cov, a.factor = factor, a.lambda = lambda, a.omega_next = omega_next, a.cov_next = cov_next;
   a.observed_next = masked ? observed_next : nullptr;
   a.mean_out = mean_out, a.cov_out = cov_out, a.cross_out = cross_out;
   a.flags = flags;
   a.total = B * N, a.N = (uint32_t)N;
-  a.D = (int)D;
   const int dp = sk_pad(D), dyp = cross ? sk_pad(model->Dy) : 2;      // (without cross_out nothing of extent Dy exists)
   const size_t lds = ((size_t)a.M * sk_per_regime(dp, dyp) + (sk_cov_in_lds(dp) ? (size_t)(dp * (dp + 1) / 2) * kSkBlock : 0)) *
                      sizeof(double);
-  const dim3 grid((unsigned)((a.total + kSkBlock - 1) / kSkBlock));
-  hipStream_t s = (hipStream_t)stream;
-  const bool launched = masked ? ss_launch_d<true>(dp, dyp, grid, lds, s, a) : ss_launch_d<false>(dp, dyp, grid, lds, s, a);
-  return launched && hipGetLastError() == hipSuccess ? AESMC_OK : AESMC_ERR_LAUNCH;
+  return sk_for_extents(dp, dyp, [&](auto d, auto dy) {
+    return sk_for_flag(masked, [&](auto m) {
+      return sk_launch(&switching_smooth_kernel<decltype(d)::value, decltype(dy)::value, decltype(m)::value>, sk_grid(a.total),
+                       dim3(kSkBlock), lds, (hipStream_t)stream, a);
+    });
+  });
 }
 
 }  // namespace aesmc
