@@ -245,6 +245,8 @@ class HipKernels:
         self._wide_dim = None       # (aesmc_affine_wide_dim(), _min_dim(), _max_dim()): see `_wide_limits`
         self._pairs = None          # (key, tensor): the interleaved weight pairs of the maps the fused launch met last
         self.evaluation = 0         # bumped by `begin_evaluation`: what a cached weight-pair block belongs to
+        self._statistics_workspaces = {}      # device index -> the two blocks of K45 / K46's partials
+        self._statistics_sizes = {}           # (D, Dy, masked) -> a block's bytes; "limits": switching_limits(), read once
         self.WEIGHT_PAIRS = settings.knob("AESMC_K16_PAIRS", "1") != "0"      # measurement knob
         self.SCALED_PAIRS = settings.knob("AESMC_K16_SCALED", "1") != "0"     # measurement knob: the constants behind the pairs
 
@@ -2794,6 +2796,103 @@ class HipKernels:
                      (model, regime_next, mean, cov, factor, lam, omega_next, cov_next, observed_next, out_mean, out_cov, out_cross,
                       block))
         return out_mean, out_cov, out_cross
+
+    # ---- K45, K46 ------------------------------------------------------------------------------
+    def switching_statistics_columns(self, latent_dim, observation_dim, masked):
+        """F of the [16, F] statistics array (aesmc_switching_statistics_columns; 0 outside the limits)."""
+        return int(self._lib.aesmc_switching_statistics_columns(int(latent_dim), int(observation_dim), int(bool(masked))))
+
+    def _switching_statistics_workspace(self, device, D, Dy, masked, block):
+        """The per-workgroup partials of K45 / K46, kept per device: two blocks (0: the t = 0 step's, 1: the later steps')
+        of aesmc_switching_statistics_workspace_bytes each, which depend on D, Dy and the entry only."""
+        if block not in (0, 1):
+            raise ValueError("aesmc_amd: a statistics block is 0 (the t = 0 step) or 1 (the later steps), got {!r}".format(block))
+        ws_bytes = self._statistics_sizes.get((D, Dy, bool(masked)))
+        if ws_bytes is None:
+            ws_bytes = self._statistics_sizes[(D, Dy, bool(masked))] = \
+                int(self._lib.aesmc_switching_statistics_workspace_bytes(D, Dy, int(masked)))
+        key = torch.device(device).index
+        held = self._statistics_workspaces.get(key)
+        if held is None or held.numel() < 2 * ws_bytes:
+            held = self._statistics_workspaces[key] = torch.empty(2 * ws_bytes, dtype=torch.uint8, device=device)
+        return held, held.data_ptr() + block * ws_bytes
+
+    def switching_statistics_step(self, observation, regime, mean, cov, num_regimes, previous=None, observed=None, block=0,
+                                  accumulate=False):
+        """One timestep's contribution to the expected sufficient statistics of a switching model
+        (aesmc_switching_moment_statistics, K45; with `observed`, aesmc_switching_masked_moment_statistics, K46), added to
+        (`accumulate`) or stored over the per-workgroup partials of `block` (0 or 1: two sets this provider keeps per device).
+        observation float32 / float64 [B,Dy]; regime int32 [B,N]; mean float64 [B,N,D], cov float64 [B,N,D(D+1)/2]: the
+        smoothed moments of time t; previous: None (the t = 0 form) or (regime_prev int32 [B,N], mean_prev, cov_prev, cross
+        float64 [B,N,D,D] with cross[i,l] = Cov(z_{t,i}, z_{t-1,l})); observed: None or torch.bool [B,Dy].  Returns nothing:
+        `switching_statistics_finish` reads the block.  A regime or previous regime outside [0, num_regimes) contributes
+        nothing and raises FLAG_INDEX_OUT_OF_RANGE.  The launches that share a block share every extent and the entry."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        _require_hip(mean, "mean")
+        device = observation.device
+        if mean.dim() != 3 or mean.dtype != torch.float64 or mean.device != device:
+            raise ValueError("aesmc_amd: mean must be [batch_size, num_trajectories, D] float64 on {}, got {} {}".format(
+                device, tuple(mean.shape), mean.dtype))
+        B, N, D = mean.shape
+        TD, M = D * (D + 1) // 2, int(num_regimes)
+        if observation.dim() != 2 or observation.size(0) != B:
+            raise ValueError("aesmc_amd: observation must be [{}, Dy], got {}".format(B, tuple(observation.shape)))
+        Dy = observation.size(1)
+        wanted = [(regime, (B, N), torch.int32, "regime"), (cov, (B, N, TD), torch.float64, "cov")]
+        if previous is not None:
+            if len(previous) != 4:
+                raise ValueError("aesmc_amd: previous must be None or (regime_prev, mean_prev, cov_prev, cross)")
+            wanted += [(previous[0], (B, N), torch.int32, "regime_prev"), (previous[1], (B, N, D), torch.float64, "mean_prev"),
+                       (previous[2], (B, N, TD), torch.float64, "cov_prev"), (previous[3], (B, N, D, D), torch.float64, "cross")]
+        for tensor, shape, dtype, what in wanted:      # (on `device`, which is a HIP device: no _require_hip of its own)
+            if not torch.is_tensor(tensor) or tensor.shape != shape or tensor.dtype != dtype or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} {} on {}".format(what, shape, dtype, device))
+        limits = self._statistics_sizes.get("limits")
+        if limits is None:
+            limits = self._statistics_sizes["limits"] = self.switching_limits()
+        max_d, max_dy, max_m = limits
+        if not (1 <= D <= max_d and 1 <= Dy <= max_dy and 1 <= M <= max_m and B * N <= 0x7fffffff // (max_d * max_d)):
+            raise ValueError("aesmc_amd: switching_statistics_step does not take these operands (see switching_covers)")
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
+        held, workspace = self._switching_statistics_workspace(device, D, Dy, observed is not None, block)
+        if B * N == 0:
+            return
+        observation, regime, mean, cov = observation.contiguous(), regime.contiguous(), mean.contiguous(), cov.contiguous()
+        earlier = (None,) * 4 if previous is None else tuple(tensor.contiguous() for tensor in previous)
+        head = (tag, _ptr(observation)) + (() if observed is None else (_ptr(observed),))
+        args = head + (_ptr(regime),) + tuple(_ptr(tensor) for tensor in earlier) + \
+            (_ptr(mean), _ptr(cov), workspace, int(bool(accumulate)), _ptr(self.flags(device)), B, N, M, D, Dy,
+             self._stream(mean))
+        per_trajectory = 4 + 8 * (D + TD) + (0 if previous is None else 4 + 8 * (D + TD + D * D))
+        self._launch(device, self._lib.aesmc_switching_moment_statistics if observed is None else
+                     self._lib.aesmc_switching_masked_moment_statistics, args,
+                     lambda: B * N * per_trajectory + B * Dy * (observation.element_size() + (0 if observed is None else 1)),
+                     (observation, observed, regime, mean, cov, earlier, held),
+                     name="switching_statistics_step" if observed is None else "switching_masked_statistics_step")
+
+    def switching_statistics_finish(self, like, batch_size, num_trajectories, latent_dim, observation_dim, masked, block=0):
+        """The [16, F] float64 statistics of `block` (aesmc_switching_statistics_finish): the workgroups' partials of the
+        `switching_statistics_step` launches into it, added in one fixed order.  like: a tensor on the device (its device
+        and stream are used); the extents and `masked` are those of the launches.  A new tensor; zeros without a launch
+        where batch_size * num_trajectories is 0."""
+        _require_hip(like, "like")
+        device = like.device
+        B, N, D, Dy = int(batch_size), int(num_trajectories), int(latent_dim), int(observation_dim)
+        max_d, max_dy, _ = self.switching_limits()
+        if not (B >= 0 and N >= 0 and 1 <= D <= max_d and 1 <= Dy <= max_dy and B * N <= 0x7fffffff // (max_d * max_d)):
+            raise ValueError("aesmc_amd: switching_statistics_finish does not take these extents (see switching_covers)")
+        columns = self.switching_statistics_columns(D, Dy, masked)
+        if B * N == 0:
+            return torch.zeros((16, columns), dtype=torch.float64, device=device)
+        held, workspace = self._switching_statistics_workspace(device, D, Dy, masked, block)
+        out = torch.empty((16, columns), dtype=torch.float64, device=device)
+        self._launch(device, self._lib.aesmc_switching_statistics_finish,
+                     (workspace, _ptr(out), int(bool(masked)), B, N, D, Dy, self._stream(like)),
+                     lambda: 8 * 16 * columns * (1 + min((B * N + 255) // 256, 512)), (held, out),
+                     name="switching_statistics_finish")
+        return out
 
     # ---- K37, K38 ------------------------------------------------------------------------------
     def switching_conditional_max_particles(self, latent_dim):

@@ -149,6 +149,11 @@ SIGNATURES = {
     "aesmc_switching_masked_lookahead_scores": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 9 + [_i64, _i64, _vp]),
     "aesmc_switching_optimal_resample_max_candidates": (_i64, []),
     "aesmc_switching_optimal_resample": (_i32, [_vp] * 9 + [_i64] * 4 + [_vp]),
+    "aesmc_switching_statistics_columns": (_i64, [_i64, _i64, _i32]),
+    "aesmc_switching_statistics_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "aesmc_switching_moment_statistics": (_i32, [_i32] + [_vp] * 9 + [_i32, _vp] + [_i64] * 5 + [_vp]),
+    "aesmc_switching_masked_moment_statistics": (_i32, [_i32] + [_vp] * 10 + [_i32, _vp] + [_i64] * 5 + [_vp]),
+    "aesmc_switching_statistics_finish": (_i32, [_vp, _vp, _i32] + [_i64] * 4 + [_vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

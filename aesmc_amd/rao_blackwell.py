@@ -66,6 +66,16 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                (examples/slds_gibbs.py: Gibbs over Pi with Dirichlet rows)
     switching_forecast         the predictive distributions of the steps after the last observation, from either filter's
                                last stored system: steps with nothing observed
+    switching_expected_statistics   EM's E-step reduction: the expected complete-data sufficient statistics per regime, summed
+                               over time, batch rows and trajectories, from the per-trajectory smoothed moments.  One launch
+                               per timestep (K45 `aesmc_switching_moment_statistics`, under a mask K46
+                               `aesmc_switching_masked_moment_statistics`): one lane per trajectory forms its terms, the
+                               float64 matrix cores sum them against the indicator of the regime — no atomics, one fixed
+                               order, the same inputs give the same bits
+    switching_m_step           the closed-form M-step for every parameter (pi0, Pi, m0, s0, A, b, q, C, d, r) on those sums:
+                               a new model (examples/slds_em_full.py)
+    switching_score            the score by Fisher's identity on the same sums, for a gradient optimiser: no adjoint of the
+                               filters' Cholesky chains is needed
 
 Missing observations: every function above takes `observed=`, per timestep None or a torch.bool [batch_size, Dy] mask.  For a
 batch row a step is then the step of the model with that row's unmeasured components deleted from C, d, r and y — exact, as
@@ -84,6 +94,7 @@ import math
 import torch
 
 from . import _kernels
+from . import _lib
 from . import _ops
 from . import _syncfree
 from . import inference
@@ -108,7 +119,9 @@ class SwitchingLinearGaussian(torch.nn.Module):
     which of them were measured at a step is the filters' `observed=`, not the model's.  Everything is held as a float64 buffer
     (`.to(device)` moves the model).  The filters are not differentiable and the buffers are no parameters: a model is
     learned by EM — `switching_smooth_states` gives the E-step's smoothed moments E[z_t z_t^T | y], E[z_{t+1} z_t^T | y] and
-    regime trajectories, the M-step builds a new model from them (examples/slds_em.py)."""
+    regime trajectories, `switching_expected_statistics` reduces them to the expected sufficient statistics per regime and
+    `switching_m_step` builds a new model from those in closed form (examples/slds_em_full.py; examples/slds_em.py does the
+    M-step for Pi, A and b by hand) — or by a gradient optimiser on `switching_score`, the score by Fisher's identity."""
 
     def __init__(self, pi0, Pi, m0, s0, A, b, q, C, d, r):
         super().__init__()
@@ -1163,3 +1176,309 @@ def kalman_log_likelihood(observations, model, observed=None):
     D = model.latent_dim
     return (out["log_marginal_likelihood"], torch.stack([m[:, 0] for m in out["means"]]),
             torch.stack([unpack_covariance(c[:, 0], D) for c in out["covariances"]]))
+
+
+# ---- EM: the expected sufficient statistics (K45 / K46), the M-step and the score -----------------------------------------------
+
+PARAMETERS = ("pi0", "Pi", "m0", "s0", "A", "b", "q", "C", "d", "r")
+_STATISTICS = ("transition_counts", "next_next", "next_prev", "prev_prev", "obs_obs", "obs_state", "state_state",
+               "initial_counts", "initial_state")
+
+
+def _statistics_layout(D, Dy, masked):
+    """name -> slice of the columns of K45 / K46's [16, F] array (include/aesmc_hip.h; `testing.switching_statistics.layout`)."""
+    X = D + 1
+    TX = X * (X + 1) // 2
+    sizes = [("gram", TX), ("obs_obs", Dy), ("obs_state", Dy * X)] + ([("grams", Dy * TX)] if masked else []) + \
+        [("counts", 16), ("next_next", D * (D + 1) // 2), ("next_prev", D * X), ("prev_prev", TX)]
+    out, at = {}, 0
+    for name, size in sizes:
+        out[name] = slice(at, at + size)
+        at += size
+    return out
+
+
+def _name_statistics(initial, later, M, D, Dy, masked):
+    """The named statistics from the two [16, F] blocks (the t = 0 step's, the later steps')."""
+    X = D + 1
+    where = _statistics_layout(D, Dy, masked)
+    total = initial + later
+    gram = unpack_covariance(total[:M, where["gram"]], X)
+    if masked:
+        grams = unpack_covariance(total[:M, where["grams"]].reshape(M, Dy, X * (X + 1) // 2), X)
+    else:
+        grams = gram.unsqueeze(1).expand(M, Dy, X, X)
+    first = unpack_covariance(initial[:M, where["gram"]], X)
+    return {"transition_counts": later[:M, where["counts"]][:, :M].t().contiguous(),
+            "next_next": unpack_covariance(later[:M, where["next_next"]], D),
+            "next_prev": later[:M, where["next_prev"]].reshape(M, D, X),
+            "prev_prev": unpack_covariance(later[:M, where["prev_prev"]], X),
+            "obs_obs": total[:M, where["obs_obs"]],
+            "obs_state": total[:M, where["obs_state"]].reshape(M, Dy, X),
+            "state_state": grams,
+            "initial_counts": first[:, D, D].clone(),
+            "initial_state": first.sum(dim=0)}
+
+
+def _check_smoothed(name, smoothed, observations, device):
+    """(B, N, D, Dy) of the per-trajectory moments of a state smoother, or ValueError."""
+    keys = ("regimes", "means", "covariances", "cross_covariances")
+    if not isinstance(smoothed, dict) or any(key not in smoothed for key in keys):
+        raise ValueError("{}: smoothed must be a dict with {} (switching_state_smooth(..., return_trajectories=True))".format(
+            name, ", ".join(keys)))
+    num_timesteps = len(observations)
+    for key in keys:
+        wanted = num_timesteps - 1 if key == "cross_covariances" else num_timesteps
+        if len(smoothed[key]) != wanted:
+            raise ValueError("{}: smoothed[{!r}] must hold {} tensors, got {}".format(name, key, wanted, len(smoothed[key])))
+    first = smoothed["means"][0]
+    if not torch.is_tensor(first) or first.dim() != 3:
+        raise ValueError("{}: smoothed['means'][0] must be a [batch_size, num_trajectories, D] float64 tensor".format(name))
+    B, N, D = first.shape
+    for y in observations:
+        if not torch.is_tensor(y) or y.dim() != 2 or tuple(y.shape) != tuple(observations[0].shape) or \
+                y.dtype not in (torch.float32, torch.float64) or y.device != device:
+            raise ValueError("{}: observations must be [batch_size, Dy] float32 or float64 tensors on one device".format(name))
+    if observations[0].size(0) != B:
+        raise ValueError("{}: the observations have {} batch rows, the moments {}".format(name, observations[0].size(0), B))
+    shapes = {"regimes": ((B, N), torch.int32), "means": ((B, N, D), torch.float64),
+              "covariances": ((B, N, D * (D + 1) // 2), torch.float64), "cross_covariances": ((B, N, D, D), torch.float64)}
+    for key in keys:
+        shape, dtype = shapes[key]
+        for time, tensor in enumerate(smoothed[key]):
+            if not torch.is_tensor(tensor) or tuple(tensor.shape) != shape or tensor.dtype != dtype or tensor.device != device:
+                raise ValueError("{}: smoothed[{!r}][{}] must be {} {} on {}".format(name, key, time, shape, dtype, device))
+    return B, N, D, observations[0].size(1)
+
+
+def switching_expected_statistics(smoothed, observations, model_or_num_regimes, observed=None):
+    """The E-step's reduction: the expected complete-data sufficient statistics of a `SwitchingLinearGaussian`, summed over
+    time, batch rows and trajectories, from the per-trajectory smoothed moments — what `switching_m_step` and
+    `switching_score` take.  With x = (z, 1), X = D + 1, j = s_t, i = s_{t-1} and o_c whether component c of y_t[b] was observed:
+
+        transition_counts [M, M]  (as [i, j])   1[s_{t-1} = i]             next_next [M, D, D]   E[z_t z_t^T]
+        next_prev [M, D, X]   E[z_t x_{t-1}^T]                             prev_prev [M, X, X]   E[x_{t-1} x_{t-1}^T]      (t >= 1)
+        obs_obs [M, Dy]   o_c y_c^2        obs_state [M, Dy, X]   o_c y_c E[x_t]^T        state_state [M, Dy, X, X]   o_c E[x_t x_t^T]
+        initial_counts [M]   1[s_0 = j]    initial_state [X, X]   E[x_0 x_0^T]
+
+    smoothed: a dict with regimes (T int32 [batch_size, N]), means (T float64 [batch_size, N, D]), covariances (T packed) and
+    cross_covariances (T-1 [batch_size, N, D, D]): what `switching_smooth_states(..., return_trajectories=True)` or
+    `switching_state_smooth(..., return_trajectories=True)` (with the regimes it was given) returns.  observations, observed:
+    as `switching_filter`'s.  model_or_num_regimes: the model, or M.
+
+    One launch per timestep — K45 (`aesmc_switching_moment_statistics`), with a mask K46: one lane per trajectory forms its
+    terms in float64 and the float64 matrix cores sum them per regime against the indicator of s_t, without atomics and in a
+    fixed order (the same inputs give the same bits) — the t = 0 step into a block of its own, then one finishing launch per
+    block.  Returns the float64 tensors above on the device (without a mask state_state is a stride-0 expansion of one gram)
+    with batch_size, num_trajectories and num_timesteps.
+
+    ValueError for operands that disagree and — read once, at the end, with the flags — a regime outside [0, M);
+    FloatingPointError if a statistic is NaN (a NaN moment, or a NaN observation at an observed position);
+    NotImplementedError naming the covered class past the limits.  No host synchronisation inside the loop; an exception on
+    the way discards whatever was flagged.  N == 0 gives zeros without a launch; T == 1 launches only the t = 0 form."""
+    name = "switching_expected_statistics"
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            num_timesteps = len(observations)
+            if num_timesteps == 0:
+                raise ValueError("{}: observations must hold at least one timestep".format(name))
+            M = model_or_num_regimes.num_regimes if isinstance(model_or_num_regimes, SwitchingLinearGaussian) else \
+                int(model_or_num_regimes)
+            if M < 1:
+                raise ValueError("{}: the number of regimes must be at least 1, got {}".format(name, M))
+            device = observations[0].device if torch.is_tensor(observations[0]) else None
+            B, N, D, Dy = _check_smoothed(name, smoothed, observations, device)
+            if isinstance(model_or_num_regimes, SwitchingLinearGaussian) and \
+                    (model_or_num_regimes.latent_dim, model_or_num_regimes.observation_dim) != (D, Dy):
+                raise ValueError("{}: the model has D = {} and Dy = {}, the moments and observations {} and {}".format(
+                    name, model_or_num_regimes.latent_dim, model_or_num_regimes.observation_dim, D, Dy))
+            mask = _observed_steps(name, observed, observations)
+            if M > MAX_REGIMES:
+                _refuse("a model of {} regimes (M > {})".format(M, MAX_REGIMES))
+            if not 1 <= D <= MAX_LATENT_DIM:
+                _refuse("a latent of {} values (D > {})".format(D, MAX_LATENT_DIM))
+            if not 1 <= Dy <= MAX_OBSERVATION_DIM:
+                _refuse("an observation of {} values (Dy > {})".format(Dy, MAX_OBSERVATION_DIM))
+            if B * N > 0x7fffffff // (MAX_LATENT_DIM * MAX_LATENT_DIM):
+                _refuse("{} trajectories in {} batch rows (batch_size * num_trajectories * D^2 beyond 32-bit element arithmetic)"
+                        .format(N, B))
+            if provider.name == "hip":
+                _kernels._require_hip(observations[0], "observations")      # (no CPU fallback)
+            masks = [mask(time) for time in range(num_timesteps)]
+            masked = any(masks)
+            sizes = dict(batch_size=B, num_trajectories=N, num_timesteps=num_timesteps)
+            if N == 0 or B == 0:
+                zeros = torch.zeros((16, provider.switching_statistics_columns(D, Dy, masked)), dtype=torch.float64, device=device)
+                return dict(_name_statistics(zeros, zeros, M, D, Dy, masked), **sizes)
+            everything = torch.ones((B, Dy), dtype=torch.bool, device=device) if masked else None
+            regimes, means, covs, crosses = (smoothed[key] for key in ("regimes", "means", "covariances", "cross_covariances"))
+            for time in range(num_timesteps):
+                seen = {"observed": masks[time].get("observed", everything)} if masked else {}
+                previous = None if time == 0 else (regimes[time - 1], means[time - 1], covs[time - 1], crosses[time - 1])
+                provider.switching_statistics_step(observations[time], regimes[time], means[time], covs[time], M,
+                                                   previous=previous, block=min(time, 1), accumulate=time > 1, **seen)
+            initial = provider.switching_statistics_finish(observations[0], B, N, D, Dy, masked, block=0)
+            later = provider.switching_statistics_finish(observations[0], B, N, D, Dy, masked, block=1) \
+                if num_timesteps > 1 else torch.zeros_like(initial)
+            out = _name_statistics(initial, later, M, D, Dy, masked)
+            flags = provider.read_flags(device)
+            if flags & _lib.FLAG_INDEX_OUT_OF_RANGE:      # (the kernels raise it themselves: no pass over the regimes here)
+                raise ValueError("{}: regimes holds a value outside [0, M)".format(name))
+            inference._raise_for_flags(flags)
+            if bool((torch.isnan(initial).any() | torch.isnan(later).any())):
+                raise FloatingPointError("a statistic contains nan element(s)")
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return dict(out, **sizes)
+
+
+def _check_statistics(name, statistics, model):
+    if not isinstance(model, SwitchingLinearGaussian):
+        raise ValueError("{}: the model must be a SwitchingLinearGaussian, got {}".format(name, type(model).__name__))
+    keys = _STATISTICS + ("batch_size", "num_trajectories", "num_timesteps")
+    if not isinstance(statistics, dict) or any(key not in statistics for key in keys):
+        raise ValueError("{}: statistics must be what switching_expected_statistics returns".format(name))
+    M, D, Dy = model.num_regimes, model.latent_dim, model.observation_dim
+    if tuple(statistics["next_prev"].shape) != (M, D, D + 1) or tuple(statistics["obs_state"].shape) != (M, Dy, D + 1):
+        raise ValueError("{}: the statistics are those of M = {}, D = {}, Dy = {}; the model has {}, {}, {}".format(
+            name, statistics["next_prev"].size(0), statistics["next_prev"].size(1), statistics["obs_state"].size(1), M, D, Dy))
+    device = statistics["next_prev"].device
+    if model.pi0.device != device:
+        raise ValueError("{}: the model is on {}, the statistics on {}".format(name, model.pi0.device, device))
+    for key, shape in (("A", (D, D)), ("b", (D,)), ("q", (D,)), ("C", (Dy, D)), ("d", (Dy,)), ("r", (Dy,))):
+        value = getattr(model, key)
+        if value.dim() != len(shape) + 1 or value.size(0) not in (1, M) or tuple(value.shape[1:]) != shape:
+            raise ValueError("{}: {} must be {} (or a leading 1: shared across regimes), got {}".format(
+                name, key, (M,) + shape, tuple(value.shape)))
+    if tuple(model.m0.shape) != (D,) or model.s0.numel() not in (1, D):
+        raise ValueError("{}: m0 must be [{}] and s0 hold one value or {}".format(name, D, D))
+    return M, D, Dy
+
+
+def _quadratic(square, cross, gram, weights):
+    """square - 2 w . cross + w gram w^T for every row w of weights [M, R, X] (gram [M, R, X, X])."""
+    return square - 2.0 * (weights * cross).sum(dim=-1) + torch.einsum("mri,mril,mrl->mr", weights, gram, weights)
+
+
+def _affine_block(statistics, D, emission):
+    """(square [M,R], cross [M,R,X], gram [M,R,X,X], count [M,R]) of the transition's or the emission's regression."""
+    if emission:
+        grams = statistics["state_state"]
+        return statistics["obs_obs"], statistics["obs_state"], grams, grams[:, :, D, D]
+    lagged = statistics["prev_prev"]
+    M, X = lagged.size(0), D + 1
+    return (torch.diagonal(statistics["next_next"], dim1=-2, dim2=-1), statistics["next_prev"],
+            lagged.unsqueeze(1).expand(M, D, X, X), lagged[:, D, D].unsqueeze(1).expand(M, D))
+
+
+def _affine_update(previous, names, block, learn):
+    """The new (weights, offsets, scales) of one affine-Gaussian block, `testing.switching_statistics._affine_update`."""
+    prev_w, prev_b, prev_scale = (getattr(previous, key) for key in names)
+    learn_w, learn_b, learn_scale = (key in learn for key in names)
+    square, cross, gram, count = block
+    M, R, X = cross.shape
+    if prev_w.size(0) != prev_b.size(0):
+        raise NotImplementedError("switching_m_step: {} and {} must both be shared across regimes or neither".format(*names[:2]))
+    pool = lambda value, shared: value.sum(dim=0, keepdim=True) if shared else value
+    w_shared, s_shared = prev_w.size(0) == 1 and M > 1, prev_scale.size(0) == 1 and M > 1
+    weights = torch.cat([prev_w, prev_b.unsqueeze(-1)], dim=-1)
+    if learn_w or learn_b:
+        device = cross.device
+        free = torch.tensor([i for i in range(X) if (learn_w if i < X - 1 else learn_b)], dtype=torch.int64, device=device)
+        fixed = torch.tensor([i for i in range(X) if not (learn_w if i < X - 1 else learn_b)], dtype=torch.int64, device=device)
+        pooled_gram, pooled_cross = pool(gram, w_shared), pool(cross, w_shared)
+        held = weights.index_select(-1, fixed).unsqueeze(-2)                                          # [., R, 1, fixed]
+        target = pooled_cross.index_select(-1, free).unsqueeze(-2) - \
+            held @ pooled_gram.index_select(-2, fixed).index_select(-1, free)
+        solved = target @ torch.linalg.pinv(pooled_gram.index_select(-2, free).index_select(-1, free), hermitian=True)
+        estimate = weights.clone()
+        estimate[..., free] = solved.squeeze(-2)
+        weights = torch.where((pool(count, w_shared) > 0).unsqueeze(-1), estimate, weights)
+    scale = prev_scale
+    if learn_scale:
+        quad = pool(_quadratic(square, cross, gram, weights.expand(M, R, X)), s_shared)
+        total = pool(count, s_shared)
+        estimate = torch.sqrt(quad.clamp_min(0.0) / total.clamp_min(1e-300))
+        scale = torch.where(total > 0, estimate, prev_scale)
+    return weights[..., :-1].contiguous(), weights[..., -1].contiguous(), scale
+
+
+def switching_m_step(statistics, previous, learn=PARAMETERS):
+    """The closed-form M-step of EM for a `SwitchingLinearGaussian`: a NEW model that maximises the expected complete-data
+    log-likelihood `statistics` (`switching_expected_statistics`'s) stands for, in the parameters named by `learn` (a tuple
+    of names out of PARAMETERS; default: all ten); every other buffer is copied from `previous`.  Plain torch float64 on the
+    statistics' device — the matrices are tiny.
+
+        pi0 = initial_counts / (batch_size N)            Pi[i, :] = transition_counts[i, :] / its sum
+        m0, s0 from initial_state                        [A_j b_j] = next_prev[j] pinv(prev_prev[j])     (hermitian pinv)
+        q_ji^2 = (next_next_ii - 2 w . next_prev_i + w prev_prev w^T) / n_j,  w = [A_j b_j]_i, clamped at 0
+        row c of [C_j d_j], r_jc: the same regression on obs_state, state_state[:, c] and obs_obs
+
+    A row of Pi with no departures, a regime never visited and a component never observed under a regime keep `previous`'s
+    values.  With only one of A, b (C, d) learned the other is held in the regression.  A parameter `previous` holds with a
+    leading extent of 1 (shared across regimes) is estimated from the statistics summed over the regimes and keeps that
+    shape; A with b (C with d) must then both be shared or neither (NotImplementedError).  The contract is
+    `aesmc_amd.testing.switching_statistics.m_step`."""
+    name = "switching_m_step"
+    M, D, Dy = _check_statistics(name, statistics, previous)
+    learn = tuple(learn)
+    unknown = sorted(set(learn) - set(PARAMETERS))
+    if unknown:
+        raise ValueError("{}: learn names {}; the parameters are {}".format(name, unknown, PARAMETERS))
+    with torch.no_grad():
+        new = {key: getattr(previous, key).clone() for key in PARAMETERS}
+        if "pi0" in learn:
+            new["pi0"] = statistics["initial_counts"] / float(statistics["batch_size"] * statistics["num_trajectories"])
+        if "Pi" in learn:
+            departures = statistics["transition_counts"].sum(dim=1, keepdim=True)
+            new["Pi"] = torch.where(departures > 0, statistics["transition_counts"] / departures.clamp_min(1.0), new["Pi"])
+        first = statistics["initial_state"]
+        total, seen = first[D, D].clamp_min(1e-300), first[D, D] > 0
+        if "m0" in learn:
+            new["m0"] = torch.where(seen, first[:D, D] / total, new["m0"])
+        if "s0" in learn:
+            m0 = new["m0"]
+            quad = (torch.diagonal(first)[:D] - 2.0 * m0 * first[:D, D] + m0 * m0 * first[D, D]).clamp_min(0.0)
+            estimate = torch.sqrt(quad / total) if previous.s0.numel() == D else torch.sqrt(quad.sum() / (D * total)).reshape(1)
+            new["s0"] = torch.where(seen, estimate.reshape(previous.s0.shape), new["s0"])
+        new["A"], new["b"], new["q"] = _affine_update(previous, ("A", "b", "q"), _affine_block(statistics, D, False), learn)
+        new["C"], new["d"], new["r"] = _affine_update(previous, ("C", "d", "r"), _affine_block(statistics, D, True), learn)
+        return SwitchingLinearGaussian(**new)
+
+
+def switching_score(statistics, model):
+    """The score by Fisher's identity: a dict with the gradient, with respect to each buffer of `model` in the buffer's own
+    shape, of the Monte Carlo estimate of sum_b log p(y^b) — (1/N) sum_{b,n} E[grad log p(y^b, z, s^{b,n}) | y^b, s^{b,n}], from
+    `switching_expected_statistics`'s sums alone: no adjoint of the filters' Cholesky chains is needed.  For [A b]:
+    diag(q_j^-2) (next_prev[j] - [A_j b_j] prev_prev[j]) / N; for q: (-n_j / q + quadratic / q^3) / N; likewise C, d, r, m0 and
+    s0; for Pi and pi0 the plain partial derivatives count / probability (0 where the count is 0; the simplex is the caller's
+    business).  A shared parameter (leading extent 1) receives the sum over the regimes.  The trajectories must be (as
+    `switching_smooth_states` draws them) samples of p(s | y) under `model` for the estimate to be the score at `model`.  The
+    contract is `aesmc_amd.testing.switching_statistics.score`."""
+    M, D, Dy = _check_statistics("switching_score", statistics, model)
+    N = float(statistics["num_trajectories"])
+    out = {}
+    with torch.no_grad():
+        for names, emission in ((("A", "b", "q"), False), (("C", "d", "r"), True)):
+            w, b, scale = (getattr(model, key) for key in names)
+            square, cross, gram, count = _affine_block(statistics, D, emission)
+            R, X = cross.size(1), D + 1
+            weights = torch.cat([w.expand((M,) + tuple(w.shape[1:])), b.expand((M,) + tuple(b.shape[1:])).unsqueeze(-1)], dim=-1)
+            sigma = scale.expand(M, R)
+            residual = (cross - torch.einsum("mrl,mrlk->mrk", weights, gram)) / (sigma * sigma).unsqueeze(-1) / N
+            grad_scale = (-count / sigma + _quadratic(square, cross, gram, weights) / sigma ** 3) / N
+            fold = lambda grad, like: grad.sum(dim=0, keepdim=True) if like.size(0) == 1 and M > 1 else grad
+            out[names[0]], out[names[1]], out[names[2]] = \
+                fold(residual[..., :-1], w), fold(residual[..., -1], b), fold(grad_scale, scale)
+        first = statistics["initial_state"]
+        m0, s0 = model.m0, model.s0.reshape(-1).expand(D)
+        out["m0"] = (first[:D, D] - m0 * first[D, D]) / (s0 * s0) / N
+        quad = torch.diagonal(first)[:D] - 2.0 * m0 * first[:D, D] + m0 * m0 * first[D, D]
+        grad_s0 = (-first[D, D] / s0 + quad / s0 ** 3) / N
+        out["s0"] = (grad_s0 if model.s0.numel() == D else grad_s0.sum().reshape(1)).reshape(model.s0.shape)
+        counts, starts = statistics["transition_counts"], statistics["initial_counts"]
+        out["Pi"] = torch.where(counts > 0, counts / model.Pi, torch.zeros_like(counts)) / N
+        out["pi0"] = torch.where(starts > 0, starts / model.pi0, torch.zeros_like(starts)) / N
+    return out

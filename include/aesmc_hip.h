@@ -93,7 +93,11 @@ extern "C" {
  *                and forecasts as steps with nothing observed);
  *                aesmc_switching_lookahead_scores, aesmc_switching_masked_lookahead_scores,
  *                aesmc_switching_optimal_resample with aesmc_switching_optimal_resample_max_candidates (K43, K44: the
- *                look-ahead's scores and optimal resampling over all successor regimes — the discrete particle filter).
+ *                look-ahead's scores and optimal resampling over all successor regimes — the discrete particle filter);
+ *                aesmc_switching_moment_statistics, aesmc_switching_masked_moment_statistics,
+ *                aesmc_switching_statistics_finish with aesmc_switching_statistics_columns and
+ *                aesmc_switching_statistics_workspace_bytes (K45, K46: the expected sufficient statistics of that model from
+ *                per-trajectory smoothed moments — the E-step's reduction, for EM and the score).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -945,6 +949,53 @@ int64_t aesmc_switching_optimal_resample_max_candidates(void);
 int aesmc_switching_optimal_resample(const double *log_w, const double *scores, const double *u, int64_t *out_parent,
                                      int32_t *out_regime, double *out_log_weight, double *out_lse, int32_t *out_count,
                                      int32_t *flags, int64_t B, int64_t K_in, int64_t M, int64_t K_out, void *stream);
+
+/* K45, K46 — the expected complete-data sufficient statistics of a switching linear-Gaussian model from per-trajectory smoothed
+ * moments (K36's): the reduction between an E-step and a closed-form M-step, or the score by Fisher's identity.  One launch
+ * adds ONE timestep's contribution, summed over all trajectories (b, n), to per-workgroup partials in `workspace`;
+ * the finishing entry adds the partials in a fixed order and writes out float64 [16, F], row j = the regime s_t
+ * (rows M .. 15 are zeros).  With x = (z, 1), X = D + 1, o_c = whether component c of y[b] was observed (K45: always 1),
+ * the columns are, in this order (F is what the columns getter returns; packed: element (i, l), i >= l, at i (i + 1) / 2 + l,
+ * the constant's index D):
+ *   emission block, every t      gram       E[x_t x_t^T] packed                          X (X + 1) / 2
+ *                                obs_obs    o_c y_c^2                                     Dy
+ *                                obs_state  o_c y_c E[x_t]^T, [c][l]                      Dy X
+ *                                grams      K46 only: o_c E[x_t x_t^T] packed, c = 0 ..    Dy X (X + 1) / 2
+ *   transition block, t >= 1     counts     1[s_{t-1} = i], i = 0 .. 15                   16
+ *                                next_next  E[z_t z_t^T] packed                           D (D + 1) / 2
+ *                                next_prev  E[z_t x_{t-1}^T] = [cross + m m'^T, m], [i][l]  D X
+ *                                prev_prev  E[x_{t-1} x_{t-1}^T] packed                   X (X + 1) / 2
+ *   y float32 / float64 [B,Dy] (y_dtype: AESMC_F32 / AESMC_F64); regime int32 [B,N]; mean [B,N,D], cov [B,N,D(D+1)/2] packed:
+ *   the smoothed moments of z_t; regime_prev int32 [B,N], mean_prev, cov_prev (of z_{t-1}) and cross float64 [B,N,D,D]
+ *   (cross[i,l] = Cov(z_{t,i}, z_{t-1,l}): rows at the later time) — all four NULL for the t = 0 form, which forms no
+ *   transition block, otherwise all four given; observed uint8 [B,Dy] (K46), nonzero = observed.
+ *   accumulate 0: the partials are overwritten (the workspace is not read; the t = 0 form writes zeros for the transition
+ *   block), 1: added to.  A run of launches that share a workspace must share B, N, D, Dy and the entry.
+ * An entry such as P_il + m_i m_l is one float64 fused multiply-add, y_c^2 and y_c m_l one rounded product; the sums are
+ * formed on the float64 matrix cores against the indicator of the regime, without floating-point atomics and in one fixed
+ * order: the same operands give the same bits.  What must not count is selected to zero before it is summed: the trajectory
+ * of a regime or previous regime outside [0, M) contributes nothing and raises AESMC_FLAG_INDEX_OUT_OF_RANGE; in K46, y at
+ * an unobserved position is never used and may be NaN or Inf.  A NaN in a moment poisons the sums it enters.
+ * The workspace holds the statistics workspace getter's bytes (it depends on D, Dy and the entry only, not on B N).
+ * NULL (but flags and the four operands of time t-1) or misaligned pointers, a y_dtype that is neither tag, negative sizes,
+ * M, D or Dy below 1, accumulate other than 0 or 1, the four operands of time t-1 given in part, and a workspace that is one of
+ * the inputs return AESMC_ERR_INVALID_ARGUMENT; B == 0 or N == 0 is a no-op; D or Dy above 8, M above 16 or B N beyond 32-bit
+ * element arithmetic (B N 64 elements) return AESMC_ERR_UNSUPPORTED.  Every check runs before any launch.
+ * The finishing entry: `masked` 0 after K45, 1 after K46; B, N, D, Dy those of the launches; out float64 [16, F], not the
+ * workspace.  B == 0 or N == 0 is a no-op there too (nothing is written). */
+int64_t aesmc_switching_statistics_columns(int64_t D, int64_t Dy, int masked);         /* F; 0 outside the limits */
+int64_t aesmc_switching_statistics_workspace_bytes(int64_t D, int64_t Dy, int masked); /* 0 outside the limits */
+int aesmc_switching_moment_statistics(int y_dtype, const void *y, const int32_t *regime, const int32_t *regime_prev,
+                                      const double *mean_prev, const double *cov_prev, const double *cross,
+                                      const double *mean, const double *cov, void *workspace, int accumulate,
+                                      int32_t *flags, int64_t B, int64_t N, int64_t M, int64_t D, int64_t Dy, void *stream);
+int aesmc_switching_masked_moment_statistics(int y_dtype, const void *y, const uint8_t *observed, const int32_t *regime,
+                                             const int32_t *regime_prev, const double *mean_prev, const double *cov_prev,
+                                             const double *cross, const double *mean, const double *cov, void *workspace,
+                                             int accumulate, int32_t *flags, int64_t B, int64_t N, int64_t M, int64_t D,
+                                             int64_t Dy, void *stream);
+int aesmc_switching_statistics_finish(const void *workspace, double *out, int masked, int64_t B, int64_t N, int64_t D,
+                                      int64_t Dy, void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
