@@ -2797,6 +2797,57 @@ class HipKernels:
                       block))
         return out_mean, out_cov, out_cross
 
+    # ---- K47 -----------------------------------------------------------------------------------
+    def switching_state_draw(self, model, regimes, means, covs, noise, following=None):
+        """A draw of the continuous state along regime paths, the whole backward pass in one launch
+        (aesmc_switching_state_draw, K47).  model as `switching_kalman_step`'s; regimes int32 [T,B,N]; means float64
+        [T,B,N,D] and covs float64 [T,B,N,D(D+1)/2]: the conditional filter's, stacked; noise float64 [T,B,N,D]: standard
+        normals; following: None, or (regime_next int32 [B,N], z_next float64 [B,N,D]) — the regime and the drawn state of
+        time T, for a pass in chunks (with T = 1 exactly one conditioning step).  Returns states float64 [T,B,N,D], a new
+        tensor.  A regime outside [0, M) where it is read (regimes[t], t >= 1, and regime_next) gives NaN at every earlier
+        time of that trajectory and FLAG_INDEX_OUT_OF_RANGE."""
+        _require_hip(means, "means")
+        device = means.device
+        if means.dim() != 4 or means.dtype != torch.float64 or means.size(0) < 1:
+            raise ValueError("aesmc_amd: means must be [T, batch_size, num_trajectories, D] float64 with T >= 1, got {} {}"
+                             .format(tuple(means.shape), means.dtype))
+        T, B, N, D = means.shape
+        TD = D * (D + 1) // 2
+        for tensor, shape, what in ((covs, (T, B, N, TD), "covs"), (noise, (T, B, N, D), "noise")):
+            _require_hip(tensor, what)
+            if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
+        _require_hip(regimes, "regimes")
+        if tuple(regimes.shape) != (T, B, N) or regimes.dtype != torch.int32 or regimes.device != device:
+            raise ValueError("aesmc_amd: regimes must be [{}, {}, {}] int32 on {}".format(T, B, N, device))
+        block, M, model_d, Dy = self._switching_block(model, device)
+        if model_d != D:
+            raise ValueError("aesmc_amd: the model's latent has {} values, the means {}".format(model_d, D))
+        regime_next = z_next = None
+        if following is not None:
+            regime_next, z_next = following
+            _require_hip(regime_next, "regime_next")
+            _require_hip(z_next, "z_next")
+            if tuple(regime_next.shape) != (B, N) or regime_next.dtype != torch.int32 or regime_next.device != device:
+                raise ValueError("aesmc_amd: regime_next must be [{}, {}] int32 on {}".format(B, N, device))
+            if tuple(z_next.shape) != (B, N, D) or z_next.dtype != torch.float64 or z_next.device != device:
+                raise ValueError("aesmc_amd: z_next must be {} float64 on {}".format((B, N, D), device))
+            regime_next, z_next = regime_next.contiguous(), z_next.contiguous()
+        max_d, max_dy, max_m = self.switching_limits()
+        if not (1 <= D <= max_d and 1 <= M <= max_m and 1 <= Dy <= max_dy and B * N <= 0x7fffffff // (max_d * max_d)):
+            raise ValueError("aesmc_amd: switching_state_draw does not take these operands (see switching_covers)")
+        regimes, means, covs, noise = regimes.contiguous(), means.contiguous(), covs.contiguous(), noise.contiguous()
+        states = torch.empty((T, B, N, D), dtype=torch.float64, device=device)
+        if B * N == 0:
+            return states
+        self._launch(device, self._lib.aesmc_switching_state_draw,
+                     (ctypes.byref(block), _ptr(regimes), _ptr(means), _ptr(covs), _ptr(noise), _ptr(regime_next),
+                      _ptr(z_next), _ptr(states), _ptr(self.flags(device)), T, B, N, self._stream(means)),
+                     lambda: B * N * (T * (8 * (3 * D + TD)) + 4 * (T - 1) + (4 + 8 * D if following is not None else 0)) +
+                     self._switching_model_bytes(M, D, Dy, rows=False) - 8 * M * (Dy * D + 2 * Dy),
+                     (model, regimes, means, covs, noise, regime_next, z_next, states, block))
+        return states
+
     # ---- K45, K46 ------------------------------------------------------------------------------
     def switching_statistics_columns(self, latent_dim, observation_dim, masked):
         """F of the [16, F] statistics array (aesmc_switching_statistics_columns; 0 outside the limits)."""

@@ -55,6 +55,14 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                factors I + F^T P F (pivots at least 1) and never a predicted covariance — q = 0 components
                                and P = 0 are fine where an RTS step would divide by a singular matrix
     switching_smooth_states    a filter, the backward simulation, then that (examples/slds_em.py: Monte Carlo EM on it)
+    switching_sample_states    a DRAW of the continuous state along given regime paths, z_{0:T-1} ~ p(z | s_{0:T-1}, y): forward
+                               filtering, backward sampling (Fruehwirth-Schnatter 1994; Carter & Kohn 1994).
+                               `conditional_kalman_filter` forward, then the whole backward pass in ONE launch (K47,
+                               `aesmc_switching_state_draw`: one lane per trajectory walks t = T-1 .. 0 with z_{t+1} in
+                               registers — a measurement update of N(m_t, P_t) by z_{t+1}, then an affine draw; both
+                               factorisations drop pivots as K34's, so q = 0 components and P = 0 are fine).  With
+                               `switching_particle_gibbs` and conjugate parameter draws: Gibbs over regimes, states and all
+                               ten parameters (examples/slds_gibbs_full.py)
     conditional_switching_filter   one sweep of particle Gibbs with ancestor sampling on the regimes (Andrieu, Doucet &
                                Holenstein 2010; Whiteley, Andrieu & Doucet 2010; Lindsten et al. 2016): a conditional
                                Rao-Blackwellised filter whose last slot carries a reference regime path — a Markov kernel on
@@ -121,7 +129,9 @@ class SwitchingLinearGaussian(torch.nn.Module):
     learned by EM — `switching_smooth_states` gives the E-step's smoothed moments E[z_t z_t^T | y], E[z_{t+1} z_t^T | y] and
     regime trajectories, `switching_expected_statistics` reduces them to the expected sufficient statistics per regime and
     `switching_m_step` builds a new model from those in closed form (examples/slds_em_full.py; examples/slds_em.py does the
-    M-step for Pi, A and b by hand) — or by a gradient optimiser on `switching_score`, the score by Fisher's identity."""
+    M-step for Pi, A and b by hand) — or by a gradient optimiser on `switching_score`, the score by Fisher's identity — or
+    sampled: `switching_particle_gibbs` draws the regimes, `switching_sample_states` the states along them, and the
+    parameters given both are conjugate (examples/slds_gibbs_full.py)."""
 
     def __init__(self, pi0, Pi, m0, s0, A, b, q, C, d, r):
         super().__init__()
@@ -888,6 +898,81 @@ def switching_state_smooth(observations, model, regimes, return_cross_moments=Fa
         inference._discard_pending_flags()
         raise
     return out
+
+
+def _state_noise(name, noise, num_timesteps, shape, device):
+    """The T standard-normal tensors of a state draw: fresh from torch's device generator, or the replayed ones, validated."""
+    from . import distributed
+    if noise is None:
+        if distributed.active_shard() is not None:
+            raise NotImplementedError(
+                "aesmc_amd.rao_blackwell: drawing the state noise inside distributed.shard_scope is not implemented: a "
+                "sharded run reproduces the unsharded one through the global block of host uniforms every rank draws, which "
+                "per-trajectory device draws do not have. Pass noise when sharding.")
+        return None
+    try:
+        length = len(noise)
+    except TypeError:
+        length = -1
+    if length != num_timesteps:
+        raise ValueError("{}: noise must be None or hold one tensor per timestep ({}), got {}".format(
+            name, num_timesteps, "{} entries".format(length) if length >= 0 else type(noise).__name__))
+    for time in range(length):
+        eps = noise[time]
+        if not torch.is_tensor(eps) or tuple(eps.shape) != shape or eps.dtype != torch.float64 or eps.device != device:
+            raise ValueError("{}: noise[{}] must be {} float64 on {}".format(name, time, shape, device))
+    return list(noise)
+
+
+def switching_sample_states(observations, model, regimes, noise=None, observed=None):
+    """A draw of the continuous state along given regime paths: z_{0:T-1} ~ p(z | s_{0:T-1}, y) per trajectory, by forward
+    filtering and backward sampling (Fruehwirth-Schnatter 1994; Carter & Kohn 1994) — the simulation smoother.  With
+    `switching_particle_gibbs` for (s | theta, y) and conjugate draws for (theta | s, z, y) it is the middle block of a Gibbs
+    sampler over regimes, states and every parameter (examples/slds_gibbs_full.py); the draws also give posterior samples of
+    any nonlinear functional of the state path (maxima, threshold crossings), which the two moments of
+    `switching_state_smooth` cannot.
+
+    observations, model, observed: as `switching_filter`'s (`observed` reaches the filter only: missing observations are in
+    the filtered moments, the backward pass reads no y).  regimes: T int32 [batch_size, N] on the device, as
+    `conditional_kalman_filter`'s.  noise: None — torch.randn float64 on the device (refused inside
+    distributed.shard_scope) — or a length-T sequence of float64 [batch_size, N, D] standard normals on the device, for replay.
+
+    `conditional_kalman_filter`'s loop runs forward; then one torch.stack per operand and ONE launch of K47
+    (`aesmc_switching_state_draw`) walk every trajectory from T-1 to 0: a Kalman measurement update of N(m_t, P_t) by
+    z_{t+1} through A, b, q of s_{t+1}, then z_t = m' + chol(P') eps_t.  Both factorisations drop a pivot at or below 2^-40
+    of the largest diagonal entry: q = 0 components and P = 0 are fine.  T == 1 is the draw from the filtered law.
+
+    Returns a dict: states (T float64 [batch_size, N, D], views of one tensor), log_likelihood [batch_size, N] (the
+    conditional filter's log p(y | s_{0:T-1})) and noise (the T tensors that were used).
+
+    Validation, refusals and flags as `conditional_kalman_filter`'s: one read at the end, an exception on the way discards
+    whatever was flagged, no host synchronisation before that read.  N == 0 gives empty tensors without a launch.  Runs
+    under torch.no_grad(): NOT differentiable."""
+    name = "switching_sample_states"
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops, num_timesteps, batch_size, num_trajectories, device, mask = _prepare_conditional(
+                name, provider, observations, model, regimes, observed)
+            D = model.latent_dim
+            shape = (batch_size, num_trajectories, D)
+            noise = _state_noise(name, noise, num_timesteps, shape, device)
+            if num_trajectories == 0:
+                empty = lambda *tail: torch.empty((batch_size, 0) + tail, dtype=torch.float64, device=device)
+                return {"states": [empty(D) for _ in range(num_timesteps)], "log_likelihood": empty(),
+                        "noise": [empty(D) for _ in range(num_timesteps)] if noise is None else noise}
+            means, covariances, log_likelihood, outside = _conditional_filter(provider, ops, observations, regimes,
+                                                                              model.num_regimes, mask)
+            stacked_noise = torch.randn((num_timesteps,) + shape, dtype=torch.float64, device=device) if noise is None else \
+                torch.stack(noise)
+            states = provider.switching_state_draw(ops, torch.stack(list(regimes)), torch.stack(means),
+                                                   torch.stack(covariances), stacked_noise)
+            _finish_conditional(name, provider, device, outside, log_likelihood)
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return {"states": list(states.unbind(0)), "log_likelihood": log_likelihood,
+            "noise": list(stacked_noise.unbind(0)) if noise is None else noise}
 
 
 def switching_smooth_states(observations, model, num_particles, num_trajectories=None, resampling=None, lookahead=False,

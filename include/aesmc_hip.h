@@ -97,7 +97,9 @@ extern "C" {
  *                aesmc_switching_moment_statistics, aesmc_switching_masked_moment_statistics,
  *                aesmc_switching_statistics_finish with aesmc_switching_statistics_columns and
  *                aesmc_switching_statistics_workspace_bytes (K45, K46: the expected sufficient statistics of that model from
- *                per-trajectory smoothed moments — the E-step's reduction, for EM and the score).
+ *                per-trajectory smoothed moments — the E-step's reduction, for EM and the score);
+ *                aesmc_switching_state_draw (K47: a draw of the continuous state path given a regime path, the whole
+ *                backward pass of forward filtering, backward sampling in one launch — for Gibbs on all parameters).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -996,6 +998,37 @@ int aesmc_switching_masked_moment_statistics(int y_dtype, const void *y, const u
                                              int64_t Dy, void *stream);
 int aesmc_switching_statistics_finish(const void *workspace, double *out, int masked, int64_t B, int64_t N, int64_t D,
                                       int64_t Dy, void *stream);
+
+/* K47 — the simulation smoother of the continuous state of the same model along GIVEN regime paths (forward filtering,
+ * backward sampling; Fruehwirth-Schnatter 1994, Carter & Kohn 1994): z_{0:T-1} ~ p(z | s_{0:T-1}, y) per trajectory, the WHOLE
+ * backward pass in one launch.  Trajectory (b,n) has at every time t the conditional Kalman filter's mean m_t and packed
+ * covariance P_t (K31 under its regimes — missing observations are already in them: no y and no mask is read) and standard
+ * normals eps_t.  One lane per trajectory walks t = T-1 .. 0 with z_{t+1} in registers.  Step T-1 draws from N(m, P) as it
+ * stands — unless regime_next and z_next hand over the regime and the drawn state of time T (a long series in chunks; with
+ * T = 1 exactly one conditioning step).  A step at t < T-1 (or with them), j = s_{t+1}, q2_i = q_j[i]^2, is a Kalman
+ * measurement update with A_j, b_j, diag(q2) as C, d, R and z_{t+1} as y; chains as K34's (float64, every sum ONE chain of
+ * fused multiply-adds in ascending index order from the value named first):
+ *   V_il = 0 + sum_c A_j[i,c] P_cl;      e_i = (z_{t+1,i} - b_j[i]) - sum_l A_j[i,l] m_l
+ *   S_ik = (i == k ? q2_i : 0) + sum_l A_j[i,l] V_kl,  i >= k;      tau = 2^-40 max_i S_ii
+ *   L = chol(S) column by column: pivot_k = S_kk - sum_{c<k} L_kc^2; KEPT when pivot_k > tau: rk_k = 1 / sqrt(pivot_k),
+ *       L_ik = (S_ik - sum_{c<k} L_ic L_kc) rk_k; otherwise the column is zero and rk_k = 0
+ *   v_i  = (e_i - sum_{c<i} L_ic v_c) rk_i;   U_il = (V_il - sum_{c<i} L_ic U_cl) rk_i      (a dropped pivot: a zero row)
+ *   P'_ps = P_ps - sum_i U_ip U_is,  p >= s;   m'_p = m_p + sum_i U_ip v_i
+ * and then, at every step (at T-1 without z_next: P' = P, m' = m), with tau' = 2^-40 max_i P_ii of the INPUT covariance:
+ *   L' = chol(P') by the same rule under tau' (a dropped column is zero);   z_t,p = m'_p + sum_{k<=p} L'_pk eps_t,k.
+ * Both matrices are only positive semi-definite — q = 0 components and P = 0 are fine; what a downdate leaves of a direction
+ * that z_{t+1} determines is rounding below tau' and is dropped, not taken for variance.
+ *   regimes int32 [T,B,N] (regimes[0] is not read);  mean float64 [T,B,N,D];  cov float64 [T,B,N,D(D+1)/2];
+ *   noise float64 [T,B,N,D];  regime_next int32 [B,N] and z_next float64 [B,N,D]: both or neither;  states float64 [T,B,N,D]
+ * A regime outside [0, M) where it is read (regimes[t], t >= 1, and regime_next) writes NaN to the trajectory's states of
+ * every earlier time (t-1 .. 0; T-1 .. 0 for regime_next) and raises AESMC_FLAG_INDEX_OUT_OF_RANGE.  No atomics but the
+ * flag's: the same inputs give the same bits.  NULL (but regime_next, z_next, flags) or misaligned pointers, only one of
+ * regime_next and z_next, T below 1, negative B or N, M, D or Dy below 1 and states being an input return
+ * AESMC_ERR_INVALID_ARGUMENT; B N == 0 is a no-op; D, Dy or M above the limits of K31 or B N D^2 beyond 32-bit element
+ * arithmetic return AESMC_ERR_UNSUPPORTED.  Every check runs before any launch.  `flags` may be NULL. */
+int aesmc_switching_state_draw(const aesmc_switching_model *model, const int32_t *regimes, const double *mean,
+                               const double *cov, const double *noise, const int32_t *regime_next, const double *z_next,
+                               double *states, int32_t *flags, int64_t T, int64_t B, int64_t N, void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
