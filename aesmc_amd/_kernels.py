@@ -2415,9 +2415,9 @@ class HipKernels:
     def _switching_kalman(self, name, entry, masked_name, model, state, index, uniforms, observation, observed, cdf=None,
                           pinned_regime=None, draw=False, pinned=False):
         """`switching_kalman_step`, `switching_kalman_draw` (`draw`: with `cdf`) and `switching_kalman_conditional_step`
-        (`pinned`: with `pinned_regime`), called as `name`, which messages and the timer's entries carry.  Without `observed`
-        the launch is the caller's own C `entry` (and so its unmasked kernel); with it, the masked entry, which takes both
-        operands as nullable, recorded as `masked_name`."""
+        (`pinned`: with `pinned_regime`; both: `switching_kalman_conditional_draw`), called as `name`, which messages and the
+        timer's entries carry.  Without `observed` the launch is the caller's own C `entry` (and so its unmasked kernel);
+        with it, the masked entry, which takes both operands as nullable, recorded as `masked_name`."""
         _require_hip(observation, "observation")
         tag = _tag(observation, "observation")
         _require_hip(uniforms, "regime uniforms")
@@ -2467,8 +2467,7 @@ class HipKernels:
         tail = (_ptr(out_regime), _ptr(out_mean), _ptr(out_cov), _ptr(log_weight), _ptr(self.flags(device)), B, K,
                 self._stream(observation))
         if observed is None:
-            middle = (_ptr(cdf), _ptr(observation)) if draw else (_ptr(pinned_regime), _ptr(observation)) if pinned else \
-                (_ptr(observation),)
+            middle = ((_ptr(cdf),) if draw else ()) + ((_ptr(pinned_regime),) if pinned else ()) + (_ptr(observation),)
         else:
             entry, name = self._lib.aesmc_switching_kalman_masked_step, masked_name
             middle = (_ptr(cdf), _ptr(pinned_regime), _ptr(observation), _ptr(observed))
@@ -3017,6 +3016,104 @@ class HipKernels:
                                       "switching_kalman_masked_conditional_step", model, state, index, uniforms, observation,
                                       observed, pinned_regime=pinned_regime, pinned=True)
 
+    # ---- K48, K49 ------------------------------------------------------------------------------
+    def switching_lookahead_conditional_max_particles(self, num_regimes, latent_dim, observation_dim):
+        """The largest K the fused `switching_lookahead_conditional_ancestor_index` (K48) takes for a model of M regimes, a
+        latent of D and an observation of Dy values, as the library exports it (0 outside the family's limits); never above
+        `switching_conditional_max_particles(latent_dim)`."""
+        return int(self._lib.aesmc_switching_lookahead_conditional_max_particles(int(num_regimes), int(latent_dim),
+                                                                                 int(observation_dim)))
+
+    def switching_lookahead_conditional_covers(self, observation, num_regimes, latent_dim, observation_dim, num_particles):
+        """Whether ONE launch (K48) takes the resampling side of a look-ahead conditional step like this: what
+        `switching_conditional_covers` asks, and at most `switching_lookahead_conditional_max_particles` particles.  Past it
+        and inside `switching_conditional_covers` the step is composed from K32 and K37."""
+        return self.switching_conditional_covers(observation, num_regimes, latent_dim, observation_dim, num_particles) and \
+            num_particles <= self.switching_lookahead_conditional_max_particles(num_regimes, latent_dim, observation_dim)
+
+    def switching_lookahead_conditional_ancestor_index(self, model, log_Pi, state, observation, u, regime_next, factor, lam,
+                                                       observed=None, fused=None):
+        """The resampling side of one step t >= 1 of a LOOK-AHEAD conditional sweep: `switching_lookahead` on the stored,
+        equally weighted system `state` with log_Pi as its log-prior, and `switching_conditional_ancestor_index` on the
+        first-stage log-weights it gives — with the pinned slot's score carrying a log-weight of 0.0, NOT the first-stage
+        weight.  model, state, observation, observed as `switching_lookahead`'s; u float64 [B,K]; regime_next int32 [B];
+        factor, lam as `switching_conditional_ancestor_index`'s, or both None (no ancestor sampling).
+        fused: None — one launch (aesmc_switching_lookahead_conditional_ancestor_index, K48; with `observed` its masked
+        entry) where `switching_lookahead_conditional_covers` holds, else the composition of existing launches: K32 (K40),
+        K37 on the first-stage weights without factor / lam for columns 0 .. K-2, K37 on zeros with them for column K-1, one
+        torch.where; True / False force either (True past the cap raises).
+        Returns (idx int64 [B,K], log_weight [B,K], cdf [B,K,M]) float64, new tensors.  Bad rows as the two functions'."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        device = observation.device
+        block, M, D, Dy = self._switching_block(model, device)
+        _require_hip(u, "uniforms")
+        if u.dim() != 2 or u.dtype != torch.float64 or u.device != device:
+            raise ValueError("aesmc_amd: uniforms must be [batch_size, num_particles] float64 on {}".format(device))
+        B, K = u.shape
+        if tuple(observation.shape) != (B, Dy):
+            raise ValueError("aesmc_amd: observation must be [{}, {}], got {}".format(B, Dy, tuple(observation.shape)))
+        if state is None:
+            raise ValueError("aesmc_amd: switching_lookahead_conditional_ancestor_index covers later steps only: step 0 has "
+                             "no resampling (switching_lookahead on the prior)")
+        if not self.switching_conditional_covers(observation, M, D, Dy, K):
+            raise ValueError("aesmc_amd: switching_lookahead_conditional_ancestor_index does not take these operands (see "
+                             "switching_conditional_covers)")
+        covered = K <= self.switching_lookahead_conditional_max_particles(M, D, Dy)
+        if fused and not covered:
+            raise ValueError("aesmc_amd: fused=True with {} particles, above switching_lookahead_conditional_max_particles({}, "
+                             "{}, {})".format(K, M, D, Dy))
+        if not (covered if fused is None else fused):
+            return compose_switching_lookahead_conditional(self, model, log_Pi, state, observation, u, regime_next, factor,
+                                                           lam, observed)
+        _require_hip(log_Pi, "log_Pi")
+        if tuple(log_Pi.shape) != (M, M) or log_Pi.dtype != torch.float64 or log_Pi.device != device:
+            raise ValueError("aesmc_amd: log_Pi must be {} float64 on {}".format((M, M), device))
+        TD = D * (D + 1) // 2
+        regime, mean, cov = self._switching_state(state, B, K, D, device)
+        if (factor is None) != (lam is None):
+            raise ValueError("aesmc_amd: factor and lam come together")
+        if factor is not None:
+            for tensor, shape, what in ((factor, (B, TD), "factor"), (lam, (B, D), "lam")):
+                _require_hip(tensor, what)
+                if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                    raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
+            factor, lam = factor.contiguous(), lam.contiguous()
+        _require_hip(regime_next, "regime_next")
+        if tuple(regime_next.shape) != (B,) or regime_next.dtype != torch.int32 or regime_next.device != device:
+            raise ValueError("aesmc_amd: regime_next must be [{}] int32 on {}".format(B, device))
+        log_Pi, u, regime_next, observation = log_Pi.contiguous(), u.contiguous(), regime_next.contiguous(), \
+            observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
+        idx = torch.empty((B, K), dtype=torch.int64, device=device)
+        log_weight = torch.empty((B, K), dtype=torch.float64, device=device)
+        cdf = torch.empty((B, K, M), dtype=torch.float64, device=device)
+        if idx.numel() == 0:
+            return idx, log_weight, cdf
+        head = (tag, ctypes.byref(block), _ptr(log_Pi), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation))
+        tail = (_ptr(u), _ptr(regime_next), _ptr(factor), _ptr(lam), _ptr(idx), _ptr(log_weight), _ptr(cdf),
+                _ptr(self.flags(device)), B, K, self._stream(observation))
+        masked = observed is not None
+        self._launch(device, self._lib.aesmc_switching_masked_lookahead_conditional_ancestor_index if masked else
+                     self._lib.aesmc_switching_lookahead_conditional_ancestor_index,
+                     head + (_ptr(observed),) + tail if masked else head + tail,
+                     lambda: B * K * (4 + 8 * D + 8 * TD + 8 + 8 * M + 16) + B * Dy * (observation.element_size() + int(masked)) +
+                     self._switching_model_bytes(M, D, Dy) + (B * (4 + 8 * (TD + D)) if factor is not None else 0),
+                     (model, log_Pi, regime, mean, cov, observation, observed, u, regime_next, factor, lam, idx, log_weight, cdf,
+                      block), name="switching_masked_lookahead_conditional_ancestor_index" if masked else
+                     "switching_lookahead_conditional_ancestor_index")
+        return idx, log_weight, cdf
+
+    def switching_kalman_conditional_draw(self, model, state, index, uniforms, cdf, pinned_regime, observation, observed=None):
+        """`switching_kalman_draw` with the regime of slot K-1 pinned (aesmc_switching_kalman_conditional_draw, K49): the
+        step of a look-ahead conditional sweep.  cdf float64 [B,K,M] as `switching_kalman_draw`'s, pinned_regime int32 [B] as
+        `switching_kalman_conditional_step`'s.  Returns (regime, mean, cov, log_likelihood [B,K] float64), new tensors;
+        observed: as `switching_kalman_step`'s (K39 with both operands)."""
+        return self._switching_kalman("switching_kalman_conditional_draw", self._lib.aesmc_switching_kalman_conditional_draw,
+                                      "switching_kalman_masked_conditional_draw", model, state, index, uniforms, observation,
+                                      observed, cdf=cdf, pinned_regime=pinned_regime, draw=True, pinned=True)
+
     # ---- K22 -----------------------------------------------------------------------------------
     PAIRWISE_LSE_MAX_DIM = 256
 
@@ -3278,6 +3375,24 @@ def get():
             if _provider is None:
                 _provider = HipKernels()
     return _provider
+
+
+def compose_switching_lookahead_conditional(provider, model, log_Pi, state, observation, u, regime_next, factor, lam,
+                                            observed=None):
+    """`switching_lookahead_conditional_ancestor_index` from a provider's existing launches: K32 (with `observed` K40), K37 on
+    the first-stage weights without factor / lam for columns 0 .. K-2, and with ancestor sampling K37 on zeros with them for
+    column K-1, joined by one torch.where.  Returns (idx, log_weight, cdf)."""
+    mask = {} if observed is None else {"observed": observed}
+    log_weight, cdf = provider.switching_lookahead(model, log_Pi, state, observation, **mask)
+    idx = provider.switching_conditional_ancestor_index(log_weight, u, log_Pi, regime_next, None, None, state)
+    if factor is not None or lam is not None:
+        pinned = provider.switching_conditional_ancestor_index(torch.zeros_like(log_weight), u, log_Pi, regime_next, factor,
+                                                               lam, state)
+        # (column K-1 of the first is K-1, or K where the row's first-stage weights are bad: those rows stay)
+        K = idx.size(1)
+        last = torch.arange(K, device=idx.device) == K - 1
+        idx = torch.where(last & (idx == K - 1), pinned, idx)
+    return idx, log_weight, cdf
 
 
 def _swap_provider_for_tests(provider):

@@ -154,6 +154,12 @@ SIGNATURES = {
     "aesmc_switching_moment_statistics": (_i32, [_i32] + [_vp] * 9 + [_i32, _vp] + [_i64] * 5 + [_vp]),
     "aesmc_switching_masked_moment_statistics": (_i32, [_i32] + [_vp] * 10 + [_i32, _vp] + [_i64] * 5 + [_vp]),
     "aesmc_switching_statistics_finish": (_i32, [_vp, _vp, _i32] + [_i64] * 4 + [_vp]),
+    "aesmc_switching_lookahead_conditional_max_particles": (_i64, [_i64, _i64, _i64]),
+    "aesmc_switching_lookahead_conditional_ancestor_index": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 13 +
+                                                             [_i64, _i64, _vp]),
+    "aesmc_switching_masked_lookahead_conditional_ancestor_index": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 14 +
+                                                                    [_i64, _i64, _vp]),
+    "aesmc_switching_kalman_conditional_draw": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 13 + [_i64, _i64, _vp]),
     "aesmc_switching_state_draw": (_i32, [ctypes.POINTER(SwitchingModel)] + [_vp] * 8 + [_i64] * 3 + [_vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),

@@ -9,6 +9,10 @@
 // pointer, `pinned_regime` [B], whose entry slot K-1 of the row takes as its regime in place of the draw — the reference
 // path's.  NULL for K31 and K33; everything after the regime is chosen is the same code for every slot.
 //
+// And aesmc_switching_kalman_conditional_draw (K49), the step of a LOOK-AHEAD conditional sweep: both pointers at once — the
+// free slots draw from their ancestors' rows as K33's, slot K-1 takes the pinned regime as K38's.  The kernel always took
+// the two together (the masked entry passes both); K49 is the unmasked entry that does.
+//
 // And aesmc_switching_kalman_masked_step (K39), any of the three under a mask of the observation's components: the kernel's
 // second instantiation per extent (`Masked`), in which a component that batch row b did not observe is deleted from the step
 // by three selections placed after the chains of the unmasked text — see the kernel's comment.  The unmasked instantiations
@@ -412,7 +416,18 @@ extern "C" int aesmc_switching_kalman_conditional_step(int y_dtype, const aesmc_
                         regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
 }
 
-// K39: particle_cdf non-NULL is K33's form, pinned_regime non-NULL K38's, both NULL K31's
+// K49: K33's and K38's operands at once — every slot draws from its ancestor's row, slot K-1 takes the pinned regime
+extern "C" int aesmc_switching_kalman_conditional_draw(int y_dtype, const aesmc_switching_model *model,
+                                                       const int32_t *regime_in, const double *mean_in, const double *cov_in,
+                                                       const int64_t *idx, const double *uniforms, const double *particle_cdf,
+                                                       const int32_t *pinned_regime, const void *y, int32_t *regime_out,
+                                                       double *mean_out, double *cov_out, double *log_weight, int32_t *flags,
+                                                       int64_t B, int64_t K, void *stream) {
+  return aesmc::sk_step(true, true, false, nullptr, y_dtype, model, regime_in, mean_in, cov_in, idx, uniforms, particle_cdf,
+                        pinned_regime, y, regime_out, mean_out, cov_out, log_weight, flags, B, K, stream);
+}
+
+// K39: particle_cdf non-NULL is K33's form, pinned_regime non-NULL K38's, both NULL K31's (both given: K49's)
 extern "C" int aesmc_switching_kalman_masked_step(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
                                                   const double *mean_in, const double *cov_in, const int64_t *idx,
                                                   const double *uniforms, const double *particle_cdf,

@@ -38,12 +38,13 @@ template <int TP, bool InLds, int Lanes = kSkBlock> struct SkCov {
 __host__ __device__ constexpr int sk_per_regime(int dp, int dyp) { return dp * dp + 2 * dp + dyp * dp + 2 * dyp; }
 
 // Stages every regime's block into `mdl` as float64, zero-padded to the instantiation's extents (r^2 padded with ONE: the
-// padded pivots are 1, their logarithms 0).  The whole workgroup calls it; the caller places the barrier.
-template <int DP, int DYP>
+// padded pivots are 1, their logarithms 0).  The whole workgroup calls it; the caller places the barrier.  Lanes: the
+// workgroup's size (K48 has two)
+template <int DP, int DYP, int Lanes = kSkBlock>
 __device__ __forceinline__ void sk_stage_model(double *mdl, int M, int D, int Dy, const double *A, const double *b,
                                                const double *q, const double *C, const double *d, const double *r) {
   constexpr int kPer = sk_per_regime(DP, DYP);
-  for (int e = threadIdx.x; e < M * kPer; e += kSkBlock) {
+  for (int e = threadIdx.x; e < M * kPer; e += Lanes) {
     const int s = e / kPer;
     int o = e - s * kPer;
     double v;

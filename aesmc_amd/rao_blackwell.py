@@ -69,7 +69,12 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                paths that leaves p(s_{0:T-1} | y) invariant for ANY number of particles, O(K) per step where the
                                smoother above costs O(N K).  Backwards K34 along the reference; per step K37
                                (`aesmc_switching_conditional_ancestor_index`: K26 with the pinned slot scored by K35's integral)
-                               and K38 (`aesmc_switching_kalman_conditional_step`: K31 with that slot's regime pinned)
+                               and K38 (`aesmc_switching_kalman_conditional_step`: K31 with that slot's regime pinned).
+                               With lookahead=True the conditional form of `adapted_switching_filter`: the free slots
+                               resample on p(y_t | history) and draw the regime from its exact posterior, the systems stay
+                               equally weighted, the pinned slot's ancestor score carries no weight.  Per step K48
+                               (`aesmc_switching_lookahead_conditional_ancestor_index`: K32 and K37 in one launch) and K49
+                               (`aesmc_switching_kalman_conditional_draw`: K33 with slot K-1 pinned)
     switching_particle_gibbs   the chain of such sweeps; its paths are what `switching_state_smooth` takes
                                (examples/slds_gibbs.py: Gibbs over Pi with Dirichlet rows)
     switching_forecast         the predictive distributions of the steps after the last observation, from either filter's
@@ -992,7 +997,7 @@ def switching_smooth_states(observations, model, num_particles, num_trajectories
 
 
 def conditional_switching_filter(observations, model, num_particles, reference, ancestor_sampling=True, uniforms=None,
-                                 regime_uniforms=None, return_particles=False, observed=None):
+                                 regime_uniforms=None, return_particles=False, observed=None, lookahead=False):
     """One sweep of particle Gibbs on the regimes of a `SwitchingLinearGaussian`: a Rao-Blackwellised conditional particle
     filter whose slot num_particles - 1 carries the regime path `reference`, then one draw of a path from the final weights
     along the ancestors.  The kernel leaves p(s_{0:T-1} | y_{0:T-1}) invariant for ANY number of particles (Andrieu, Doucet &
@@ -1018,6 +1023,18 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
         means, covariances (packed), log_weights — and ancestral_indices ((T-1) int64 [batch_size, K]) and indices (T int64
         [batch_size]: the slot the new path passes through).
     observed: `switching_filter`'s (K41 along the reference, K39 with the pinned regime in place of K38).
+    lookahead: False — the sweep described here, call for call.  True — the look-ahead (fully adapted) conditional filter:
+        the free slots resample on the exact first-stage weights p(y_t | history) of the stored system and draw the regime
+        from the ANCESTOR'S exact posterior row, as `adapted_switching_filter` does; slot num_particles - 1 takes the
+        reference's regime.  Every stored system is then equally weighted, so the pinned slot's ancestor is drawn in
+        proportion to Pi[s, reference[t]] x K35's integral alone — it does NOT carry the first-stage weight — and the final
+        draw is from equal weights.  Step 0 is K32 on the prior and the step; a later step is K48
+        (`aesmc_switching_lookahead_conditional_ancestor_index`: the look-ahead and the conditional ancestors in one launch;
+        past `switching_lookahead_conditional_max_particles` the provider composes it from K32 and K37) and K49
+        (`aesmc_switching_kalman_conditional_draw`: K31 drawing from the ancestor's row with slot K-1 pinned).  The uniforms,
+        their order and the limits are the same.  With return_particles, `log_weights` holds T zero tensors and
+        `first_stage_log_weights` (T float64 [batch_size, K]; step 0's on the prior) is added.  With few particles a free
+        slot meets a regime change in the step where it happens instead of only when it draws it from Pi.
 
     Returns T int32 [batch_size] tensors, the new path.  With return_particles: (path, particles).
 
@@ -1086,9 +1103,31 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
                                                                                 observations[time], **mask(time))
                     info = (omega, lam, c)
                     information[time] = (factor[:, 0], lam[:, 0])
-            regimes, means, covariances, log_weights, ancestral = [], [], [], [], []
+            regimes, means, covariances, log_weights, ancestral, first_stage = [], [], [], [], [], []
             state, index = None, None
             for time in range(num_timesteps):
+                if lookahead:
+                    if time == 0:
+                        regime_u = draw(0)
+                        log_v, cdf = provider.switching_lookahead(ops, torch.log(ops["pi0"]), None, observations[0],
+                                                                  num_particles=num_particles, **mask(0))
+                    else:
+                        factor, lam = information[time] if ancestor_sampling else (None, None)
+                        resampling_u, regime_u = block(time - 1), draw(time)
+                        index, log_v, cdf = provider.switching_lookahead_conditional_ancestor_index(
+                            ops, log_Pi, state, observations[time], resampling_u, reference[time], factor, lam, **mask(time))
+                        ancestral.append(index)
+                        index = index.clamp(max=pinned)      # (a failed draw is position K, as below)
+                    regime, mean, cov, _ = provider.switching_kalman_conditional_draw(ops, state, index, regime_u, cdf,
+                                                                                      reference[time], observations[time],
+                                                                                      **mask(time))
+                    state = (regime, mean, cov)
+                    regimes.append(regime), means.append(mean), covariances.append(cov), first_stage.append(log_v)
+                    # the systems after a look-ahead draw are equally weighted: T zero tensors where they are returned, one
+                    # for the final draw where they are not (a fill per step is a launch per step)
+                    if return_particles or time == num_timesteps - 1:
+                        log_weights.append(torch.zeros_like(log_v))
+                    continue
                 if time > 0:
                     factor, lam = information[time] if ancestor_sampling else (None, None)
                     index = provider.switching_conditional_ancestor_index(log_weights[-1], block(time - 1), log_Pi,
@@ -1111,17 +1150,23 @@ def conditional_switching_filter(observations, model, num_particles, reference, 
             path = [torch.gather(regimes[time], 1, indices[time].clamp(max=pinned).unsqueeze(1))[:, 0]
                     for time in range(num_timesteps)]
             inference._raise_for_flags(provider.read_flags(device))
+            # (step 0's first-stage weights meet no resampling launch: a NaN among them is reported here, after the one read)
+            if lookahead and bool(torch.isnan(first_stage[0]).any()):
+                raise FloatingPointError("log_weight contains nan element(s)")
     except BaseException:
         inference._discard_pending_flags()
         raise
     if return_particles:
-        return path, {"regimes": regimes, "means": means, "covariances": covariances, "log_weights": log_weights,
-                      "ancestral_indices": ancestral, "indices": indices}
+        particles = {"regimes": regimes, "means": means, "covariances": covariances, "log_weights": log_weights,
+                     "ancestral_indices": ancestral, "indices": indices}
+        if lookahead:
+            particles["first_stage_log_weights"] = first_stage
+        return path, particles
     return path
 
 
 def switching_particle_gibbs(observations, model, num_particles, num_sweeps, reference=None, ancestor_sampling=True,
-                             burn_in=0, observed=None):
+                             burn_in=0, observed=None, lookahead=False):
     """Runs `num_sweeps` sweeps of `conditional_switching_filter`, each from the path the one before returned: batch_size
     independent Markov chains on regime paths whose stationary law is p(s_{0:T-1} | y_{0:T-1}) for any num_particles; with
     ancestor sampling 8 .. 64 particles mix.
@@ -1129,6 +1174,8 @@ def switching_particle_gibbs(observations, model, num_particles, num_sweeps, ref
     reference: the first path, T int32 [batch_size] tensors; None — one trajectory of `switching_smooth` with num_particles
         particles (which consumes numpy's RandomState as `switching_filter` does; the sweeps draw from torch's generator).
     burn_in: the first `burn_in` sweeps are run and not returned.
+    lookahead: `conditional_switching_filter`'s, for every sweep; with reference=None the first path then comes from
+        `switching_smooth(..., lookahead=True)`.  False is today's chain, call for call.
     The other arguments, `observed` among them, are `conditional_switching_filter`'s.
 
     Returns a dict: regimes (T int32 [batch_size, num_sweeps - burn_in]: regimes[t][b, s] is s_t of chain b after sweep
@@ -1139,12 +1186,14 @@ def switching_particle_gibbs(observations, model, num_particles, num_sweeps, ref
         raise ValueError("switching_particle_gibbs: 0 <= burn_in < num_sweeps, got burn_in = {} and num_sweeps = {}".format(
             burn_in, num_sweeps))
     if reference is None:
-        drawn, _ = switching_smooth(observations, model, num_particles, num_trajectories=1, observed=observed)
+        drawn, _ = switching_smooth(observations, model, num_particles, num_trajectories=1, observed=observed,
+                                    **({"lookahead": True} if lookahead else {}))
         reference = [regime[:, 0].contiguous() for regime in drawn["regimes"]]
     path, kept = list(reference), []
+    more = {"lookahead": True} if lookahead else {}
     for sweep in range(num_sweeps):
         path = conditional_switching_filter(observations, model, num_particles, path, ancestor_sampling=ancestor_sampling,
-                                            observed=observed)
+                                            observed=observed, **more)
         if sweep >= burn_in:
             kept.append(path)
     M = model.num_regimes

@@ -1,7 +1,7 @@
 """Bayesian learning of the transition matrix of a switching linear-Gaussian state-space model by particle Gibbs.
 
     python examples/slds_gibbs.py [--dim 2] [--particles 16] [--batch 16] [--timesteps 200] [--iterations 200]
-                                  [--burn-in 50] [--alpha 1.0] [--seed 0]
+                                  [--burn-in 50] [--alpha 1.0] [--seed 0] [--lookahead]
 
 Simulates series from a two-regime model with a known Pi, puts an independent Dirichlet(alpha, .., alpha) prior on every row of
 Pi and alternates
@@ -13,7 +13,9 @@ Pi and alternates
     Pi | regimes      row i ~ Dirichlet(alpha + the number of transitions i -> j over all series), in plain torch
 
 — a Gibbs sampler on (regimes, Pi) whose stationary law is their joint posterior.  The other parameters are held at their true
-values.  Prints the posterior mean and standard deviation of Pi over the kept iterations beside the truth.
+values.  --lookahead: the sweeps are the look-ahead (fully adapted) conditional filter — the free particles resample on
+p(y_t | history) and draw the regime from its exact posterior (K48 and K49 per step in place of K37 and K38).  Prints the
+posterior mean and standard deviation of Pi over the kept iterations beside the truth.
 """
 import argparse
 import os
@@ -61,6 +63,7 @@ def main():
     parser.add_argument("--burn-in", type=int, default=50)
     parser.add_argument("--alpha", type=float, default=1.0)
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--lookahead", action="store_true")
     args = parser.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("aesmc_amd runs on a HIP device (no CPU fallback)")
@@ -73,11 +76,12 @@ def main():
     Pi = np.full((M, M), 1.0 / M)      # the start: no stickiness at all
     model = build(dict(truth, Pi=Pi), device)
     # the first path: one trajectory of the smoother under the starting Pi (reference=None), then the chain
-    out = rao_blackwell.switching_particle_gibbs(observations, model, args.particles, 1)
+    out = rao_blackwell.switching_particle_gibbs(observations, model, args.particles, 1, lookahead=args.lookahead)
     path = [regime[:, 0].contiguous() for regime in out["regimes"]]
     kept = []
     for iteration in range(args.iterations):
-        out = rao_blackwell.switching_particle_gibbs(observations, model, args.particles, 1, reference=path)
+        out = rao_blackwell.switching_particle_gibbs(observations, model, args.particles, 1, reference=path,
+                                                     lookahead=args.lookahead)
         path = [regime[:, 0].contiguous() for regime in out["regimes"]]
         counts = transition_counts(out["regimes"], M)
         Pi = torch.distributions.Dirichlet(counts + args.alpha).sample()

@@ -99,7 +99,12 @@ extern "C" {
  *                aesmc_switching_statistics_workspace_bytes (K45, K46: the expected sufficient statistics of that model from
  *                per-trajectory smoothed moments — the E-step's reduction, for EM and the score);
  *                aesmc_switching_state_draw (K47: a draw of the continuous state path given a regime path, the whole
- *                backward pass of forward filtering, backward sampling in one launch — for Gibbs on all parameters).
+ *                backward pass of forward filtering, backward sampling in one launch — for Gibbs on all parameters);
+ *                aesmc_switching_lookahead_conditional_ancestor_index, its masked form
+ *                aesmc_switching_masked_lookahead_conditional_ancestor_index, with
+ *                aesmc_switching_lookahead_conditional_max_particles, and aesmc_switching_kalman_conditional_draw (K48, K49:
+ *                the look-ahead and the conditional ancestors in one launch, and K31's step with the regime drawn from the
+ *                ancestor's posterior row and one slot pinned — look-ahead particle Gibbs on the regimes).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -861,6 +866,55 @@ int aesmc_switching_kalman_conditional_step(int y_dtype, const aesmc_switching_m
                                             const double *uniforms, const int32_t *pinned_regime, const void *y,
                                             int32_t *regime_out, double *mean_out, double *cov_out, double *log_weight,
                                             int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K48 — the resampling side of a LOOK-AHEAD conditional sweep in one launch: K32 on the stored system (regime, mean, cov) with
+ * log_Pi as its log-prior, and K37 on the first-stage log-weights K32 gives.  The stored system of a look-ahead sweep is
+ * EQUALLY weighted, so
+ *   log_weight[b,j], cdf[b,j,:]   K32's outputs for particle j (the same chains in the same order), written out
+ *   idx[b,k]   = K37's free slots over log_weight[b,:] at u[b,k]                                             k = 0 .. K-2
+ *   idx[b,K-1] = K37's pinned slot at u[b,K-1] over s[j] = K35's score of particle j against (regime_next[b], factor[b],
+ *                lambda[b]) with a log-weight of exactly 0.0 — NOT log_weight[b,j]: the weights that enter ancestor sampling
+ *                are those of the stored system
+ *   idx[b,K-1] = K - 1         factor and lambda both NULL (no ancestor sampling; regime_next is not read and may be NULL)
+ * Operands as K32's (y, y_dtype, the model, of which m0, s0 and the chain's rows are not read) and K37's (u, regime_next,
+ * factor, lambda).  Later steps only: the state is not optional.
+ * Bad rows as K37's: a NaN first-stage weight (K32's: a stored regime outside [0, M), which also raises
+ * AESMC_FLAG_INDEX_OUT_OF_RANGE; a pivot that is not positive under a regime of positive prior) raises
+ * AESMC_FLAG_NAN_LOG_WEIGHT, no finite maximum AESMC_FLAG_DEGENERATE_ROW, and every slot of the row is K; the same among s
+ * (also: regime_next[b] outside [0, M), with AESMC_FLAG_INDEX_OUT_OF_RANGE) marks only idx[b,K-1] = K.  log_weight and cdf of
+ * such particles are NaN, as K32 writes them.
+ * aesmc_switching_masked_lookahead_conditional_ancestor_index: the same under K40's mask (observed uint8 [B,Dy], not NULL).
+ * The launch keeps log Pi, the model, the scores, for D above 4 a covariance per lane and two arrays of K in LDS: K above
+ * aesmc_switching_lookahead_conditional_max_particles(M, D, Dy) = min(aesmc_switching_conditional_max_particles(D),
+ * (20480 - [T + P + 30 + M M + M (P P + 2 P + Q P + 2 Q) + (P == 8 ? 256 T : 0) + 256 M]) / 2), with P, Q the extents D, Dy
+ * padded to 2, 4 or 8 and T = P (P + 1) / 2 (0 outside the limits of K31), returns AESMC_ERR_UNSUPPORTED, as M, D, Dy above
+ * the limits and B K beyond 32-bit element arithmetic do: such a step is composed from K32 and K37.  NULL (but flags; factor
+ * and lambda together, and regime_next without them) or misaligned pointers, negative sizes, extents below 1 and an output
+ * that is another operand return AESMC_ERR_INVALID_ARGUMENT; B K == 0 is a no-op.  Every check runs before any launch. */
+int64_t aesmc_switching_lookahead_conditional_max_particles(int64_t M, int64_t D, int64_t Dy);
+int aesmc_switching_lookahead_conditional_ancestor_index(int y_dtype, const aesmc_switching_model *model, const double *log_Pi,
+                                                         const int32_t *regime, const double *mean, const double *cov,
+                                                         const void *y, const double *u, const int32_t *regime_next,
+                                                         const double *factor, const double *lambda, int64_t *out_idx,
+                                                         double *log_weight, double *cdf, int32_t *flags, int64_t B,
+                                                         int64_t K, void *stream);
+int aesmc_switching_masked_lookahead_conditional_ancestor_index(int y_dtype, const aesmc_switching_model *model,
+                                                                const double *log_Pi, const int32_t *regime,
+                                                                const double *mean, const double *cov, const void *y,
+                                                                const uint8_t *observed, const double *u,
+                                                                const int32_t *regime_next, const double *factor,
+                                                                const double *lambda, int64_t *out_idx, double *log_weight,
+                                                                double *cdf, int32_t *flags, int64_t B, int64_t K,
+                                                                void *stream);
+
+/* K49 — K31 with K33's and K38's operands at once, the step of a look-ahead conditional sweep: every slot reads its regime from
+ * the ancestor's row of particle_cdf [B,K,M] (K48's, K32's), and slot K-1 takes pinned_regime[b] in its place.  The same kernel;
+ * checks, conventions and statuses are K33's and K38's together.  Under a mask: aesmc_switching_kalman_masked_step with both. */
+int aesmc_switching_kalman_conditional_draw(int y_dtype, const aesmc_switching_model *model, const int32_t *regime_in,
+                                            const double *mean_in, const double *cov_in, const int64_t *idx,
+                                            const double *uniforms, const double *particle_cdf, const int32_t *pinned_regime,
+                                            const void *y, int32_t *regime_out, double *mean_out, double *cov_out,
+                                            double *log_weight, int32_t *flags, int64_t B, int64_t K, void *stream);
 
 /* K39, K40, K41 — K31 (with its K33 and K38 forms), K32 and K34 under a mask of the observation's components.
  *   observed: uint8 [B,Dy], nonzero = component i of y[b] was observed (the storage of a contiguous bool tensor).
