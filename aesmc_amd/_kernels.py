@@ -2847,6 +2847,76 @@ class HipKernels:
                      (model, regimes, means, covs, noise, regime_next, z_next, states, block))
         return states
 
+    # ---- K50, K51 ------------------------------------------------------------------------------
+    def switching_collapse(self, means, covs, log_weights):
+        """The moment-matching collapse of Gaussian mixtures (aesmc_switching_collapse, K50): group (b,g) of N weighted
+        components becomes one Gaussian.  log_weights float64 [B,G,N]; means float64 [B,G,N,D] and covs float64
+        [B,G,N,D(D+1)/2] (packed) — or [B,N,D] and [B,N,D(D+1)/2]: the shared-components form, the row's N components under
+        every one of its G weight rows.  Returns (log_mass [B,G], mean [B,G,D], cov [B,G,D(D+1)/2]) float64, new tensors.
+        A group of weights all -inf: -inf, zeros, zeros; a component of weight -inf is not read; a NaN weight: NaN."""
+        _require_hip(log_weights, "log_weights")
+        device = log_weights.device
+        if log_weights.dim() != 3 or log_weights.dtype != torch.float64:
+            raise ValueError("aesmc_amd: log_weights must be [batch_size, groups, components] float64, got {} {}".format(
+                tuple(log_weights.shape), log_weights.dtype))
+        B, G, N = log_weights.shape
+        _require_hip(means, "means")
+        shared = means.dim() == 3
+        lead = (B, N) if shared else (B, G, N)
+        D = means.size(-1) if means.dim() in (3, 4) else 0
+        TD = D * (D + 1) // 2
+        for tensor, shape, what in ((means, lead + (D,), "means"), (covs, lead + (TD,), "covs")):
+            _require_hip(tensor, what)
+            if D < 1 or tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} (or without the groups: shared) float64 on {}, got {} {} on {}"
+                                 .format(what, (B, G, N, D if what == "means" else TD), device, tuple(tensor.shape),
+                                         tensor.dtype, tensor.device))
+        if D > self.switching_limits()[0] or N > 256 or G > 256 or B * G > 0x7fffffff:
+            raise ValueError("aesmc_amd: switching_collapse takes D <= 8 and at most 256 groups of at most 256 components")
+        means, covs, log_weights = means.contiguous(), covs.contiguous(), log_weights.contiguous()
+        log_mass = torch.empty((B, G), dtype=torch.float64, device=device)
+        mean = torch.empty((B, G, D), dtype=torch.float64, device=device)
+        cov = torch.empty((B, G, TD), dtype=torch.float64, device=device)
+        if B * G == 0:
+            return log_mass, mean, cov
+        self._launch(device, self._lib.aesmc_switching_collapse,
+                     (_ptr(means), 0 if shared else N * D, _ptr(covs), 0 if shared else N * TD, _ptr(log_weights),
+                      _ptr(log_mass), _ptr(mean), _ptr(cov), B, G, N, D, self._stream(log_weights)),
+                     lambda: 8 * (B * (1 if shared else G) * N * (D + TD) + B * G * (N + 1 + D + TD)),
+                     (means, covs, log_weights, log_mass, mean, cov))
+        return log_mass, mean, cov
+
+    def switching_pair_smooth(self, model, mean, cov, mean_next, cov_next):
+        """A Rauch-Tung-Striebel step between mixture components (aesmc_switching_pair_smooth, K51).  model as
+        `switching_kalman_step`'s (A, b, q are read); mean float64 [B,M,D] and cov float64 [B,M,D(D+1)/2]: the components
+        filtered at t; mean_next, cov_next: the same shapes, smoothed at t+1.  Returns (means [B,M,M,D], covs
+        [B,M,M,D(D+1)/2]) float64, new tensors: entry (b,i,j) is component i smoothed against regime j's component."""
+        _require_hip(mean, "mean")
+        device = mean.device
+        block, M, D, Dy = self._switching_block(model, device)
+        TD = D * (D + 1) // 2
+        B = mean.size(0) if mean.dim() == 3 else -1
+        for tensor, shape, what in ((mean, (B, M, D), "mean"), (cov, (B, M, TD), "cov"), (mean_next, (B, M, D), "mean_next"),
+                                    (cov_next, (B, M, TD), "cov_next")):
+            _require_hip(tensor, what)
+            if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, ("batch_size",) + shape[1:], device))
+        max_d, max_dy, max_m = self.switching_limits()
+        if not (1 <= D <= max_d and 1 <= M <= max_m and 1 <= Dy <= max_dy and B * M * M <= 0x7fffffff):
+            raise ValueError("aesmc_amd: switching_pair_smooth does not take these operands (see switching_covers)")
+        mean, cov, mean_next, cov_next = mean.contiguous(), cov.contiguous(), mean_next.contiguous(), cov_next.contiguous()
+        means = torch.empty((B, M, M, D), dtype=torch.float64, device=device)
+        covs = torch.empty((B, M, M, TD), dtype=torch.float64, device=device)
+        if B == 0:
+            return means, covs
+        self._launch(device, self._lib.aesmc_switching_pair_smooth,
+                     (ctypes.byref(block), _ptr(mean), _ptr(cov), _ptr(mean_next), _ptr(cov_next), _ptr(means), _ptr(covs), B,
+                      self._stream(mean)),
+                     lambda: 8 * B * M * (D + TD) * (2 + M) + self._switching_model_bytes(M, D, Dy, rows=False) -
+                     8 * M * (Dy * D + 2 * Dy),
+                     (model, mean, cov, mean_next, cov_next, means, covs, block))
+        return means, covs
+
     # ---- K45, K46 ------------------------------------------------------------------------------
     def switching_statistics_columns(self, latent_dim, observation_dim, masked):
         """F of the [16, F] statistics array (aesmc_switching_statistics_columns; 0 outside the limits)."""

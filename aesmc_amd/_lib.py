@@ -161,6 +161,8 @@ SIGNATURES = {
                                                                     [_i64, _i64, _vp]),
     "aesmc_switching_kalman_conditional_draw": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 13 + [_i64, _i64, _vp]),
     "aesmc_switching_state_draw": (_i32, [ctypes.POINTER(SwitchingModel)] + [_vp] * 8 + [_i64] * 3 + [_vp]),
+    "aesmc_switching_collapse": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 4 + [_i64] * 4 + [_vp]),
+    "aesmc_switching_pair_smooth": (_i32, [ctypes.POINTER(SwitchingModel)] + [_vp] * 6 + [_i64, _vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

@@ -75,6 +75,17 @@ float64.  The NumPy contract of both is `aesmc_amd.testing.rao_blackwell`.
                                equally weighted, the pinned slot's ancestor score carries no weight.  Per step K48
                                (`aesmc_switching_lookahead_conditional_ancestor_index`: K32 and K37 in one launch) and K49
                                (`aesmc_switching_kalman_conditional_draw`: K33 with slot K-1 pinned)
+    collapsed_switching_filter   the DETERMINISTIC collapsed-mixture filter everyone else uses on this model class: GPB2,
+                               which is Kim's filter (Kim 1994; Kim & Nelson 1999), and its first-order cousin IMM (Blom &
+                               Bar-Shalom 1988).  M Gaussians per series, no particles, no random numbers, M^2 (IMM: M)
+                               Kalman updates per step: K31 with the regime forced on the pair slots, then K50
+                               (`aesmc_switching_collapse`: the moment-matching collapse of every regime's mixture into one
+                               Gaussian).  A noise-free approximate evidence and segmentation — exact for T <= 2 (IMM: T = 1),
+                               for one regime and for dynamics shared across regimes — to hold the particle filters against
+    collapsed_switching_smooth   Kim's smoother on top of it: backwards, K51 (`aesmc_switching_pair_smooth`: a
+                               Rauch-Tung-Striebel step between component i at t and regime j's smoothed component at t+1,
+                               K47's pivot rule) and K50 over j.  Smoothed regime, pair and state moments without a random
+                               number: a good start for particle Gibbs for free
     switching_particle_gibbs   the chain of such sweeps; its paths are what `switching_state_smooth` takes
                                (examples/slds_gibbs.py: Gibbs over Pi with Dirichlet rows)
     switching_forecast         the predictive distributions of the steps after the last observation, from either filter's
@@ -978,6 +989,183 @@ def switching_sample_states(observations, model, regimes, noise=None, observed=N
         raise
     return {"states": list(states.unbind(0)), "log_likelihood": log_likelihood,
             "noise": list(stacked_noise.unbind(0)) if noise is None else noise}
+
+
+def _collapsed_forward(provider, ops, observations, num_regimes, order, mask):
+    """The forward pass of the collapsed-mixture filters (`testing.switching_collapsed.collapsed_pass`, call for call): per
+    step K31 forced (`_conditional_filter`'s shim) on M^2 pair slots (order 2) or M slots (order 1, and step 0), K50 over the
+    pairs or the mixing weights, and K50 once more over the M components for the increment and the overall moments.  Returns
+    a dict of T-lists: log_mu [B,M], means [B,M,D], covariances [B,M,TD], scores ([B,M,M] indexed (b,j,i), order 2, t >= 1;
+    else None), masses ([B,M]; None at step 0), increments [B], overall_mean [B,D], overall_cov [B,TD].  Reads nothing from
+    the device."""
+    M = num_regimes
+    B, device = observations[0].size(0), observations[0].device
+    edges = (torch.arange(M, dtype=torch.float64, device=device) + 1.0) / M
+    forced = dict(ops, cdf0=edges, cdf=edges.expand(M, M).contiguous())
+    log_pi0, log_Pi = torch.log(ops["pi0"]), torch.log(ops["Pi"])      # (-inf where a probability is 0) once
+    transposed = log_Pi.t().unsqueeze(0)                                # [1,j,i] = log Pi[i,j]
+    slots = torch.arange(M, dtype=torch.int32, device=device).expand(B, M).contiguous()
+    slot_uniforms = (slots.to(torch.float64) + 0.5) / M
+    pair_slots = slots.repeat(1, M)                                     # slot j M + i: component i ...
+    pair_uniforms = slot_uniforms.repeat_interleave(M, dim=1)           # ... under regime j
+    # a score whose prior part is -inf is -inf whatever its likelihood part is (K32's rule)
+    scored = lambda prior, likelihood: torch.where(prior == -math.inf, prior, prior + likelihood)
+    out = {name: [] for name in ("log_mu", "means", "covariances", "scores", "masses", "increments", "overall_mean",
+                                 "overall_cov")}
+    log_mu = mean = cov = None
+    for time, observation in enumerate(observations):
+        scores = mass = None
+        if time == 0:
+            _, mean, cov, likelihood = provider.switching_kalman_step(forced, None, None, slot_uniforms, observation, **mask(0))
+            g = scored(log_pi0.expand(B, M), likelihood)
+        else:
+            prior = log_mu.unsqueeze(1) + transposed                    # [b,j,i] = log mu_i + log Pi[i,j]
+            if order == 2:
+                state = (pair_slots, mean.repeat(1, M, 1), cov.repeat(1, M, 1))
+                _, pair_mean, pair_cov, likelihood = provider.switching_kalman_step(forced, state, None, pair_uniforms,
+                                                                                    observation, **mask(time))
+                scores = scored(prior, likelihood.reshape(B, M, M))
+                mass, mean, cov = provider.switching_collapse(pair_mean.reshape(B, M, M, -1), pair_cov.reshape(B, M, M, -1),
+                                                              scores)
+                g = mass
+            else:
+                mass, mixed_mean, mixed_cov = provider.switching_collapse(mean, cov, prior)      # (the shared-components form)
+                _, mean, cov, likelihood = provider.switching_kalman_step(forced, (slots, mixed_mean, mixed_cov), None,
+                                                                          slot_uniforms, observation, **mask(time))
+                g = scored(mass, likelihood)
+        increment, overall_mean, overall_cov = provider.switching_collapse(mean.unsqueeze(1), cov.unsqueeze(1), g.unsqueeze(1))
+        log_mu = g - increment
+        for name, value in (("log_mu", log_mu), ("means", mean), ("covariances", cov), ("scores", scores), ("masses", mass),
+                            ("increments", increment.squeeze(1)), ("overall_mean", overall_mean.squeeze(1)),
+                            ("overall_cov", overall_cov.squeeze(1))):
+            out[name].append(value)
+    return out
+
+
+def _prepare_collapsed(name, provider, observations, model, slots_per_regime, observed):
+    if len(observations) == 0:
+        raise ValueError("{}: observations must hold at least one timestep".format(name))
+    ops = model.operands()
+    _, device = _check_observations(name, provider, observations, model, model.num_regimes * slots_per_regime)
+    return ops, device, _observed_steps(name, observed, observations)
+
+
+def _collapsed_filter_results(forward, D, return_components):
+    total = forward["increments"][0]
+    for increment in forward["increments"][1:]:
+        total = total + increment
+    out = {"log_marginal_likelihood": total, "regime_probabilities": torch.exp(torch.stack(forward["log_mu"])),
+           "filtered_mean": torch.stack(forward["overall_mean"]),
+           "filtered_covariance": unpack_covariance(torch.stack(forward["overall_cov"]), D)}
+    if return_components:
+        out.update(log_regime_probabilities=forward["log_mu"], means=forward["means"], covariances=forward["covariances"])
+    return out
+
+
+def collapsed_switching_filter(observations, model, order=2, observed=None, return_components=False):
+    """The deterministic collapsed-mixture filter of a `SwitchingLinearGaussian`: GPB2, which is Kim's filter (Kim 1994; Kim &
+    Nelson 1999), for order=2, and its first-order cousin IMM (Blom & Bar-Shalom 1988) for order=1.  No particles and no
+    random numbers: per series M Gaussians (log mu_i, m_i, P_i), mu_i = p(s_t = i | y_{0:t}), and M^2 (order 1: M) Kalman
+    updates per step where a particle filter makes K M.  What the particle filters of this module are held against: a fast,
+    noise-free approximate evidence and segmentation of thousands of series — a likelihood surface, a start for EM or Gibbs
+    (examples/slds_gibbs.py --start collapsed), a sanity check of a particle run (examples/slds_filter.py --collapsed).
+
+    observations, model, observed: as `switching_filter`'s (`observed` reaches K31's masked entry K39 unchanged; K50 reads no
+    y).  order: 2 or 1.
+
+    Step 0: K31's step-0 form on M slots, slot j forced to regime j as `conditional_kalman_filter` forces it: (m_j, P_j,
+    l_j), g_j = log pi0_j + l_j.  Order 2, t >= 1: K31 forced on M^2 pair slots (slot j M + i: component i under regime j),
+    g[b,j,i] = log mu_i + log Pi[i,j] + l_ij, and K50 (`aesmc_switching_collapse`, the moment-matching collapse) of every
+    group j over i: (mass_j, m_j, P_j), g_j = mass_j.  Order 1, t >= 1: K50 in its shared-components form mixes the M
+    components once per target regime j under log mu_i + log Pi[i,j]: (log c_j, m0_j, P0_j); K31 forced on M slots from
+    those: g_j = log c_j + l_j.  Every step: K50 over the one group of the M components under g — its mass is the evidence
+    increment lse_j g_j, its mean and covariance the filtered ones — and log mu_j = g_j - increment.  Everything stays in the
+    log domain; a score whose prior part is -inf is -inf whatever its likelihood part is (K32's rule: a singular innovation
+    under an impossible regime is ignored).
+
+    Returns a dict: log_marginal_likelihood [batch_size] float64 — DETERMINISTIC and APPROXIMATE: the sum of the
+    increments, not an unbiased estimate and not a bound.  It is exact (to rounding) for order 2 while T <= 2, for order 1 at
+    T = 1, and for both orders and any T with one regime or with dynamics and emission shared across regimes; otherwise off by
+    the moment matching (DESIGN 30 has figures: a few 1e-3 for order 2, a few 1e-2 for order 1 on this package's example
+    models).  regime_probabilities [T, batch_size, M] (p(s_t | y_{0:t})), filtered_mean [T, batch_size, D] and
+    filtered_covariance [T, batch_size, D, D] (the moments of the M-component mixture).  With return_components, T-lists of
+    log_regime_probabilities [batch_size, M], means [batch_size, M, D] and covariances [batch_size, M, D(D+1)/2] (packed);
+    the moments of a regime of probability zero are whatever K31 or K50 left there and are read by nothing.
+
+    ValueError for an invalid model, T == 0 and an order that is not 1 or 2.  Refusals, flags and NaNs as
+    `conditional_kalman_filter`'s: read once, at the end; an exception on the way discards whatever was flagged.  No host
+    synchronisation inside the loop.  Runs under torch.no_grad(): NOT differentiable."""
+    name = "collapsed_switching_filter"
+    if order not in (1, 2):
+        raise ValueError("{}: order must be 1 or 2, got {!r}".format(name, order))
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops, device, mask = _prepare_collapsed(name, provider, observations, model,
+                                                   model.num_regimes if order == 2 else 1, observed)
+            forward = _collapsed_forward(provider, ops, observations, model.num_regimes, order, mask)
+            out = _collapsed_filter_results(forward, model.latent_dim, return_components)
+            _finish_conditional(name, provider, device, False, out["log_marginal_likelihood"])
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
+
+
+def collapsed_switching_smooth(observations, model, observed=None):
+    """The collapsed-mixture smoother (Kim 1994; Kim & Nelson 1999) of a `SwitchingLinearGaussian`: `collapsed_switching_filter`
+    of order 2, keeping each step's pair scores g_t and masses, then backwards for t = T-2 .. 0:
+
+        log joint[b,i,j] = (g_{t+1}[b,j,i] - mass_{t+1}[b,j]) + log mu^s_{t+1}[b,j]
+
+    (the first term is p(s_t = i | s_{t+1} = j, y_{0:t+1}), one observation more than Kim's original uses); K51
+    (`aesmc_switching_pair_smooth`, a Rauch-Tung-Striebel step between components) forms the pair-smoothed (m_ij, P_ij) from
+    component i filtered at t and regime j's smoothed component of t+1; K50 collapses group i over j under log joint[b,i,:]
+    — its mass is log mu^s_t(i) — and once more the M smoothed components into the smoothed moments.  At T-1 the smoothed
+    quantities are the filtered ones.  K51 drops pivots as K47 does: q = 0 components and P = 0 are fine.
+
+    observations, model, observed: as `collapsed_switching_filter`'s.  Returns its keys (without components) plus
+    smoothed_regime_probabilities [T, batch_size, M] (p(s_t | y_{0:T-1})), smoothed_pair_probabilities [T-1, batch_size, M, M]
+    (p(s_t = i, s_{t+1} = j | y_{0:T-1}), indexed (i, j)), smoothed_mean [T, batch_size, D] and smoothed_covariance
+    [T, batch_size, D, D].  All approximate, by the same moment matching; exact (to rounding) for the regime probabilities
+    at T = 2, and for everything with one regime or with dynamics and emission shared across regimes.  Deterministic: a start
+    for `switching_particle_gibbs` is the argmax of smoothed_regime_probabilities.
+
+    Validation, refusals, flags and NaNs as `collapsed_switching_filter`'s: one read at the end, no host synchronisation
+    inside the loops.  Runs under torch.no_grad(): NOT differentiable."""
+    name = "collapsed_switching_smooth"
+    provider = _kernels.get()
+    try:
+        with torch.no_grad(), _syncfree.scope():
+            ops, device, mask = _prepare_collapsed(name, provider, observations, model, model.num_regimes, observed)
+            M, D = model.num_regimes, model.latent_dim
+            forward = _collapsed_forward(provider, ops, observations, M, 2, mask)
+            out = _collapsed_filter_results(forward, D, False)
+            last = len(observations) - 1
+            log_s, mean, cov = forward["log_mu"][last], forward["means"][last], forward["covariances"][last]
+            regimes, pairs = [None] * last + [log_s], [None] * last
+            centre, spread = [None] * last + [forward["overall_mean"][last]], [None] * last + [forward["overall_cov"][last]]
+            for time in range(last - 1, -1, -1):
+                conditional = (forward["scores"][time + 1] - forward["masses"][time + 1].unsqueeze(2)).transpose(1, 2)
+                prior = log_s.unsqueeze(1)                              # [b,i,j]: log mu^s_{t+1}(j)
+                joint = torch.where(prior == -math.inf, prior, conditional + prior)
+                pair_mean, pair_cov = provider.switching_pair_smooth(ops, forward["means"][time], forward["covariances"][time],
+                                                                     mean, cov)
+                log_s, mean, cov = provider.switching_collapse(pair_mean, pair_cov, joint)
+                _, overall_mean, overall_cov = provider.switching_collapse(mean.unsqueeze(1), cov.unsqueeze(1),
+                                                                           log_s.unsqueeze(1))
+                regimes[time], pairs[time] = log_s, joint
+                centre[time], spread[time] = overall_mean.squeeze(1), overall_cov.squeeze(1)
+            batch_size = observations[0].size(0)
+            out.update(smoothed_regime_probabilities=torch.exp(torch.stack(regimes)),
+                       smoothed_pair_probabilities=torch.exp(torch.stack(pairs)) if last > 0 else
+                       torch.zeros((0, batch_size, M, M), dtype=torch.float64, device=device),
+                       smoothed_mean=torch.stack(centre), smoothed_covariance=unpack_covariance(torch.stack(spread), D))
+            _finish_conditional(name, provider, device, False, out["log_marginal_likelihood"])
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return out
 
 
 def switching_smooth_states(observations, model, num_particles, num_trajectories=None, resampling=None, lookahead=False,

@@ -3,7 +3,7 @@
 covariance of the continuous state given its regime history (kernel K31).
 
     python examples/slds_filter.py [--regimes 2] [--dim 2] [--particles 256] [--batch 8] [--timesteps 200] [--short 6]
-                                   [--lookahead | --discrete] [--smooth] [--missing FRACTION] [--forecast H]
+                                   [--lookahead | --discrete] [--smooth] [--missing FRACTION] [--forecast H] [--collapsed]
 
 Simulates a series whose regimes differ in their dynamics, filters it, and prints how often the most probable filtered
 regime is the true one and the error of the filtered mean; then, for a short series, log Z-hat beside the exact log p(y)
@@ -20,6 +20,10 @@ every observation is dropped with that probability (NaN is written over it) and 
 `observed=` (the masked kernels K39 / K40): regime accuracy and state RMSE beside the fully observed run's.  With
 --forecast H the last H steps are held out, the filter runs on the rest and `switching_forecast` predicts them: the RMSE
 of the forecast's observation mean against the held-out observations, beside their own spread and the forecast's.
+With --collapsed the deterministic collapsed-mixture filters (`collapsed_switching_filter`: GPB2 / Kim's filter and IMM, kernel
+K50) and Kim's smoother (`collapsed_switching_smooth`, kernel K51) run on the same series — no particles, no random numbers
+— and their evidence, regime accuracy and state RMSE are printed beside the particle filter's; for the short series their
+evidence stands beside the exact one.
 """
 import argparse
 import os
@@ -62,6 +66,8 @@ def main():
     ap.add_argument("--missing", type=float, default=0.0, metavar="FRACTION",
                     help="also filter with every component dropped with this probability")
     ap.add_argument("--forecast", type=int, default=0, metavar="H", help="also hold out the last H steps and forecast them")
+    ap.add_argument("--collapsed", action="store_true",
+                    help="also run the deterministic collapsed-mixture filters (GPB2 / Kim, IMM) and Kim's smoother: the baseline")
     args = ap.parse_args()
     if args.lookahead and args.discrete:
         ap.error("--lookahead and --discrete name two filters: give one")
@@ -80,6 +86,19 @@ def main():
     print("T = {}, {} series, K = {}: filtered regime = true regime {:.1%} of the time; RMSE of the filtered mean {:.3f}; "
           "log Z-hat per step {:.4f}".format(args.timesteps, args.batch, args.particles, accuracy, error,
                                              out["log_marginal_likelihood"].mean().item() / args.timesteps))
+    if args.collapsed:
+        truth, latent = torch.stack(regimes), torch.stack(states)
+        for label, baseline in (("GPB2 / Kim (order 2)", rao_blackwell.collapsed_switching_filter(observations, model, order=2)),
+                                ("IMM (order 1)", rao_blackwell.collapsed_switching_filter(observations, model, order=1))):
+            print("collapsed {}: filtered regime = true regime {:.1%} of the time; RMSE of the filtered mean {:.3f}; approximate "
+                  "log p(y) per step {:.4f}".format(
+                      label, (baseline["regime_probabilities"].argmax(dim=-1) == truth).double().mean().item(),
+                      (baseline["filtered_mean"] - latent).pow(2).mean().sqrt().item(),
+                      baseline["log_marginal_likelihood"].mean().item() / args.timesteps))
+        kim = rao_blackwell.collapsed_switching_smooth(observations, model)
+        print("collapsed smoother (Kim): smoothed regime = true regime {:.1%} of the time; RMSE of the smoothed mean {:.3f}".format(
+            (kim["smoothed_regime_probabilities"].argmax(dim=-1) == truth).double().mean().item(),
+            (kim["smoothed_mean"] - latent).pow(2).mean().sqrt().item()))
     if args.smooth:
         smoothed = rao_blackwell.switching_backward_simulate(out, model, observations, num_trajectories=args.trajectories)
         guess = smoothed["smoothed_regime_probabilities"].argmax(dim=-1)
@@ -112,6 +131,10 @@ def main():
                for _ in range(5)]
     print("T = {}: exact log p(y) = {:.6f} ({} regime sequences); log Z-hat over 5 runs: {}".format(
         args.short, exact, args.regimes ** args.short, ", ".join("{:.6f}".format(v) for v in repeats)))
+    if args.collapsed:
+        print("T = {}: collapsed log p(y): order 2 {:.6f}, order 1 {:.6f} (deterministic, approximate)".format(
+            args.short, *[rao_blackwell.collapsed_switching_filter(short, model, order=order)["log_marginal_likelihood"].item()
+                          for order in (2, 1)]))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Bayesian learning of the transition matrix of a switching linear-Gaussian state-space model by particle Gibbs.
 
     python examples/slds_gibbs.py [--dim 2] [--particles 16] [--batch 16] [--timesteps 200] [--iterations 200]
-                                  [--burn-in 50] [--alpha 1.0] [--seed 0] [--lookahead]
+                                  [--burn-in 50] [--alpha 1.0] [--seed 0] [--lookahead] [--start smoother|collapsed]
 
 Simulates series from a two-regime model with a known Pi, puts an independent Dirichlet(alpha, .., alpha) prior on every row of
 Pi and alternates
@@ -14,7 +14,10 @@ Pi and alternates
 
 — a Gibbs sampler on (regimes, Pi) whose stationary law is their joint posterior.  The other parameters are held at their true
 values.  --lookahead: the sweeps are the look-ahead (fully adapted) conditional filter — the free particles resample on
-p(y_t | history) and draw the regime from its exact posterior (K48 and K49 per step in place of K37 and K38).  Prints the
+p(y_t | history) and draw the regime from its exact posterior (K48 and K49 per step in place of K37 and K38).  --start
+collapsed: the first reference path is the argmax of the smoothed regime probabilities of the deterministic collapsed-mixture
+smoother (`collapsed_switching_smooth`: Kim's smoother, kernels K50 and K51) under the starting Pi — a good start that costs
+no particles — instead of one trajectory of the particle smoother.  Prints the
 posterior mean and standard deviation of Pi over the kept iterations beside the truth.
 """
 import argparse
@@ -64,6 +67,8 @@ def main():
     parser.add_argument("--alpha", type=float, default=1.0)
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--lookahead", action="store_true")
+    parser.add_argument("--start", choices=("smoother", "collapsed"), default="smoother",
+                        help="the first reference path: a trajectory of the particle smoother, or the collapsed smoother's argmax")
     args = parser.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("aesmc_amd runs on a HIP device (no CPU fallback)")
@@ -75,9 +80,14 @@ def main():
     observations = build(truth, device).simulate(args.timesteps, args.batch, seed=args.seed)
     Pi = np.full((M, M), 1.0 / M)      # the start: no stickiness at all
     model = build(dict(truth, Pi=Pi), device)
-    # the first path: one trajectory of the smoother under the starting Pi (reference=None), then the chain
-    out = rao_blackwell.switching_particle_gibbs(observations, model, args.particles, 1, lookahead=args.lookahead)
-    path = [regime[:, 0].contiguous() for regime in out["regimes"]]
+    if args.start == "collapsed":
+        # the first path: the most probable smoothed regime of Kim's smoother under the starting Pi, then the chain
+        smoothed = rao_blackwell.collapsed_switching_smooth(observations, model)["smoothed_regime_probabilities"]
+        path = list(smoothed.argmax(dim=-1).to(torch.int32).unbind(0))
+    else:
+        # the first path: one trajectory of the smoother under the starting Pi (reference=None), then the chain
+        out = rao_blackwell.switching_particle_gibbs(observations, model, args.particles, 1, lookahead=args.lookahead)
+        path = [regime[:, 0].contiguous() for regime in out["regimes"]]
     kept = []
     for iteration in range(args.iterations):
         out = rao_blackwell.switching_particle_gibbs(observations, model, args.particles, 1, reference=path,

@@ -104,7 +104,10 @@ extern "C" {
  *                aesmc_switching_masked_lookahead_conditional_ancestor_index, with
  *                aesmc_switching_lookahead_conditional_max_particles, and aesmc_switching_kalman_conditional_draw (K48, K49:
  *                the look-ahead and the conditional ancestors in one launch, and K31's step with the regime drawn from the
- *                ancestor's posterior row and one slot pinned — look-ahead particle Gibbs on the regimes).
+ *                ancestor's posterior row and one slot pinned — look-ahead particle Gibbs on the regimes);
+ *                aesmc_switching_collapse, aesmc_switching_pair_smooth (K50, K51: the moment-matching collapse of Gaussian
+ *                mixtures and a Rauch-Tung-Striebel step between mixture components — the deterministic collapsed-mixture
+ *                filter and smoother, GPB2 / Kim's filter and IMM).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -1083,6 +1086,54 @@ int aesmc_switching_statistics_finish(const void *workspace, double *out, int ma
 int aesmc_switching_state_draw(const aesmc_switching_model *model, const int32_t *regimes, const double *mean,
                                const double *cov, const double *noise, const int32_t *regime_next, const double *z_next,
                                double *states, int32_t *flags, int64_t T, int64_t B, int64_t N, void *stream);
+
+/* K50 — the moment-matching collapse of Gaussian mixtures, what the collapsed-mixture filters of the same model (GPB2, which
+ * is Kim's filter — Kim 1994; Kim & Nelson 1999 — and IMM, Blom & Bar-Shalom 1988) do between two steps of K31: group (b,g)
+ * has N components (lw_n, m_n, P_n) — a log-weight, a mean and a packed covariance — and is replaced by ONE Gaussian with
+ * the mixture's mass, mean and covariance.  One lane per group; float64, every sum ONE chain of fused multiply-adds
+ * ascending in n from the value named first:
+ *   top = max_n lw_n;   e_n = exp(lw_n - top);   sum = 0 + sum_n e_n;   log_mass = top + log(sum);   w_n = e_n (1 / sum)
+ *   mean_p = 0 + sum_n w_n m_np
+ *   cov_ps = 0 + sum_n [w_n P_n,ps, then (w_n d_np) d_ns],  p >= s,  d_n = m_n - mean      (the centred two-pass form)
+ * A group whose every weight is -inf (and one with N == 0) writes log_mass = -inf, a zero mean and a zero covariance.  A
+ * component of weight -inf is not read into a chain: its moments may be NaN.  A NaN weight gives NaN outputs for its group.
+ *   mean float64 [B,G,N,D] and cov float64 [B,G,N,D(D+1)/2], each with an element stride between groups: the dense one
+ *   (N D, N D(D+1)/2), or 0 — the row's N components are shared by its G groups and the operand is [B,N,D], [B,N,D(D+1)/2]
+ *   (IMM's mixing: one set of components under M rows of weights);  log_weight float64 [B,G,N];
+ *   log_mass float64 [B,G];  mean_out float64 [B,G,D];  cov_out float64 [B,G,D(D+1)/2]
+ * No atomics: the same inputs give the same bits.  NULL or misaligned pointers, negative B, G or N, D below 1, a group
+ * stride that is neither 0 nor the dense one and an output that is an input or another output return
+ * AESMC_ERR_INVALID_ARGUMENT; B G == 0 is a no-op; D above K31's limit, N or G above 256, or B G beyond 32-bit arithmetic
+ * return AESMC_ERR_UNSUPPORTED.  Every check runs before any launch. */
+int aesmc_switching_collapse(const double *mean, int64_t mean_group_stride, const double *cov, int64_t cov_group_stride,
+                             const double *log_weight, double *log_mass, double *mean_out, double *cov_out, int64_t B,
+                             int64_t G, int64_t N, int64_t D, void *stream);
+
+/* K51 — a Rauch-Tung-Striebel step between mixture components, the backward step of the collapsed-mixture smoother (Kim
+ * 1994): lane (b,i,j) smooths component i filtered at time t, N(m, P), against regime j's smoothed component of time t+1,
+ * N(ms, Ps), through A_j, b_j, q2 = q_j^2.  It is K47's measurement update with ms as the observation, and the smoothed
+ * covariance carried through the gain; chains and the pivot rule as K47's (float64, every sum ONE chain of fused
+ * multiply-adds in ascending index order from the value named first):
+ *   V_il = 0 + sum_c A_j[i,c] P_cl;      e_i = (ms_i - b_j[i]) - sum_l A_j[i,l] m_l
+ *   S_ik = (i == k ? q2_i : 0) + sum_l A_j[i,l] V_kl,  i >= k;      tau = 2^-40 max_i S_ii
+ *   L = chol(S) column by column: pivot_k = S_kk - sum_{c<k} L_kc^2; KEPT when pivot_k > tau: rk_k = 1 / sqrt(pivot_k),
+ *       L_ik = (S_ik - sum_{c<k} L_ic L_kc) rk_k; otherwise the column is zero and rk_k = 0
+ *   v_i  = (e_i - sum_{c<i} L_ic v_c) rk_i;   U_il = (V_il - sum_{c<i} L_ic U_cl) rk_i;
+ *   X_il = (Ps_il - sum_{c<i} L_ic X_cl) rk_i                                              (a dropped pivot: a zero row)
+ *   Gm_ik = (X_ik - sum_{c<k} Gm_ic L_kc) rk_k                                             (a dropped pivot: a zero column)
+ *   Y_ks = 0 + sum_c Gm_kc U_cs
+ *   m'_p = m_p + sum_i U_ip v_i;      P'_ps = P_ps - sum_k U_kp U_ks + sum_k U_kp Y_ks,  p >= s
+ * S is only positive semi-definite — q = 0 components and P = 0 are fine (P = 0 returns m and P as they are).
+ *   mean float64 [B,M,D] and cov float64 [B,M,D(D+1)/2]: the components filtered at t;  mean_next, cov_next: the same
+ *   shapes, smoothed at t+1;  mean_out float64 [B,M,M,D] and cov_out float64 [B,M,M,D(D+1)/2], indexed (b, i, j): i is the
+ *   outer index, K50's [B,G,N] layout for the collapse over j that follows.
+ * No y, no flags, no atomics: the same inputs give the same bits.  NULL or misaligned pointers, a negative B, M, D or Dy below
+ * 1 and an output that is an input or the other output return AESMC_ERR_INVALID_ARGUMENT; B == 0 is a no-op; D, Dy or M
+ * above the limits of K31 or B M^2 beyond 32-bit arithmetic return AESMC_ERR_UNSUPPORTED.  Every check runs before any
+ * launch. */
+int aesmc_switching_pair_smooth(const aesmc_switching_model *model, const double *mean, const double *cov,
+                                const double *mean_next, const double *cov_next, double *mean_out, double *cov_out, int64_t B,
+                                void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
