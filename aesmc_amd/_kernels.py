@@ -2917,6 +2917,131 @@ class HipKernels:
                      (model, mean, cov, mean_next, cov_next, means, covs, block))
         return means, covs
 
+    # ---- K52, K53, K54 -------------------------------------------------------------------------
+    SWITCHING_GRADIENTS = ("m0", "s0", "A", "b", "q", "C", "d", "r")
+
+    def switching_kalman_step_backward(self, model, regime, state, observation, grad_mean, grad_cov, grad_log_weight,
+                                       observed=None, need_state=True, need=SWITCHING_GRADIENTS):
+        """The adjoint of `switching_kalman_step` with the regime given (aesmc_switching_kalman_step_backward, K52; with
+        `observed` aesmc_switching_kalman_masked_step_backward, K53).  model, observation, observed as the step's; regime
+        int32 [B,K]: what the step returned; state: None (step 0) or (mean [B,K,D], cov [B,K,D(D+1)/2]), what it was given;
+        grad_mean [B,K,D], grad_cov [B,K,D(D+1)/2], grad_log_weight [B,K] float64: the gradients arriving at its outputs.
+        Returns (grad_mean_in, grad_cov_in, grads): the per-slot two None at step 0 or without `need_state` (a bool for
+        both, or a pair (mean, cov) for each alone); grads a dict
+        of the names in `need` (of SWITCHING_GRADIENTS; m0 and s0 only at step 0, where A, b and q are zero) to new float64
+        tensors of the operands' shapes.  Only what is asked for is computed; the per-regime sums go through a workspace
+        of aesmc_switching_backward_workspace_bytes from torch's caching allocator, per call."""
+        _require_hip(observation, "observation")
+        tag = _tag(observation, "observation")
+        device = observation.device
+        block, M, D, Dy = self._switching_block(model, device)
+        TD = D * (D + 1) // 2
+        B = observation.size(0) if observation.dim() == 2 else -1
+        K = regime.size(1) if torch.is_tensor(regime) and regime.dim() == 2 else -1
+        if tuple(observation.shape) != (B, Dy):
+            raise ValueError("aesmc_amd: observation must be [batch_size, {}], got {}".format(Dy, tuple(observation.shape)))
+        if not self.switching_covers(observation, M, D, Dy, max(K, 0)):
+            raise ValueError("aesmc_amd: switching_kalman_step_backward does not take these operands (see switching_covers)")
+        later = state is not None
+        mean = cov = None
+        if later:
+            regime, mean, cov = self._switching_state((regime,) + tuple(state), B, K, D, device)
+        else:
+            _require_hip(regime, "regime")
+            if tuple(regime.shape) != (B, K) or regime.dtype != torch.int32 or regime.device != device:
+                raise ValueError("aesmc_amd: regime must be {} int32 on {}".format((B, K), device))
+            regime = regime.contiguous()
+        arriving = []
+        for tensor, shape, what in ((grad_mean, (B, K, D), "grad_mean"), (grad_cov, (B, K, TD), "grad_cov"),
+                                    (grad_log_weight, (B, K), "grad_log_weight")):
+            _require_hip(tensor, what)
+            if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} float64 on {}".format(what, shape, device))
+            arriving.append(tensor.contiguous())
+        observation = observation.contiguous()
+        if observed is not None:
+            observed = self._switching_observed(observed, B, Dy, device)
+        need = tuple(name for name in self.SWITCHING_GRADIENTS if name in need and not (later and name in ("m0", "s0")))
+        need_mean, need_cov = need_state if isinstance(need_state, (tuple, list)) else (need_state, need_state)
+        need_mean, need_cov = bool(need_mean) and later, bool(need_cov) and later
+        need_state = need_mean or need_cov
+        if not need and not need_state:
+            raise ValueError("aesmc_amd: switching_kalman_step_backward was asked for nothing")
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=device)
+        grad_mean_in, grad_cov_in = new(B, K, D) if need_mean else None, new(B, K, TD) if need_cov else None
+        grads = {name: new(*model[name].shape) for name in need}
+        if B * K == 0:
+            for value in grads.values():
+                value.zero_()
+            return grad_mean_in, grad_cov_in, grads
+        ws_bytes = int(self._lib.aesmc_switching_backward_workspace_bytes(B, K, D, Dy)) if need else 0
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if need else None
+        head = (tag, ctypes.byref(block), _ptr(regime), _ptr(mean), _ptr(cov), _ptr(observation))
+        tail = tuple(_ptr(t) for t in arriving) + (_ptr(grad_mean_in), _ptr(grad_cov_in)) + \
+            tuple(_ptr(grads.get(name)) for name in self.SWITCHING_GRADIENTS) + \
+            (_ptr(ws), ws_bytes, _ptr(self.flags(device)), B, K, self._stream(observation))
+        entry, name, middle = (self._lib.aesmc_switching_kalman_step_backward, "switching_kalman_step_backward", ()) \
+            if observed is None else (self._lib.aesmc_switching_kalman_masked_step_backward,
+                                      "switching_kalman_masked_step_backward", (_ptr(observed),))
+        self._launch(device, entry, head + middle + tail,
+                     lambda: B * K * (4 + 8 * (D + TD + 1) + (8 * (D + TD) if later else 0) +
+                                      (8 * D if need_mean else 0) + (8 * TD if need_cov else 0)) + 2 * ws_bytes +
+                     B * Dy * (observation.element_size() + (0 if observed is None else 1)) +
+                     self._switching_model_bytes(M, D, Dy, rows=False),
+                     (model, regime, mean, cov, observation, observed, arriving, grad_mean_in, grad_cov_in, grads, ws, block),
+                     name=name)
+        return grad_mean_in, grad_cov_in, grads
+
+    def switching_collapse_backward(self, means, covs, log_weights, grad_log_mass, grad_mean, grad_cov, need_means=True,
+                                    need_covs=True, need_log_weights=True):
+        """The adjoint of `switching_collapse` (aesmc_switching_collapse_backward, K54): its three operands and the float64
+        gradients arriving at log_mass [B,G], mean [B,G,D] and cov [B,G,D(D+1)/2].  Returns (grad_means, grad_covs,
+        grad_log_weights) in the operands' shapes — for shared components [B,N,.]: the sum over the row's groups in
+        ascending order — None where not asked for."""
+        _require_hip(log_weights, "log_weights")
+        device = log_weights.device
+        if log_weights.dim() != 3 or log_weights.dtype != torch.float64:
+            raise ValueError("aesmc_amd: log_weights must be [batch_size, groups, components] float64, got {} {}".format(
+                tuple(log_weights.shape), log_weights.dtype))
+        B, G, N = log_weights.shape
+        _require_hip(means, "means")
+        shared = means.dim() == 3
+        lead = (B, N) if shared else (B, G, N)
+        D = means.size(-1) if means.dim() in (3, 4) else 0
+        TD = D * (D + 1) // 2
+        checked = []
+        for tensor, shape, what in ((means, lead + (D,), "means"), (covs, lead + (TD,), "covs"),
+                                    (grad_log_mass, (B, G), "grad_log_mass"), (grad_mean, (B, G, D), "grad_mean"),
+                                    (grad_cov, (B, G, TD), "grad_cov")):
+            _require_hip(tensor, what)
+            if D < 1 or tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != device:
+                raise ValueError("aesmc_amd: {} must be {} float64 on {}, got {} {} on {}".format(
+                    what, shape, device, tuple(tensor.shape), tensor.dtype, tensor.device))
+            checked.append(tensor.contiguous())
+        means, covs, grad_log_mass, grad_mean, grad_cov = checked
+        if D > self.switching_limits()[0] or N > 256 or G > 256 or B * G > 0x7fffffff:
+            raise ValueError("aesmc_amd: switching_collapse_backward takes D <= 8 and at most 256 groups of at most 256 components")
+        if not (need_means or need_covs or need_log_weights):
+            raise ValueError("aesmc_amd: switching_collapse_backward was asked for nothing")
+        log_weights = log_weights.contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=device)
+        out_means = new(*means.shape) if need_means else None
+        out_covs = new(*covs.shape) if need_covs else None
+        out_weights = new(B, G, N) if need_log_weights else None
+        if B * G == 0 or N == 0:
+            for value in (out_means, out_covs):
+                if value is not None:
+                    value.zero_()
+            return out_means, out_covs, out_weights
+        self._launch(device, self._lib.aesmc_switching_collapse_backward,
+                     (_ptr(means), 0 if shared else N * D, _ptr(covs), 0 if shared else N * TD, _ptr(log_weights),
+                      _ptr(grad_log_mass), _ptr(grad_mean), _ptr(grad_cov), _ptr(out_weights), _ptr(out_means), _ptr(out_covs),
+                      B, G, N, D, self._stream(log_weights)),
+                     lambda: 8 * (B * (1 if shared else G) * N * (D + TD) * (1 + (1 if need_means or need_covs else 0)) +
+                                  B * G * (2 * N + 1 + D + TD)),
+                     (means, covs, log_weights, grad_log_mass, grad_mean, grad_cov, out_means, out_covs, out_weights))
+        return out_means, out_covs, out_weights
+
     # ---- K45, K46 ------------------------------------------------------------------------------
     def switching_statistics_columns(self, latent_dim, observation_dim, masked):
         """F of the [16, F] statistics array (aesmc_switching_statistics_columns; 0 outside the limits)."""

@@ -163,6 +163,12 @@ SIGNATURES = {
     "aesmc_switching_state_draw": (_i32, [ctypes.POINTER(SwitchingModel)] + [_vp] * 8 + [_i64] * 3 + [_vp]),
     "aesmc_switching_collapse": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 4 + [_i64] * 4 + [_vp]),
     "aesmc_switching_pair_smooth": (_i32, [ctypes.POINTER(SwitchingModel)] + [_vp] * 6 + [_i64, _vp]),
+    "aesmc_switching_backward_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "aesmc_switching_kalman_step_backward": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 18 + [_i64, _vp, _i64,
+                                                                                                           _i64, _vp]),
+    "aesmc_switching_kalman_masked_step_backward": (_i32, [_i32, ctypes.POINTER(SwitchingModel)] + [_vp] * 19 +
+                                                    [_i64, _vp, _i64, _i64, _vp]),
+    "aesmc_switching_collapse_backward": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 7 + [_i64] * 4 + [_vp]),
     "aesmc_affine_normal_logweight": (_i32, [_i32, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp, _vp, _vp,
                                              _i64, _i64, _vp]),
     "aesmc_affine_normal_propagate_resampled": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _map_p, _map_p, _map_p, _vp, _vp,

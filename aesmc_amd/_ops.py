@@ -1084,3 +1084,88 @@ def adapted_draw(loc, index, M, offset, L, eps):
     if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
         return _AdaptedDraw.apply(loc, None if index is None else _kernels.as_index(index), M, offset, L, eps.detach())
     return _kernels.get().adapted_draw(loc.detach(), index, M.detach(), offset.detach(), L.detach(), eps.detach())
+
+
+# ---- the collapsed-mixture evidence: K31 forced and K50, their backwards K52 / K53 and K54 -------------------------------
+_SWITCHING_GRADIENTS = ("m0", "s0", "A", "b", "q", "C", "d", "r")
+
+
+class _SwitchingKalmanStep(torch.autograd.Function):
+    """(regime, mean, cov, log_weight) of one step of K31 with the regime forced by the caller's rows and uniforms (with
+    `observed`: K39) — the provider's `switching_kalman_step`, unchanged.  The backward is one launch of K52 (K53) and its
+    finishing launch: the gradients of the stored mean and covariance and of the eight model tensors the step reads, each
+    only where asked for.  The regime carries no gradient; the rows, the uniforms and y take none.  First order only."""
+
+    @staticmethod
+    def forward(ctx, cdf0, cdf, regime_in, mean_in, cov_in, uniforms, observation, observed, *model):
+        ops = dict(zip(_SWITCHING_GRADIENTS, (t.detach() for t in model)), cdf0=cdf0, cdf=cdf)
+        state = None if regime_in is None else (regime_in, mean_in.detach(), cov_in.detach())
+        regime, mean, cov, log_weight = _kernels.get().switching_kalman_step(
+            ops, state, None, uniforms, observation, **({} if observed is None else {"observed": observed}))
+        ctx.save_for_backward(cdf0, cdf, regime, mean_in, cov_in, observation, observed, *model)
+        ctx.mark_non_differentiable(regime)
+        return regime, mean, cov, log_weight
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _, grad_mean, grad_cov, grad_log_weight):
+        cdf0, cdf, regime, mean_in, cov_in, observation, observed = ctx.saved_tensors[:7]
+        ops = dict(zip(_SWITCHING_GRADIENTS, ctx.saved_tensors[7:]), cdf0=cdf0, cdf=cdf)
+        need = ctx.needs_input_grad
+        later = mean_in is not None
+        wanted = tuple(name for i, name in enumerate(_SWITCHING_GRADIENTS)
+                       if need[8 + i] and not (later and name in ("m0", "s0")))
+        need_state = (later and need[3], later and need[4])
+        grad_mean_in = grad_cov_in = None
+        grads = {}
+        if wanted or any(need_state):
+            grad_mean_in, grad_cov_in, grads = _kernels.get().switching_kalman_step_backward(
+                ops, regime, None if not later else (mean_in, cov_in), observation, grad_mean, grad_cov, grad_log_weight,
+                observed=observed, need_state=need_state, need=wanted)
+        model_grads = tuple(grads.get(name) for name in _SWITCHING_GRADIENTS)
+        return (None, None, None, grad_mean_in, grad_cov_in, None, None, None) + \
+            model_grads
+
+
+def switching_kalman_step_forced(model, state, uniforms, observation, observed=None):
+    """`HipKernels.switching_kalman_step(model, state, None, uniforms, observation, observed)` for a caller that FORCES the
+    regimes (cumulative rows (1/M, .., 1) and uniforms (s + 1/2) / M: the collapsed-mixture filters), differentiable in the
+    stored mean and covariance and in m0, s0, A, b, q, C, d, r through K52 / K53.  Returns (regime, mean, cov, log_weight)."""
+    regime_in, mean_in, cov_in = (None, None, None) if state is None else state
+    tensors = [model[name] for name in _SWITCHING_GRADIENTS]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors + [mean_in, cov_in]):
+        return _SwitchingKalmanStep.apply(model["cdf0"], model["cdf"], regime_in, mean_in, cov_in, uniforms, observation,
+                                          observed, *tensors)
+    ops = {name: value.detach() for name, value in model.items()}
+    state = None if state is None else (regime_in, mean_in.detach(), cov_in.detach())
+    return _kernels.get().switching_kalman_step(ops, state, None, uniforms, observation,
+                                                **({} if observed is None else {"observed": observed}))
+
+
+class _SwitchingCollapse(torch.autograd.Function):
+    """(log_mass, mean, cov) of the moment-matching collapse K50 — the provider's `switching_collapse`, unchanged; the
+    backward is one launch of K54.  First order only."""
+
+    @staticmethod
+    def forward(ctx, means, covs, log_weights):
+        out = _kernels.get().switching_collapse(means.detach(), covs.detach(), log_weights.detach())
+        ctx.save_for_backward(means, covs, log_weights)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_log_mass, grad_mean, grad_cov):
+        means, covs, log_weights = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need):
+            return None, None, None
+        return _kernels.get().switching_collapse_backward(means, covs, log_weights, grad_log_mass, grad_mean, grad_cov,
+                                                          need_means=need[0], need_covs=need[1], need_log_weights=need[2])
+
+
+def switching_collapse(means, covs, log_weights):
+    """`HipKernels.switching_collapse`, differentiable in all three operands through K54."""
+    operands = (means, covs, log_weights)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
+        return _SwitchingCollapse.apply(*operands)
+    return _kernels.get().switching_collapse(*(t.detach() for t in operands))

@@ -21,7 +21,8 @@ SOURCES = ["abi.hip", "logweight_lse.hip", "ancestor_index.hip", "ancestor_index
            "linear_gaussian_initial.hip", "adapted_step.hip", "adapted_step_backward.hip",
            "switching_kalman.hip", "switching_lookahead.hip", "switching_information.hip", "switching_backward.hip",
            "switching_smooth.hip", "switching_conditional.hip", "switching_optimal_resample.hip", "switching_statistics.hip",
-           "switching_state_draw.hip", "switching_lookahead_conditional.hip", "switching_collapse.hip"]
+           "switching_state_draw.hip", "switching_lookahead_conditional.hip", "switching_collapse.hip",
+           "switching_kalman_backward.hip", "switching_collapse_backward.hip"]
 HEADER = os.path.join(os.path.dirname(HERE), "include", "aesmc_hip.h")      # the C ABI (csrc/common.hpp includes it)
 ARCH = "gfx950"
 # per translation unit: the generic matrix-core step's product loops are 96 - 128 operand groups of eight v_mfma each, written

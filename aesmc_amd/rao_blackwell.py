@@ -141,9 +141,11 @@ class SwitchingLinearGaussian(torch.nn.Module):
     pi0 [M], Pi [M,M] (rows: from-regime); m0 [D], s0 (one value or D); A [M,D,D], b [M,D], q [M,D]; C [M,Dy,D], d [M,Dy],
     r [M,Dy].  A leading extent of 1 in place of M means shared across regimes.  Every component of y_t is part of the model;
     which of them were measured at a step is the filters' `observed=`, not the model's.  Everything is held as a float64 buffer
-    (`.to(device)` moves the model).  The filters are not differentiable and the buffers are no parameters: a model is
-    learned by EM — `switching_smooth_states` gives the E-step's smoothed moments E[z_t z_t^T | y], E[z_{t+1} z_t^T | y] and
-    regime trajectories, `switching_expected_statistics` reduces them to the expected sufficient statistics per regime and
+    (`.to(device)` moves the model).  The filters are not differentiable — with one exception,
+    `collapsed_switching_log_likelihood`, which takes the ten tensors themselves and returns the collapsed-mixture evidence
+    with its graph (examples/slds_sgd.py) — and the buffers are no parameters: a model is otherwise learned by EM —
+    `switching_smooth_states` gives the E-step's smoothed moments E[z_t z_t^T | y], E[z_{t+1} z_t^T | y] and regime
+    trajectories, `switching_expected_statistics` reduces them to the expected sufficient statistics per regime and
     `switching_m_step` builds a new model from those in closed form (examples/slds_em_full.py; examples/slds_em.py does the
     M-step for Pi, A and b by hand) — or by a gradient optimiser on `switching_score`, the score by Fisher's identity — or
     sampled: `switching_particle_gibbs` draws the regimes, `switching_sample_states` the states along them, and the
@@ -991,18 +993,20 @@ def switching_sample_states(observations, model, regimes, noise=None, observed=N
             "noise": list(stacked_noise.unbind(0)) if noise is None else noise}
 
 
-def _collapsed_forward(provider, ops, observations, num_regimes, order, mask):
+def _collapsed_forward(provider, ops, observations, num_regimes, order, mask, log_priors=None):
     """The forward pass of the collapsed-mixture filters (`testing.switching_collapsed.collapsed_pass`, call for call): per
     step K31 forced (`_conditional_filter`'s shim) on M^2 pair slots (order 2) or M slots (order 1, and step 0), K50 over the
     pairs or the mixing weights, and K50 once more over the M components for the increment and the overall moments.  Returns
     a dict of T-lists: log_mu [B,M], means [B,M,D], covariances [B,M,TD], scores ([B,M,M] indexed (b,j,i), order 2, t >= 1;
     else None), masses ([B,M]; None at step 0), increments [B], overall_mean [B,D], overall_cov [B,TD].  Reads nothing from
-    the device."""
+    the device.  log_priors: (log pi0, log Pi) where the caller forms them itself (`collapsed_switching_log_likelihood`:
+    with a zero gradient at a zero probability); None: torch.log of the operands."""
     M = num_regimes
     B, device = observations[0].size(0), observations[0].device
     edges = (torch.arange(M, dtype=torch.float64, device=device) + 1.0) / M
     forced = dict(ops, cdf0=edges, cdf=edges.expand(M, M).contiguous())
-    log_pi0, log_Pi = torch.log(ops["pi0"]), torch.log(ops["Pi"])      # (-inf where a probability is 0) once
+    # (-inf where a probability is 0) once
+    log_pi0, log_Pi = (torch.log(ops["pi0"]), torch.log(ops["Pi"])) if log_priors is None else log_priors
     transposed = log_Pi.t().unsqueeze(0)                                # [1,j,i] = log Pi[i,j]
     slots = torch.arange(M, dtype=torch.int32, device=device).expand(B, M).contiguous()
     slot_uniforms = (slots.to(torch.float64) + 0.5) / M
@@ -1110,6 +1114,105 @@ def collapsed_switching_filter(observations, model, order=2, observed=None, retu
         inference._discard_pending_flags()
         raise
     return out
+
+
+class _DifferentiableSteps:
+    """What `_collapsed_forward` asks of a provider, answered by the autograd functions of `_ops` around the same provider
+    calls (K31 forced and K50 forward, K52 / K53 and K54 backward)."""
+
+    @staticmethod
+    def switching_kalman_step(model, state, index, uniforms, observation, observed=None):
+        assert index is None
+        return _ops.switching_kalman_step_forced(model, state, uniforms, observation, observed)
+
+    @staticmethod
+    def switching_collapse(means, covs, log_weights):
+        return _ops.switching_collapse(means, covs, log_weights)
+
+
+def _log_probabilities(probabilities):
+    """log p, -inf where p is exactly 0, with a gradient of exactly 0 there: a zero probability is structural (torch.log's
+    backward forms 0 / 0 = NaN at such an entry)."""
+    positive = probabilities > 0
+    return torch.where(positive, torch.log(torch.where(positive, probabilities, torch.ones_like(probabilities))),
+                       torch.full_like(probabilities, -math.inf))
+
+
+def collapsed_switching_log_likelihood(observations, parameters, order=2, observed=None):
+    """The log-evidence of `collapsed_switching_filter` WITH its graph: float64 [batch_size], differentiable in the ten
+    parameters of the model — the one differentiable function of this module.  The collapsed-mixture filter is
+    deterministic (no particles, no random numbers, no resampling), so this is the exact gradient of a deterministic,
+    approximate objective: no genealogy bias and no score-function term.
+
+    parameters: a mapping with the ten names of `PARAMETERS` to float64 tensors on the observations' device, any of which
+    may require grad, in the shapes `SwitchingLinearGaussian` takes (a leading 1 for parameters shared across regimes, one
+    value or D for s0) — the user's own parametrisation (softmax rows, exp of log-scales, the output of a network) stays
+    in torch ops in front of it (examples/slds_sgd.py).  A `SwitchingLinearGaussian` is accepted too and gives a result
+    without a graph.  observations, order, observed: as `collapsed_switching_filter`'s.
+
+    The pass is `collapsed_switching_filter`'s, call for call, with autograd enabled: K31 forced (masked: K39) and K50 run
+    as there, and the value is `torch.equal` to its log_marginal_likelihood; backwards each call is one launch of its
+    adjoint — K52 (K53) `aesmc_switching_kalman_step_backward` with its finishing launch, K54
+    `aesmc_switching_collapse_backward` — which recompute the forward chains (nothing but the calls' inputs is kept) and
+    compute only what `needs_input_grad` asks for.  Shared or expanded parameters get their sums from `expand`'s own
+    backward.  Gradients are with respect to q, r and s0 themselves.  A probability that is exactly 0 in pi0 or Pi is
+    structural: its gradient is exactly 0 and every other gradient stays finite.  First order only.
+
+    Validation goes through `SwitchingLinearGaussian(...).operands()` on detached values (the same errors, one host copy);
+    flags and the NaN check are read once at the end of the forward, as the filter's.  NotImplementedError during a
+    hipGraph capture and inside `distributed.shard_scope`."""
+    from . import distributed
+    name = "collapsed_switching_log_likelihood"
+    if order not in (1, 2):
+        raise ValueError("{}: order must be 1 or 2, got {!r}".format(name, order))
+    if distributed.active_shard() is not None:
+        raise NotImplementedError("aesmc_amd.rao_blackwell: {} inside distributed.shard_scope is not implemented".format(name))
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise NotImplementedError("aesmc_amd.rao_blackwell: {} cannot be captured into a hipGraph (its backward allocates "
+                                  "per call and the flags are read back)".format(name))
+    if isinstance(parameters, SwitchingLinearGaussian):
+        model = parameters
+        given = {key: getattr(model, key) for key in PARAMETERS}
+    else:
+        try:
+            given = {key: parameters[key] for key in PARAMETERS}
+        except (KeyError, TypeError, IndexError):
+            raise ValueError("{}: parameters must be a SwitchingLinearGaussian or a mapping with the keys {}".format(
+                name, ", ".join(PARAMETERS)))
+        for key, value in given.items():
+            if not torch.is_tensor(value) or value.dtype != torch.float64:
+                raise ValueError("{}: parameters[{!r}] must be a float64 tensor, got {}".format(
+                    name, key, value.dtype if torch.is_tensor(value) else type(value).__name__))
+        model = SwitchingLinearGaussian(**{key: value.detach() for key, value in given.items()})
+    provider = _kernels.get()
+    try:
+        with _syncfree.scope():
+            with torch.no_grad():
+                checked, device, mask = _prepare_collapsed(name, provider, observations, model,
+                                                           model.num_regimes if order == 2 else 1, observed)
+            for key, value in given.items():
+                if value.device != device:
+                    raise ValueError("{}: parameters[{!r}] is on {}, the observations on {}".format(name, key, value.device,
+                                                                                                  device))
+            # the validated operands, rebuilt from the given tensors so that the graph reaches them: the same values
+            ops = {key: given[key].reshape(-1).expand(checked[key].shape).contiguous() if key == "s0" else
+                   given[key].expand(checked[key].shape).contiguous() for key in PARAMETERS}
+            ops.update(cdf0=checked["cdf0"], cdf=checked["cdf"])
+            forward = _collapsed_forward(_DifferentiableSteps, ops, observations, model.num_regimes, order, mask,
+                                         log_priors=(_log_probabilities(ops["pi0"]), _log_probabilities(ops["Pi"])))
+            total = forward["increments"][0]
+            for increment in forward["increments"][1:]:
+                total = total + increment
+            _finish_conditional(name, provider, device, False, total.detach())
+    except BaseException:
+        inference._discard_pending_flags()
+        raise
+    return total
+
+
+def collapsed_switching_loss(observations, parameters, order=2, observed=None):
+    """Minus the batch mean of `collapsed_switching_log_likelihood`: a scalar to minimise."""
+    return -collapsed_switching_log_likelihood(observations, parameters, order=order, observed=observed).mean()
 
 
 def collapsed_switching_smooth(observations, model, observed=None):

@@ -107,7 +107,10 @@ extern "C" {
  *                ancestor's posterior row and one slot pinned — look-ahead particle Gibbs on the regimes);
  *                aesmc_switching_collapse, aesmc_switching_pair_smooth (K50, K51: the moment-matching collapse of Gaussian
  *                mixtures and a Rauch-Tung-Striebel step between mixture components — the deterministic collapsed-mixture
- *                filter and smoother, GPB2 / Kim's filter and IMM).
+ *                filter and smoother, GPB2 / Kim's filter and IMM);
+ *                aesmc_switching_kalman_step_backward, aesmc_switching_kalman_masked_step_backward,
+ *                aesmc_switching_backward_workspace_bytes, aesmc_switching_collapse_backward (K52, K53, K54: the adjoints
+ *                of K31 / K39 with the regime given and of K50 — the gradient of the collapsed-mixture evidence).
  *   400 (0.4.0)  aesmc_affine_chain grew `pairs_in` / `pairs_out` (a run of backward steps builds the weight pairs once);
  *                added aesmc_wide_adjoint_tile, aesmc_wide_adjoint_scale, aesmc_wide_adjoint_merge
  *   300 (0.3.0)  added aesmc_affine_normal_propagate_drawn_paired, aesmc_affine_weight_pairs,
@@ -1134,6 +1137,77 @@ int aesmc_switching_collapse(const double *mean, int64_t mean_group_stride, cons
 int aesmc_switching_pair_smooth(const aesmc_switching_model *model, const double *mean, const double *cov,
                                 const double *mean_next, const double *cov_next, double *mean_out, double *cov_out, int64_t B,
                                 void *stream);
+
+/* K52 — the adjoint of one step of K31 in the forms the collapsed-mixture filter uses: the regime GIVEN (`regime`, what K31
+ * wrote to regime_out: it carries no gradient, so neither the cumulative rows nor the uniforms are read), no ancestors, later
+ * steps (mean_in and cov_in given) and step 0 (both NULL: m- = m0, P- = diag(s0^2)).  One lane per slot recomputes the step's
+ * forward chains in K31's order (predict, innovation e, U = C P-, S, its factor Lam, v = Lam^-1 e, V = Lam^-1 U) and
+ * then, with g = grad_log_weight, mu = grad_mean and G the dense symmetric form of grad_cov (packed covariances: the gradient
+ * with respect to a packed element is the derivative of the function of the packed vector, so an off-diagonal element
+ * stands for both positions — it enters halved and leaves doubled; what autograd through an unpacking gives):
+ *   z = V mu;  alpha = Lam^-T v;  t = Lam^-T z;  ebar = t - g alpha;      Y = v mu^T - 2 V G;  Ubar = Lam^-T Y
+ *   Shat = g/2 (v v^T - I) - sym(z v^T) + (V G) V^T;      Sbar = Lam^-T Shat Lam^-1   (triangular solves with the factor; S^-1
+ *                                                                                     is never formed)
+ *   Hhat = Ubar + Sbar C;      Pbar- = G + sym(C^T Hhat);      mbar- = mu - C^T ebar
+ *   grad_C = (Hhat + Sbar C) P- - ebar m-^T;   grad_d = -ebar;   grad_r = 2 r o diag Sbar
+ *   later steps:  grad_A = 2 Pbar- (A P) + mbar- m^T;  grad_b = mbar-;  grad_q = 2 q o diag Pbar-;
+ *                 grad_mean_in = A^T mbar-;  grad_cov_in = A^T Pbar- A (packed)
+ *   step 0:       grad_m0 = mbar-;  grad_s0 = 2 s0 o diag Pbar-
+ * (gradients with respect to q, r and s0 themselves, not their squares; y gets none).
+ *   regime int32 [B,K];  mean_in float64 [B,K,D], cov_in float64 [B,K,D(D+1)/2] or both NULL;  y [B,Dy] of y_dtype;
+ *   grad_mean [B,K,D], grad_cov [B,K,D(D+1)/2], grad_log_weight [B,K] float64: the arriving gradients;
+ *   outputs, each of which may be NULL (not wanted, not computed): grad_mean_in [B,K,D], grad_cov_in [B,K,D(D+1)/2] (per
+ *   slot; later steps only), grad_m0 [D], grad_s0 [D] (step 0 only), grad_A [M,D,D], grad_b [M,D], grad_q [M,D],
+ *   grad_C [M,Dy,D], grad_d [M,Dy], grad_r [M,Dy] (the sums over the slots of each regime; at step 0 the first three are zero).
+ * The sums use no floating-point atomics: every slot leaves its row in `workspace`
+ * (aesmc_switching_backward_workspace_bytes(B, K, D, Dy) bytes, 8-byte aligned; needed when any of the eight reduced outputs
+ * is wanted) and two finishing launches add them per regime and element: the slots are cut into min(64, ceil(B K / 256))
+ * consecutive parts; per part, sixteen consecutive runs of slots are added in ascending order and then the sixteen sums in
+ * ascending order; then the parts in ascending order.  The same inputs and extents give the same bits.
+ * A slot whose three arriving gradients are all exactly zero contributes exactly nothing and writes exact zeros to its rows
+ * of the per-slot outputs, even where its recomputed forward is NaN (K31 under an impossible regime).  A regime outside
+ * [0, M) raises AESMC_FLAG_INDEX_OUT_OF_RANGE, writes NaN to the slot's per-slot rows and adds nothing to any sum.  A pivot
+ * that is not positive gives NaN (per slot and in the sums).
+ * NULL model, regime, y or arriving gradients, only one of mean_in and cov_in, all outputs NULL, grad_mean_in or grad_cov_in
+ * at step 0, grad_m0 or grad_s0 at a later step, misaligned pointers, negative B or K, M, D or Dy below 1 and an output that
+ * is an input or another output return AESMC_ERR_INVALID_ARGUMENT; a reduced output without a workspace, or (non-empty
+ * launches) with too small a one, AESMC_ERR_WORKSPACE; B K == 0 is a no-op; D, Dy or M above K31's limits or B K rows beyond
+ * 32-bit element arithmetic AESMC_ERR_UNSUPPORTED.  Every check runs before any launch.  `flags` may be NULL. */
+int64_t aesmc_switching_backward_workspace_bytes(int64_t B, int64_t K, int64_t D, int64_t Dy);
+int aesmc_switching_kalman_step_backward(int y_dtype, const aesmc_switching_model *model, const int32_t *regime,
+                                         const double *mean_in, const double *cov_in, const void *y, const double *grad_mean,
+                                         const double *grad_cov, const double *grad_log_weight, double *grad_mean_in,
+                                         double *grad_cov_in, double *grad_m0, double *grad_s0, double *grad_A, double *grad_b,
+                                         double *grad_q, double *grad_C, double *grad_d, double *grad_r, void *workspace,
+                                         int64_t workspace_bytes, int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K53 — K52 under K39's mask (`observed` uint8 [B,Dy], nonzero = observed; not NULL): the adjoint of
+ * aesmc_switching_kalman_masked_step with the regime given.  A deleted component's e, row of U and row and column of S are
+ * selected as K39 selects them (its y is never read into a chain and may be NaN), its diagonal entry of Shat is 0, and it
+ * contributes exactly nothing to that row's gradients of C, d and r.  Everything else as K52. */
+int aesmc_switching_kalman_masked_step_backward(int y_dtype, const aesmc_switching_model *model, const int32_t *regime,
+                                                const double *mean_in, const double *cov_in, const void *y,
+                                                const uint8_t *observed, const double *grad_mean, const double *grad_cov,
+                                                const double *grad_log_weight, double *grad_mean_in, double *grad_cov_in,
+                                                double *grad_m0, double *grad_s0, double *grad_A, double *grad_b, double *grad_q,
+                                                double *grad_C, double *grad_d, double *grad_r, void *workspace,
+                                                int64_t workspace_bytes, int32_t *flags, int64_t B, int64_t K, void *stream);
+
+/* K54 — the adjoint of K50.  K50's inputs (the same layouts and group strides) and the gradients arriving at its outputs,
+ * grad_log_mass [B,G], grad_mean_out [B,G,D], grad_cov_out [B,G,D(D+1)/2] (packed, as K52's); with w_n, mean and
+ * d_n = m_n - mean recomputed by K50's chains, abar, mu, c the three arriving gradients of the group:
+ *   grad_cov_n = w_n c;      grad_mean_n = w_n (mu + 2 sym(c) d_n);      omega_n = <mu, d_n> + <c, P_n + d_n d_n^T>  (packed sums)
+ *   grad_log_weight_n = w_n (abar + omega_n - sum_k w_k omega_k)
+ * Outputs, each of which may be NULL: grad_log_weight [B,G,N]; grad_mean and grad_cov in the layout of mean and cov — dense
+ * [B,G,N,.], or with group stride 0 [B,N,.]: the SUM over the row's G groups, taken in ascending group order inside one
+ * lane.  A component of weight -inf is not read and gets gradient exactly zero; a group whose every weight is -inf gives
+ * zeros; a NaN weight gives NaN for its group (stride 0: for the row's components).  No atomics: the same inputs give the
+ * same bits.  Status codes as K50's; the two strides are both 0 or both dense; all three outputs NULL is
+ * AESMC_ERR_INVALID_ARGUMENT. */
+int aesmc_switching_collapse_backward(const double *mean, int64_t mean_group_stride, const double *cov, int64_t cov_group_stride,
+                                      const double *log_weight, const double *grad_log_mass, const double *grad_mean_out,
+                                      const double *grad_cov_out, double *grad_log_weight, double *grad_mean, double *grad_cov,
+                                      int64_t B, int64_t G, int64_t N, int64_t D, void *stream);
 
 /* K6— reparameterised Normal draw  out[b,k,j] = loc[b,k,j] + eps[b,k,j] * scale[b,k,j].
  *
